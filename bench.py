@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- env-steps/s of the MI355X vector-environment engine (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--env CartPole-v1] [--num-envs 65536] [--inner 128]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--env CartPole-v1] [--num-envs 65536] [--inner 128] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and nothing more: set up, clock spin-up and W warm-up launches, EXACTLY K timed launches, the
+line (`value`, `ms_per_step`; the roofline from the recorded traffic profile).  --dump-outputs DIR writes what the last timed launch computed
+(a fixed, seeded sample of the sub-environments: dump_outputs).  --full adds everything else described below: the digest of the first timed
+launch and the oracle's verdict on it, the sustained figure, the live PMC passes, the CPU baseline and the sidecar of scripts/bench_extras.py.
 
 Primary workload (BASELINE.json configs[1]): CartPole-v1, num_envs = 65536 PER GPU, random policy.  One bench "step" is one launch of the
 hot path over the whole batch: `mi_rollout(inner)` = `inner` lockstep vector steps of all sub-environments with the random policy
@@ -147,6 +152,35 @@ def cpu_baseline(env_id, num_envs, budget_s=12.0, workers=None):
             "usable_cpus_source": why, "per_core_value": steps / dt / workers,
             "sample": f"{env_id} num_envs={num_envs} over {workers} single-threaded C-oracle process(es), same random policy, same outputs written, "
                       f"{steps} env-steps in {dt:.1f} s"}
+
+
+DUMP_BYTES = 48 << 20  # --dump-outputs writes at most this much over all ranks; beyond it, a seeded sample of the sub-environments
+DUMP_SEED = 20240611
+DUMP_NAMES = ("actions", "observations", "rewards", "terminated", "truncated")
+
+
+def dump_outputs(out_dir, traj, rank=0, world=1, budget=DUMP_BYTES):
+    """Write one launch's trajectory (actions, observations, rewards, terminated, truncated: time-major, sub-environment second; torch tensors or
+    NumPy arrays) as out_dir/<name>.npy: float32 stays float32, bool becomes float32, everything else float64.  When all sub-environments do not fit
+    into this rank's share of `budget`, the same seeded sample of them is taken every time (sorted); env_index.npy holds their global indices.
+    At world size > 1 every rank writes its own files, named rank<r>_<name>.npy."""
+    itemsize = [4 if str(a.dtype).rsplit(".", 1)[-1] in ("float32", "bool") else 8 for a in traj]
+    N = int(traj[0].shape[1])
+    per_env = 8 + sum(s * int(np.prod(a.shape)) // N for s, a in zip(itemsize, traj))
+    n = max(1, min(N, (budget // max(1, world)) // per_env))
+    idx = np.arange(N) if n == N else np.sort(np.random.default_rng(DUMP_SEED).choice(N, n, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    prefix = f"rank{rank}_" if world > 1 else ""
+    for name, s, a in zip(DUMP_NAMES, itemsize, traj):
+        if hasattr(a, "index_select"):  # a device tensor: only the sample crosses to the host
+            import torch
+
+            a = a.index_select(1, torch.as_tensor(idx, device=a.device)).cpu().numpy()
+        else:
+            a = np.asarray(a)[:, idx]
+        np.save(os.path.join(out_dir, f"{prefix}{name}.npy"), np.ascontiguousarray(a, dtype=np.float32 if s == 4 else np.float64))
+    np.save(os.path.join(out_dir, f"{prefix}env_index.npy"), (idx + rank * N).astype(np.float64))
+    return idx
 
 
 def trajectory_digest(traj) -> str:
@@ -474,6 +508,10 @@ class Config:
         self.env._bind_stream()
         self.eng.action_seed(_native.pcg_words(self.env.action_space.np_random))
 
+    def last_trajectory(self, K):
+        """The buffers the last of K timed launches wrote (the first one writes its own set)."""
+        return (self.first if K == 1 else self.rest)[0]
+
     def launch(self, bufs=None):
         p = (bufs or self.rest)[1]
         self.eng.rollout(self.inner, None, p[0], p[1], p[2], p[3], p[4])
@@ -588,8 +626,11 @@ def main(argv=None, harness=None):
     ap.add_argument("--num-envs", type=int, default=65536, help="sub-environments PER GPU")
     ap.add_argument("--inner", type=int, default=128, help="vector steps fused into one launch (one bench step)")
     ap.add_argument("--spinup", type=float, default=0.5, help="seconds of untimed launches before the warm-up, so that the timed region runs at sustained clocks (0 = off)")
-    ap.add_argument("--sustained", type=float, default=1.5, help="seconds of back-to-back launches for sustained_value (0 = skip)")
-    ap.add_argument("--pmc", choices=["auto", "full", "off"], default="auto", help="live rocprofv3 counter passes on child invocations (off = recorded values only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write what the last timed launch computed as DIR/<name>.npy (a seeded sample of the sub-environments beyond 48 MiB)")
+    ap.add_argument("--full", action="store_true", help="also the digest and oracle check of the first timed launch, the sustained figure, live PMC passes, the CPU "
+                                                        "baseline and scripts/bench_extras.py (the options below narrow these down)")
+    ap.add_argument("--sustained", type=float, default=1.5, help="--full: seconds of back-to-back launches for sustained_value (0 = skip)")
+    ap.add_argument("--pmc", choices=["auto", "full", "off"], default="auto", help="--full: live rocprofv3 counter passes on child invocations (off = recorded values only)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-verify", action="store_true", help="skip the oracle comparison of the first timed launch (the digest is still reported)")
     ap.add_argument("--no-api", action="store_true", help="extras: skip the per-launch step() API measurements")
@@ -603,6 +644,8 @@ def main(argv=None, harness=None):
     ap.add_argument("--cpu-budget", type=float, default=12.0, help=argparse.SUPPRESS)
     ap.add_argument("--pilot-seconds", type=float, default=1.0, help=argparse.SUPPRESS)
     args = ap.parse_args(argv)
+    if args.steps is not None and args.steps < 1 or args.warmup is not None and args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")  # (already exported on the GPU boxes: the host driver only supports dmabuf IPC, which RCCL needs across ranks)
     import torch
@@ -681,22 +724,25 @@ def main(argv=None, harness=None):
         return 0
     cfg.rearm()  # known start of the timed region: its first launch is the known-answer rollout (output_sha256 / verified)
     elapsed, kernel_s, st = cfg.timed(K, sync_all)
+    if args.dump_outputs:  # before anything else launches into the same buffers
+        dump_outputs(args.dump_outputs, cfg.last_trajectory(K), rank, world)
     from gymnasium_amd import distributed as gd
 
     red = gd.reduce_statistics(st, elapsed_s=elapsed, device=dev)  # the only collective: a few dozen bytes over RCCL/xGMI
     elapsed = red["elapsed_s"]
     env_steps, episodes, return_sum = float(red["env_steps"]), float(red["episodes"]), float(red["return_sum"])
 
-    # ---- the first timed launch: digest on every rank, oracle comparison (the checker; never the thing measured) ----------------------
-    traj = cfg.host_trajectory()
-    digest = trajectory_digest(traj)
-    verified = None
-    if not args.no_verify:
-        try:
-            verified = oracle_check(cfg, traj)
-        except Exception as e:
-            verified = {"ok": None, "error": f"{type(e).__name__}: {e}"[:200]}
-    del traj
+    # ---- --full: the first timed launch: digest on every rank, oracle comparison (the checker; never the thing measured) ---------------
+    digest, verified = None, None
+    if args.full:
+        traj = cfg.host_trajectory()
+        digest = trajectory_digest(traj)
+        if not args.no_verify:
+            try:
+                verified = oracle_check(cfg, traj)
+            except Exception as e:
+                verified = {"ok": None, "error": f"{type(e).__name__}: {e}"[:200]}
+        del traj
     if verified is not None and verified.get("ok") is not None and args.env in MJ_IDS and gpu:
         try:  # ... and ten more launches from where the timed region left the robots (contacts, resets, TimeLimit), window by window
             later = mujoco_window_check(cfg)
@@ -706,15 +752,15 @@ def main(argv=None, harness=None):
             verified["later_windows"] = {"ok": None, "error": f"{type(e).__name__}: {e}"[:200]}
     # ---- sustained: the same launch back to back for >= args.sustained seconds (all ranks, same barrier discipline) ----------------
     sustained = None
-    if args.sustained > 0 and elapsed >= 0.8:  # (elapsed is the all-reduced maximum: every rank takes the same branch)
+    if args.full and args.sustained > 0 and elapsed >= 0.8:  # (elapsed is the all-reduced maximum: every rank takes the same branch)
         sustained = {"value": env_steps / elapsed, "launches": K, "seconds": elapsed, "avg_kernel_ms": kernel_s * 1e3, "note": "the timed region itself"}
-    elif args.sustained > 0:
+    elif args.full and args.sustained > 0:
         Ks = max(K, int(args.sustained / max(kernel_s, 1e-7)) + 1)
         el_s, k_s, st_s = cfg.timed(Ks, sync_all)
         red_s = gd.reduce_statistics(st_s, elapsed_s=el_s, device=dev)
         sustained = {"value": float(red_s["env_steps"]) / red_s["elapsed_s"], "launches": Ks, "seconds": red_s["elapsed_s"], "avg_kernel_ms": k_s * 1e3}
     # What the collective itself proves about the job (n_gpus below is NOT read from the environment): gymnasium_amd/distributed.py census()
-    cen = gd.census(rank, local_rank, device=dev, extra={"output_sha256": digest[:16], "verified": None if verified is None else verified["ok"]})
+    cen = gd.census(rank, local_rank, device=dev, extra={"output_sha256": digest and digest[:16], "verified": None if verified is None else verified["ok"]})
     ranks_seen = cen["ranks"]
     single = rank == 0 and world == 1 and gpu
 
@@ -729,9 +775,9 @@ def main(argv=None, harness=None):
                                    f"fused rollout of {inner} vector steps per launch, trajectory (actions, obs, rewards, terminated, truncated) written to HBM",
                        "env": args.env, "env_kwargs": env_kwargs, "num_envs_per_gpu": N, "vector_steps_per_launch": inner,
                        "parallelism": f"env-sharded x{world} (no data-path collective)"},
-            "roofline": cfg.roofline(kernel_s, live=single and args.pmc != "off"),
+            "roofline": cfg.roofline(kernel_s, live=single and args.full and args.pmc != "off"),
             "cpu_baseline": None,
-            "output_sha256": digest, "verified": verified, "verified_all_ranks": (None if args.no_verify else (False if any(v is False for v in all_ok) else (True if all(v is True for v in all_ok) else None))),
+            "output_sha256": digest, "verified": verified, "verified_all_ranks": (None if args.no_verify or not args.full else (False if any(v is False for v in all_ok) else (True if all(v is True for v in all_ok) else None))),
             "rccl_ranks": ranks_seen, "world_size_env": world, "distinct_devices": cen["distinct_devices"],
             "devices": [{k: d.get(k) for k in ("rank", "uuid", "output_sha256", "verified")} for d in cen["devices"]],
             "episodes": episodes, "mean_episode_return": (return_sum / episodes) if episodes else None,
@@ -741,13 +787,13 @@ def main(argv=None, harness=None):
     cfg.close()
 
     # ---- CPU leg: the oracle port on rank 0, at N = 1 only (the contract; --cpu-baseline-at-any-n for the dry runs of the N > 1 flow) ------------------
-    if rank == 0 and not args.no_cpu_baseline and (world == 1 or args.cpu_baseline_at_any_n):
+    if rank == 0 and args.full and not args.no_cpu_baseline and (world == 1 or args.cpu_baseline_at_any_n):
         # the whole batch of one GPU on every host core (MuJoCo: a bounded sample of 64 sub-environments per core -- the oracle's per-env cost
         # does not depend on the batch size)
         n_cpu = min(N, 64 * usable_cpus()[0]) if args.env in MJ_COOP else N
         result["cpu_baseline"] = cpu_baseline(args.env, n_cpu, budget_s=args.cpu_budget)
     # ---- everything else (rank 0, one GPU): a child process, a sidecar file, headline values in the line ------------------------------------
-    if single and not args.no_secondary:
+    if single and args.full and not args.no_secondary:
         result["secondary"] = run_extras(args, args.full_out, result)
         result["full"] = os.path.relpath(args.full_out, ROOT)
     if world > 1:

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Everything bench.py's one line leaves out, measured on ONE GPU by a child process of `python bench.py --gpus 1` (or by hand):
+"""Everything bench.py's one line leaves out, measured on ONE GPU by a child process of `python bench.py --gpus 1 --full` (or by hand):
 
     python scripts/bench_extras.py --out gpurun_out/bench_full.json [--primary primary.json] [--pmc auto|full|off] [--budget 150]
 

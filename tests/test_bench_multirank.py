@@ -46,7 +46,7 @@ def _run(world, extra, num_envs=256, inner=8):
 @pytest.mark.parametrize("world", [2, 3])
 def test_default_flags_pilot_sets_k_on_every_rank(world):
     """No --steps: K comes from the pilot, all-reduced MAX over the ranks; a timed region that is long enough IS the sustained figure."""
-    r = _run(world, ["--pilot-seconds", "0.9", "--sustained", "0.5"])
+    r = _run(world, ["--full", "--pilot-seconds", "0.9", "--sustained", "0.5"])
     assert r["n_gpus"] == world and r["scaling"] == "weak" and r["higher_is_better"] is True and r["unit"] == "env-steps/s"
     # the rank count comes out of the collective, and every rank reported its own device
     assert r["rccl_ranks"] == world == r["world_size_env"] and r["distinct_devices"] == world and sorted(d["rank"] for d in r["devices"]) == list(range(world))
@@ -67,7 +67,7 @@ def test_default_flags_pilot_sets_k_on_every_rank(world):
 
 def test_driver_style_explicit_steps_takes_the_separate_sustained_loop():
     """--steps K --warmup W as the driver passes them: EXACTLY K timed launches; a short timed region is followed by the separate sustained loop."""
-    r = _run(2, ["--steps", "6", "--warmup", "2", "--sustained", "0.3"])
+    r = _run(2, ["--full", "--steps", "6", "--warmup", "2", "--sustained", "0.3"])
     assert r["steps"] == 6 and r["warmup"] == 2 and r["n_gpus"] == 2
     assert r["sustained"]["launches"] > 6 and r["sustained"]["seconds"] > 0  # (a launch count, not a wall-clock threshold: the oracle's speed varies with the host's load)
     assert r["episodes"] > 0 and 9.0 < r["mean_episode_return"] < 60.0  # CartPole under the random policy: ~22 steps per episode
@@ -76,7 +76,7 @@ def test_driver_style_explicit_steps_takes_the_separate_sustained_loop():
 def test_baseline_config4_command_line_humanoid_sharded():
     """BASELINE.json configs[4] -- Humanoid-v5 sharded over the ranks -- with the driver's flags (`--env Humanoid-v5 --num-envs N --inner 4`): the MuJoCo
     branch of the line (algorithmic bytes of a cooperative robot, `bound: "valu"`, the CPU leg's bounded sample) on two gloo ranks."""
-    r = _run(2, ["--env", "Humanoid-v5", "--steps", "2", "--warmup", "1", "--sustained", "0", "--cpu-baseline-at-any-n"], num_envs=6, inner=2)
+    r = _run(2, ["--full", "--env", "Humanoid-v5", "--steps", "2", "--warmup", "1", "--sustained", "0", "--cpu-baseline-at-any-n"], num_envs=6, inner=2)
     assert r["n_gpus"] == 2 and r["rccl_ranks"] == 2 and r["config"]["env"] == "Humanoid-v5" and r["config"]["num_envs_per_gpu"] == 6
     lanes = 2 * 6 * 2 * r["steps"]
     assert 0 < r["value"] * r["ms_per_step"] * 1e-3 * r["steps"] <= lanes * (1 + 1e-9)  # (no episode ends in 4 steps: exactly `lanes` env-steps, up to rounding)
@@ -89,7 +89,7 @@ def test_baseline_config4_at_its_real_world_size():
     """BASELINE.json configs[4] as the driver will launch it -- `torchrun --nproc-per-node 8 bench.py --gpus 8 --env Humanoid-v5 --num-envs 32768 --inner 4` -- at
     world size 8, with a tiny shard per rank: eight ranks in the collective, eight distinct digests (every rank owns its own global
     env indices), every rank's first timed launch verified against the oracle, one line under 4 KB."""
-    r = _run(8, ["--env", "Humanoid-v5", "--steps", "2", "--warmup", "1", "--sustained", "0"], num_envs=2, inner=4)
+    r = _run(8, ["--full", "--env", "Humanoid-v5", "--steps", "2", "--warmup", "1", "--sustained", "0"], num_envs=2, inner=4)
     assert r["n_gpus"] == 8 and r["rccl_ranks"] == 8 and r["world_size_env"] == 8 and r["distinct_devices"] == 8
     assert sorted(d["rank"] for d in r["devices"]) == list(range(8)) and len({d["output_sha256"] for d in r["devices"]}) == 8
     assert r["verified_all_ranks"] is True and all(d["verified"] is True for d in r["devices"])

@@ -46,7 +46,7 @@ def _check_contract(r, K, W):
 
 
 def test_short_explicit_run():
-    r = _run(["--gpus", "1", "--steps", "5", "--warmup", "2", "--no-extras", "--pmc", "off", "--sustained", "0", "--cpu-budget", "2"], 600)
+    r = _run(["--gpus", "1", "--steps", "5", "--warmup", "2", "--full", "--no-extras", "--pmc", "off", "--sustained", "0", "--cpu-budget", "2"], 600)
     _check_contract(r, 5, 2)
     assert r["clock_spinup"]["seconds"] == 0.5 and r["clock_spinup"]["launches"] > 0  # untimed, before the warm-up
     cb = r["cpu_baseline"]
@@ -58,8 +58,8 @@ def test_short_explicit_run():
 
 
 def test_the_drivers_own_command_line():
-    """`python bench.py --gpus 1 --steps 20 --warmup 5` with everything on: the sidecar file is written, the line carries the headline values only."""
-    r = _run(["--gpus", "1", "--steps", "20", "--warmup", "5"], 900)
+    """`python bench.py --gpus 1 --steps 20 --warmup 5 --full` with everything on: the sidecar file is written, the line carries the headline values only."""
+    r = _run(["--gpus", "1", "--steps", "20", "--warmup", "5", "--full"], 900)
     _check_contract(r, 20, 5)
     assert r["roofline"]["traffic"] is None or 0.8 < r["roofline"]["traffic_over_algorithmic"] < 1.5
     sec = r["secondary"]
@@ -77,3 +77,28 @@ def test_the_drivers_own_command_line():
             assert line["output_sha256"] == ref2[key], line["env"]
             seen += 1
     assert seen >= 3  # configs[2]; plus the ToyText lines when the run was young enough to measure them
+
+
+def test_plain_run_is_lean_and_dumps_its_last_launch(tmp_path):
+    """The plain command (no --full): the headline fields and nothing that takes runs of its own; with --steps 1 the last timed launch is the
+    known-answer one, so the dumped sample must equal the oracle's rollout from reset(seed=0) under the policy seeded 0."""
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    r = _run(["--gpus", "1", "--steps", "1", "--warmup", "5", "--dump-outputs", str(tmp_path)], 600)
+    assert r["n_gpus"] == 1 and r["steps"] == 1 and r["warmup"] == 5 and r["metric"] == bench.METRIC and r["unit"] == "env-steps/s"
+    assert r["higher_is_better"] is True and r["dtype"] == "f64" and r["value"] > 1e9
+    assert abs(r["ms_per_step"] - 65536 * 128 / r["value"] * 1e3) / r["ms_per_step"] < 0.2
+    assert r["cpu_baseline"] is None and r["verified"] is None and r["output_sha256"] is None and r["sustained"] is None and "secondary" not in r
+    assert r["roofline"]["bound"] == "hbm" and r["roofline"]["algorithmic_bytes_per_launch"] == (34 * 128 + 96) * 65536
+    files = sorted(os.listdir(tmp_path))
+    assert files == sorted(f"{n}.npy" for n in (*bench.DUMP_NAMES, "env_index"))
+    assert sum(os.path.getsize(os.path.join(tmp_path, f)) for f in files) <= 64 << 20
+    idx = np.load(os.path.join(tmp_path, "env_index.npy")).astype(np.int64)
+    assert 1000 < len(idx) < 65536 and np.all(np.diff(idx) > 0)
+    ref = bench.oracle_trajectory("CartPole-v1", 65536, 128, offset=0, policy_seed=0)
+    for name, x in zip(bench.DUMP_NAMES, ref):
+        d = np.load(os.path.join(tmp_path, f"{name}.npy"))
+        assert d.dtype in (np.float32, np.float64) and np.array_equal(d, x[:, idx].astype(d.dtype)), name
