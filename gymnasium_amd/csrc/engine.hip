@@ -769,6 +769,11 @@ struct ActionStream {
     uint64_t state_hi, state_lo, inc_hi, inc_lo;
     const PcgJump *pow2;  // [64] device
     PcgJump jump_n;
+    // the classic kinds' sampling rollouts (rollout_kernel, rollout_duo_kernel): the per-lane states (act_lane[2][N], act_init_kernel's meaning)
+    // the launch leaves behind -- a lane writes its state after the last jump, i.e. its state for the position T * N draws on.  nullptr: none
+    // (the other kernels; a launch inside a stream capture).  lane_valid: they hold the launch's start already, so no skip-ahead from state_hi / lo.
+    uint64_t *lane;
+    int lane_valid;
 };
 
 struct RolloutPtrs {
@@ -818,11 +823,14 @@ __global__ __launch_bounds__(kBlock) void rollout_kernel(DevEnv d, RolloutPtrs i
         u128 astate = 0;
         const u128 ainc = make_u128(as.inc_hi, as.inc_lo);
         if (SAMPLE) {
-            // skip ahead by (i + 1) draws: one affine map per set bit of (i + 1)
-            astate = make_u128(as.state_hi, as.state_lo);
-            uint32_t delta = (uint32_t)i + 1u;
-            for (int j = 0; delta; j++, delta >>= 1)
-                if (delta & 1u) astate = as.pow2[j].mult * astate + as.pow2[j].plus;
+            if (as.lane_valid) {  // the lane's state from the last launch (or act_init_kernel)
+                astate = make_u128(as.lane[i], as.lane[(size_t)d.N + i]);
+            } else {  // skip ahead by (i + 1) draws: one affine map per set bit of (i + 1)
+                astate = make_u128(as.state_hi, as.state_lo);
+                uint32_t delta = (uint32_t)i + 1u;
+                for (int j = 0; delta; j++, delta >>= 1)
+                    if (delta & 1u) astate = as.pow2[j].mult * astate + as.pow2[j].plus;
+            }
         }
         (void)ainc;
         const size_t N = (size_t)d.N;
@@ -858,6 +866,11 @@ __global__ __launch_bounds__(kBlock) void rollout_kernel(DevEnv d, RolloutPtrs i
             for (int k = 0; k < E::NDRAWS; k++) q.rng.unstep();
         }
         store_rng_state(d, i, q.rng);
+        if (SAMPLE && as.lane) {  // (the addresses from an opaque copy of i: the compiler otherwise keeps the load's 64-bit addresses live through the loop)
+            int w = i;
+            hold_opaque(w);
+            as.lane[w] = (uint64_t)(astate >> 64), as.lane[(size_t)d.N + w] = (uint64_t)astate;
+        }
     }
     block_accumulate(d, st);
 }
@@ -889,11 +902,21 @@ struct DuoTraits {
 #endif
 };
 
+// E::step_hooked (CartPole): the step's own rare branch also runs a caller's rare work (envs_classic.h)
+template <class E, class = void>
+struct HasRareHook : std::false_type {};
+template <class E>
+struct HasRareHook<E, std::void_t<decltype(E::RARE_HOOK)>> : std::integral_constant<bool, E::RARE_HOOK> {};
+
 // env role: lane_step_fused<E, false> without the episode statistics; `bits`: 1 terminated, 2 truncated, 4 this was the autoreset step
 template <class E>
 MI_DEV void duo_env_step(const DevEnv &d, Lane<E> &L, typename E::Act a, ResetQueue<E> &q, float obs[E::OBS], double &reward, uint32_t &bits) {
     const bool resetting = (L.flags & kNeedsReset) != 0;
-    if (__builtin_expect(resetting && !q.have, 0)) q.refill();  // rare: two episode ends within one refill period
+    // rare: two episode ends within one refill period.  The refill only feeds the reset select after the step, so an environment with a rare
+    // branch of its own takes it there, behind ONE exec-mask branch per step instead of two.
+    const bool refill = resetting && !q.have;
+    constexpr bool HOOK = HasRareHook<E>::value && !E::SPLIT_TERMINAL && !E::AUX_REWARD;
+    if (!HOOK && __builtin_expect(refill, 0)) q.refill();
     const double (&rs)[E::S] = q.rs;
     const uint32_t rflags = ResetQueue<E>::reset_flags(L.flags & ~kNeedsReset);
     double rew;
@@ -908,6 +931,10 @@ MI_DEV void duo_env_step(const DevEnv &d, Lane<E> &L, typename E::Act a, ResetQu
     } else if constexpr (E::AUX_REWARD) {  // the aux role evaluates the reward (from E::aux_pre of the state before this step): the dynamics alone
         E::advance(L.s, a, d.P, L.trig);
         rew = 0.0, te = false;
+    } else if constexpr (HOOK) {
+        E::step_hooked(L.s, sflags, a, d.P, rew, te, L.trig, refill, [&]() __attribute__((always_inline)) {
+            if (refill) q.refill();
+        });
     } else {
         E::step(L.s, sflags, a, d.P, rew, te, L.trig);
     }
@@ -980,6 +1007,9 @@ __global__ __launch_bounds__(kDuoBlock) void rollout_duo_kernel(DevEnv d, Rollou
     __shared__ MI_DUO_FLAG_T sh_bits[DERIVE ? 1 : 2][DERIVE ? 1 : C][DERIVE ? 1 : kBlock];
     __shared__ uint64_t sh_c[4][kBlock / 64];
     __shared__ double sh_r[kBlock / 64];
+#ifdef MI_DUO_TIMING
+    const unsigned long long t_begin = __builtin_readcyclecounter();  // (the prologue: tables, the roles' loads, the policy's start state)
+#endif
     tables_init<E>();
     const int role = threadIdx.x / kBlock;  // wavefronts j (env), j + 4 (aux / policy) and j + 8 (book) share a SIMD and 64 sub-environments
     const bool is_env = role == 0, is_policy = role == 1, is_book = role == ROLES - 1;
@@ -1012,15 +1042,24 @@ __global__ __launch_bounds__(kDuoBlock) void rollout_duo_kernel(DevEnv d, Rollou
             ep_len_start = (start_flags & kNeedsReset) ? 0 : ep_len;
         }
         if (is_policy) {
-            astate = make_u128(as.state_hi, as.state_lo);  // skip ahead by (i + 1) draws: one affine map per set bit of (i + 1)
-            uint32_t delta = (uint32_t)i + 1u;
-            for (int j = 0; delta; j++, delta >>= 1)
-                if (delta & 1u) astate = as.pow2[j].mult * astate + as.pow2[j].plus;
+            // The lane's state as the previous launch (or act_init_kernel) left it: two loads next to the book-keeping's.  Without it (the first
+            // launch after mi_action_skip or after a seed or a launch inside a stream capture; a launch inside a capture) a skip-ahead by (i + 1)
+            // draws, one affine map per set bit of (i + 1): 17 dependent trips to the pow2 table at 65 536 sub-environments, which the env role
+            // waits for at the first barrier.
+            if (as.lane_valid) {
+                astate = make_u128(as.lane[i], as.lane[N + i]);
+            } else {
+                astate = make_u128(as.state_hi, as.state_lo);
+                uint32_t delta = (uint32_t)i + 1u;
+                for (int j = 0; delta; j++, delta >>= 1)
+                    if (delta & 1u) astate = as.pow2[j].mult * astate + as.pow2[j].plus;
+            }
         }
     }
     const int chunks = T / C;  // (the launcher sends a T that C does not divide to the one-role kernel)
 #ifdef MI_DUO_TIMING
-    unsigned long long t_work = 0, t_wait = 0, t_mark = __builtin_readcyclecounter();
+    unsigned long long t_work = 0, t_wait = 0, t_wait0 = 0, t_mark = __builtin_readcyclecounter();
+    const unsigned long long t_prologue = t_mark - t_begin;
 #endif
     // One phase of one role.  (Round 6, last cut: a loop per ROLE instead of one loop with both roles' code in it.  The values
     // a role keeps in scalar registers across the phases -- the env role's float64 constants, the aux role's pointers and multipliers -- were live through the
@@ -1039,7 +1078,11 @@ __global__ __launch_bounds__(kDuoBlock) void rollout_duo_kernel(DevEnv d, Rollou
                     if (REFILL_PER_CHUNK && ((c * C) & (kRefillPeriod - 1)) == 0 && !q.have) q.refill();
                     // ACT_AHEAD: the action of step k + 1 is requested while step k runs -- the rolled loop otherwise starts every step with an LDS round trip
                     ActLds a_next = sh_act[buf][0][slot];
+#ifdef MI_DUO_ENV_UNROLL  // (A/B builds: scripts/build_variant.py ... -DMI_DUO_ENV_UNROLL=2)
+#pragma unroll MI_DUO_ENV_UNROLL
+#else
 #pragma unroll 1
+#endif
                     for (int k = 0; k < C; k++) {
                         const int t = c * C + k;
                         if (!REFILL_PER_CHUNK && (t & (kRefillPeriod - 1)) == 0 && !q.have) q.refill();
@@ -1211,6 +1254,7 @@ __global__ __launch_bounds__(kDuoBlock) void rollout_duo_kernel(DevEnv d, Rollou
 #ifdef MI_DUO_TIMING
         {
             const unsigned long long now = __builtin_readcyclecounter();
+            if (p == 0) t_wait0 = now - t_mark;  // phase 0: the env role has nothing to step and waits for the policy's first chunk
             t_wait += now - t_mark, t_mark = now;
         }
 #endif
@@ -1224,7 +1268,8 @@ __global__ __launch_bounds__(kDuoBlock) void rollout_duo_kernel(DevEnv d, Rollou
     }
 #ifdef MI_DUO_TIMING  // scripts/r04/duo_timing.py: where each role's time goes
     if (blockIdx.x == 7 && (threadIdx.x & 63) == 0)
-        printf("duo timing: wave %d (role %d) work %llu wait-at-barrier %llu cycles over %d phases\n", (int)(threadIdx.x >> 6), role, t_work, t_wait, chunks + 2);
+        printf("duo timing: wave %d (role %d) prologue %llu work %llu wait-at-barrier %llu (phase 0: %llu) cycles over %d phases\n", (int)(threadIdx.x >> 6), role,
+               t_prologue, t_work, t_wait, t_wait0, chunks + 2);
 #endif
     if (active) {
         if (is_env) {
@@ -1273,6 +1318,11 @@ __global__ __launch_bounds__(kDuoBlock) void rollout_duo_kernel(DevEnv d, Rollou
                 if (chunks == 0) ep_ret = d.ep_ret[i];
             }
             d.ep_ret[i] = ep_ret, d.ep_len[i] = ep_len;
+        }
+        if (is_policy && as.lane) {  // after the last jump: the next launch's start (addresses from an opaque i, as in rollout_kernel)
+            int w = i;
+            hold_opaque(w);
+            as.lane[w] = (uint64_t)(astate >> 64), as.lane[N + w] = (uint64_t)astate;
         }
     }
     // the workgroup's totals (block_accumulate for several roles: only the book-keeping wavefronts carry any)
@@ -3323,15 +3373,18 @@ static int action_sync_host(mi_vecenv *v) {
     v->act_on_device = false;
     return MI_OK;
 }
-// per-lane states for the host copy's position (skip-ahead by i * act_dim + 1 draws per lane); a no-op while they are current
-static int action_prepare_lanes(mi_vecenv *v) {
-    if (v->act_lane_valid) return MI_OK;
+static bool stream_capturing(const mi_vecenv *v) {
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     if (v->stream && hipStreamIsCapturing(v->stream, &cap) != hipSuccess) {
         (void)hipGetLastError();
         cap = hipStreamCaptureStatusNone;
     }
-    if (cap != hipStreamCaptureStatusNone)
+    return cap != hipStreamCaptureStatusNone;
+}
+// per-lane states for the host copy's position (skip-ahead by i * act_dim + 1 draws per lane); a no-op while they are current
+static int action_prepare_lanes(mi_vecenv *v) {
+    if (v->act_lane_valid) return MI_OK;
+    if (stream_capturing(v))
         return fail(MI_ERR_STATE, "the on-device policy's lane states must exist before a stream capture: call mi_action_sample(env, 0, NULL, MI_DEVICE) first");
     hipLaunchKernelGGL(act_init_kernel, dim3(v->grid), dim3(kBlock), 0, v->stream, action_stream(v), v->d_act_lane, v->cfg.num_envs, v->lay.act_dim);
     HIP_TRY(hipGetLastError());
@@ -3589,6 +3642,10 @@ int mi_action_seed(mi_vecenv *v, const uint64_t pcg[4]) {
         v->jump_n = pcg_jump(inc, (u128)v->cfg.num_envs * (u128)v->lay.act_dim - (u128)(v->lay.act_dim - 1));
     }
     v->act_seeded = true;
+    // the per-lane states of the new position right away (one act_init_kernel): the first rollout or step(None) after a seed then starts from them.
+    // Not inside a stream capture -- the lanes stay invalid there, and the next consumer prepares them or skips ahead as before.
+    if (!stream_capturing(v))
+        if (int rc = action_prepare_lanes(v)) return rc;
     return MI_OK;
 }
 
@@ -3601,7 +3658,11 @@ int mi_rollout(mi_vecenv *v, int T, const mi_rollout_io *io) {
     if (sample && !v->act_seeded) return fail(MI_ERR_STATE, "rollout without actions needs mi_action_seed");
     if (T == 0) return MI_OK;
     if (set_device(v)) return MI_ERR_HIP;
-    if (sample)  // (earlier steps / samples may have left the position on the device)
+    // The classic kinds' sampling kernels keep the per-lane states of the action stream (ActionStream::lane): they start from them when they are
+    // current and leave them current for the next launch, so the position stays on the device.  Not inside a stream capture: a captured launch
+    // skips ahead from the host copy baked into the graph and writes no lane states.
+    const bool keep_lanes = sample && !is_tab(v->cfg.kind) && !is_mj(v->cfg.kind) && !v->shared_rng && !stream_capturing(v);
+    if (sample && !(keep_lanes && v->act_on_device))  // (earlier steps / samples may have left the position on the device)
         if (int rc = action_sync_host(v)) return rc;
     RolloutPtrs p = {io->actions_in, io->actions_out, io->obs, io->reward, io->terminated, io->truncated};
     const bool box = v->lay.act_dtype == MI_F32;
@@ -3615,6 +3676,7 @@ int mi_rollout(mi_vecenv *v, int T, const mi_rollout_io *io) {
         as.state_hi = (uint64_t)(v->act_rng.state >> 64), as.state_lo = (uint64_t)v->act_rng.state;
         as.inc_hi = (uint64_t)(v->act_rng.inc >> 64), as.inc_lo = (uint64_t)v->act_rng.inc;
         as.pow2 = v->d_pow2, as.jump_n = v->jump_n;
+        if (keep_lanes) as.lane = v->d_act_lane, as.lane_valid = v->act_lane_valid ? 1 : 0;
     }
     int rc;
     if (is_tab(v->cfg.kind)) {
@@ -3722,10 +3784,10 @@ int mi_rollout(mi_vecenv *v, int T, const mi_rollout_io *io) {
         rc = mi_classic::rollout(v, p, as, T, sample, in_kind);
     }
     if (rc) return rc;
-    if (sample) {  // the host copy of the generator moves past the T*N draws the kernel consumes
+    if (sample) {  // the host copy of the generator moves past the T*N draws the kernel consumes (stale, and harmlessly so, while act_on_device)
         const PcgJump j = pcg_jump(v->act_rng.inc, (u128)T * (u128)v->cfg.num_envs * (u128)v->lay.act_dim);
         v->act_rng.state = j.mult * v->act_rng.state + j.plus;
-        v->act_lane_valid = false;
+        v->act_lane_valid = keep_lanes;  // ... and the lane states with it, where the kernel wrote them
     }
     return MI_OK;
 }

@@ -188,6 +188,19 @@ MI_DEV bool div_by_constant_in_range(double x) {
     return (ax <= 1e300) & (ax >= 1e-300);
 }
 
+// x / y as the compiler's float64 division computes it (SharedDivisor, above: v_rcp_f64, two Newton steps on the reciprocal, q0 = x r and one FMA
+// correction) WITHOUT v_div_scale, v_div_fmas and v_div_fixup -- the same bits wherever those three change nothing: y normal and of ordinary size
+// (v_div_scale scales neither operand and leaves VCC clear, so v_div_fmas is that FMA) and x finite with 2^-969 <= |x| and |x / y| far from the top
+// of the range (v_div_fixup then only gives the quotient the sign of x / y, which a nonzero q0 + e r already has).  NOT for x = 0 (q0 + e r is +0 for
+// x = -0), subnormal or tiny x (v_div_scale would rescale), infinities or NaNs: the caller's range test sends those lanes elsewhere.
+MI_DEV double div_unscaled(double x, double y) {
+    const double r0 = __builtin_amdgcn_rcp(y);
+    const double r1 = __builtin_fma(r0, __builtin_fma(-y, r0, 1.0), r0);
+    const double r = __builtin_fma(r1, __builtin_fma(-y, r1, 1.0), r1);
+    const double q0 = x * r;
+    return __builtin_fma(__builtin_fma(-y, q0, x), r, q0);
+}
+
 struct EnvParams {
     double p[16];
 };
@@ -324,7 +337,14 @@ struct CartPoleT {
         return r;
     }
     // cartpole.py:164-226: explicit Euler with the OLD velocities, all float64.
-    static MI_DEV void step(double s[S], uint32_t &, Act action, const EnvParams &P, double &reward, bool &terminated, Trig &) {
+    static MI_DEV void step(double s[S], uint32_t &f, Act action, const EnvParams &P, double &reward, bool &terminated, Trig &t) {
+        step_hooked(s, f, action, P, reward, terminated, t, false, [] {});
+    }
+    // ... with a caller's own rare work behind the step's one rare branch: `rare()` runs (in the out-of-line block, for the lanes with `extra` among
+    // those that enter it) after the accelerations.  engine.hip duo_env_step: the reset queue's refill, which only feeds the reset select after the step.
+    static constexpr bool RARE_HOOK = true;
+    template <class F>
+    static MI_DEV void step_hooked(double s[S], uint32_t &, Act action, const EnvParams &P, double &reward, bool &terminated, Trig &, bool extra, F &&rare) {
         const double gravity = 9.8, masspole = 0.1, length = 0.5, force_mag = 10.0, tau = 0.02;
         const double polemass_length = masspole * length;
         const double theta_threshold = 12 * 2 * kPi / 360;
@@ -344,15 +364,24 @@ struct CartPoleT {
             M::sincos_main_unchecked(theta, sintheta, costheta);
             const double t1 = force + polemass_length * (theta_dot * theta_dot) * sintheta;
             temp = div_by_constant_unchecked(t1, TotalMass());
-            thetaacc = (gravity * sintheta - costheta * temp) /
-                       (length * (4.0 / 3.0 - div_by_constant_unchecked(masspole * (costheta * costheta), TotalMass())));
+            // (the quotient without the compiler's scaling and fixup steps, div_unscaled: its divisor lies in [0.62, 0.65] inside the main range, where
+            //  cos >= 0.65, and its numerator's range is vouched for by t3's test below)
+            thetaacc = div_unscaled(gravity * sintheta - costheta * temp,
+                                    length * (4.0 / 3.0 - div_by_constant_unchecked(masspole * (costheta * costheta), TotalMass())));
             const double t3 = polemass_length * thetaacc * costheta;
             xacc = temp - div_by_constant_unchecked(t3, TotalMass());
+            // t3 = 0.05 cos thetaacc within [1e-270, 1e220] -- narrower than the constant division needs -- puts the numerator of thetaacc within
+            // [1.2e-269, 2e221]: far above v_div_scale's 2^-969 (~2e-292) and far below overflow.  A zero, tiny, huge, infinite or NaN numerator gives a
+            // thetaacc (its unscaled quotient, off by at most a few ulp) and hence a t3 outside, so that lane redoes the step through general_accel.
+            const double at3 = fabs(t3);
             // (`&`, not `&&`: three flags combined by scalar instructions, no control flow of their own)
-            const bool common = main_range & div_by_constant_in_range(t1) & div_by_constant_in_range(t3);
-            if (__builtin_expect(!common, 0)) {
-                const Accel r = general_accel(theta, theta_dot, force);
-                thetaacc = r.thetaacc, xacc = r.xacc;
+            const bool common = main_range & div_by_constant_in_range(t1) & (at3 <= 1e220) & (at3 >= 1e-270);
+            if (__builtin_expect(!common | extra, 0)) {
+                if (!common) {
+                    const Accel r = general_accel(theta, theta_dot, force);
+                    thetaacc = r.thetaacc, xacc = r.xacc;
+                }
+                rare();
             }
         } else {
             M::sincos(theta, sintheta, costheta);
@@ -360,6 +389,7 @@ struct CartPoleT {
             thetaacc = (gravity * sintheta - costheta * temp) /
                        (length * (4.0 / 3.0 - div_by_constant(masspole * (costheta * costheta), TotalMass())));
             xacc = temp - div_by_constant(polemass_length * thetaacc * costheta, TotalMass());
+            if (__builtin_expect(extra, 0)) rare();
         }
         x = x + tau * x_dot;
         x_dot = x_dot + tau * xacc;
