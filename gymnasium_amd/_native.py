@@ -19,7 +19,7 @@ FLAG_NEEDS_RESET, FLAG_STATE_F32 = 1, 2
 CFG_SOLVER_NEWTON = 1  # MI_CFG_SOLVER_NEWTON
 CFG_FAST_MATH = 2  # MI_CFG_FAST_MATH (classic control: device sin / cos and x * x instead of the libm restatements)
 CFG_SHARED_RNG = 4  # MI_CFG_SHARED_RNG (CartPole: the reference's CartPoleVectorEnv semantics -- one generator for all sub-environments)
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 ENV_KINDS = {"cartpole": 0, "pendulum": 1, "acrobot": 2, "mountain_car": 3, "mountain_car_continuous": 4,
              "half_cheetah": 5, "ant": 6, "humanoid": 7, "tabular": 8,
@@ -39,6 +39,9 @@ SYMBOLS = [
 # (oracle/wrappers.py), so they are not part of the orc_-prefixed checker ABI.
 # Host stepping through the engine's pinned staging block (mi_step_async / mi_step_wait / mi_host_buffers): product library only.
 HOST_SYMBOLS = ["step_async", "step_wait", "host_buffers"]
+# Per-sub-environment attributes (mi_set_env_attr / mi_get_env_attr, ABI 8): product library only -- the checker has no per-lane physics, and
+# HipVectorEnv.set_attr tells the two apart by whether the entry point is bound.
+HOST_SYMBOLS += ["set_env_attr", "get_env_attr"]
 WRAPPER_SYMBOLS = ["rms_create", "rms_destroy", "rms_get", "rms_set", "normalize_observation", "normalize_reward", "clip_reward", "set_step_epilogue"]
 
 
@@ -144,6 +147,8 @@ class NativeLib:
             self.step_async = f("step_async", [vp, C.POINTER(MiStepIO)], i32)
             self.step_wait = f("step_wait", [vp], i32)
             self.host_buffers = f("host_buffers", [vp, C.POINTER(MiStepIO)], i32)
+            self.set_env_attr = f("set_env_attr", [vp, i32, vp, i32], i32)
+            self.get_env_attr = f("get_env_attr", [vp, i32, vp], i32)
 
     def _fn(self, name, argtypes, restype):
         fn = getattr(self.dll, self.prefix + name)
@@ -393,6 +398,19 @@ class Engine:
                 np.ascontiguousarray(isd_csprob, np.float64)]
         t.csprob, t.prob, t.next_state, t.reward, t.terminated, t.count, t.isd_csprob = [a.ctypes.data for a in keep]
         self.lib.check(self.lib.tabular_load(self.handle, C.byref(t)))
+
+    def set_env_attr(self, attr: int, values, on_device: bool = False):
+        """mi_set_env_attr: ``values`` = num_envs float64 values (a host array, or with ``on_device`` a device address), or None for the
+        construction value."""
+        if values is not None and not on_device:
+            values = np.ascontiguousarray(values, dtype=np.float64)
+            assert values.shape == (self.num_envs,)
+        self.lib.check(self.lib.set_env_attr(self.handle, int(attr), _ptr(values), 1 if on_device else 0))
+
+    def get_env_attr(self, attr: int) -> np.ndarray:
+        out = np.empty(self.num_envs, dtype=np.float64)
+        self.lib.check(self.lib.get_env_attr(self.handle, int(attr), _ptr(out)))
+        return out
 
     def get_rng(self) -> np.ndarray:
         words = np.empty((self.num_envs, 4), dtype=np.uint64)

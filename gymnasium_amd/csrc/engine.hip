@@ -83,6 +83,12 @@ struct DevEnv {
     EnvParams P;
     TabTable tab;
 };
+// Per-sub-environment attributes (mi_set_env_attr; the *AttrT types of envs_classic.h): attribute a of sub-environment i is rows[a * N + i] if bit
+// a of `mask` is set, else its construction value.  An extra argument of step_kernel / rollout_kernel, which the other types do not read.
+struct AttrDev {
+    const double *rows;  // [A][N] component-major, like DevEnv::state
+    uint32_t mask;       // wave-uniform
+};
 }  // namespace mi_internal
 using namespace mi_internal;
 namespace {
@@ -119,6 +125,32 @@ MI_DEV void hold_opaque(T &x) {
     static_assert(sizeof(T) == 4 || sizeof(T) == 8, "one or two VGPRs");
     asm volatile("" : "+v"(x));
 }
+// E has per-lane attributes (envs_classic.h *AttrT: N_ATTR, attr_default, attrs_arrive)
+template <class E, class = void>
+struct HasAttrs : std::false_type {};
+template <class E>
+struct HasAttrs<E, std::void_t<decltype(E::N_ATTR)>> : std::true_type {};
+// The lane's attributes, requested with the rest of its loads and handed to its register struct (Lane::trig) on arrival; empty for the other types.
+template <class E, bool = HasAttrs<E>::value>
+struct AttrRequest {
+    MI_DEV void request(const AttrDev &, const DevEnv &, int) {}
+    template <class T>
+    MI_DEV void arrive(T &) {}
+};
+template <class E>
+struct AttrRequest<E, true> {
+    double v[E::N_ATTR];
+    MI_DEV void request(const AttrDev &at, const DevEnv &d, int i) {
+#pragma unroll
+        for (int a = 0; a < E::N_ATTR; a++) v[a] = (at.mask >> a) & 1u ? at.rows[(size_t)a * d.N + i] : E::attr_default(a, d.P);
+    }
+    MI_DEV void arrive(typename E::Trig &t) {
+#pragma unroll
+        for (int a = 0; a < E::N_ATTR; a++) hold_opaque(v[a]);
+        E::attrs_arrive(v, t);
+    }
+};
+
 template <class E>
 struct LaneRequest {
     double s[E::S], ep_ret;
@@ -695,7 +727,7 @@ MI_DEV typename E::Act action_of_state(u128 astate) {
 // stream (spaces/multi_discrete.py:176-178, spaces/box.py:463-465: draw number pos + i of the batched space's generator), which rides along with the
 // lane's other loads, and leaves the state of its draw in the NEXT batch behind.  Nothing on the host changes from step to step: capturable.
 template <class E, int MODE, bool EPI = false, bool SAMPLE = false>
-__global__ __launch_bounds__(kBlock) void step_kernel(DevEnv d, StepPtrs io, EpiDev epi) {
+__global__ __launch_bounds__(kBlock) void step_kernel(DevEnv d, StepPtrs io, EpiDev epi, AttrDev at) {
     // One step is ~200 instructions per lane between trips to memory that take a microsecond each: everything the step may read -- the lane's
     // state and action, its generator (consumed only by a reset, which some lane of a 64-CartPole wavefront needs on ~95 % of the steps) and the
     // workgroup's running totals -- is requested BEFORE the math tables are staged into LDS, so that all of it is ONE trip, not four in a row.
@@ -703,7 +735,8 @@ __global__ __launch_bounds__(kBlock) void step_kernel(DevEnv d, StepPtrs io, Epi
     LaneStats st = {0u, 0u, 0u, 0ull, 0.0};
     StepOut<E> o;
     LaneRequest<E> rq;
-    if (i < d.N) rq.template request<SAMPLE>(d, io.actions, io.act_lane, i, MODE != MI_AUTORESET_DISABLED);
+    AttrRequest<E> ar;
+    if (i < d.N) rq.template request<SAMPLE>(d, io.actions, io.act_lane, i, MODE != MI_AUTORESET_DISABLED), ar.request(at, d, i);
     BlockTotals before = block_totals_load(d);
     tables_init<E>();
     hold_opaque(before.count), hold_opaque(before.ret);
@@ -711,6 +744,7 @@ __global__ __launch_bounds__(kBlock) void step_kernel(DevEnv d, StepPtrs io, Epi
         Lane<E> L;
         Pcg64 gen;
         rq.arrive(L, gen);
+        ar.arrive(L.trig);
         typename E::Act a = rq.a;
         if constexpr (SAMPLE) {
             const u128 astate = make_u128(rq.ag[0], rq.ag[1]);
@@ -813,13 +847,18 @@ namespace {
 // FULL: every trajectory output is materialised -- the per-store null checks (five taken branches per step for a
 // wavefront that runs alone on its SIMD) disappear from the loop.
 template <class E, int MODE, bool SAMPLE, bool FULL>
-__global__ __launch_bounds__(kBlock) void rollout_kernel(DevEnv d, RolloutPtrs io, ActionStream as, int T) {
+__global__ __launch_bounds__(kBlock) void rollout_kernel(DevEnv d, RolloutPtrs io, ActionStream as, int T, AttrDev at) {
     tables_init<E>();
     const int i = blockIdx.x * kBlock + threadIdx.x;
     LaneStats st = {0u, 0u, 0u, 0ull, 0.0};
     if (i < d.N) {
         Lane<E> L;
         load_lane<E>(d, i, L);
+        {  // the lane's attributes and what they make invariant, once per launch (no-op for the types without attributes)
+            AttrRequest<E> ar;
+            ar.request(at, d, i);
+            ar.arrive(L.trig);
+        }
         u128 astate = 0;
         const u128 ainc = make_u128(as.inc_hi, as.inc_lo);
         if (SAMPLE) {
@@ -2615,6 +2654,10 @@ struct mi_vecenv {
     SharedRng shared;
     PcgJump *d_shared_pow2;
     Pcg64 shared_base;      // host copy of the base generator (mi_get_rng: base advanced by the device's `consumed` counter)
+    // mi_set_env_attr: [A][N] float64 rows of the per-sub-environment attributes (allocated by the first call) and the set of attributes that
+    // come from them.  attr_mask != 0 ("per-lane mode"): step and rollout run the *AttrT kernels (envs_classic.h); a bit, once set, stays set
+    double *d_attr;
+    uint32_t attr_mask;
 };
 
 namespace {
@@ -2655,6 +2698,20 @@ int dispatch_kind_act_math(int kind, int act_kind, F &&f) {
 template <class F>
 int dispatch_kind_act(int kind, bool fast_math, int act_kind, F &&f) {
     return fast_math ? dispatch_kind_act_math<FastMath>(kind, act_kind, f) : dispatch_kind_act_math<ExactMath>(kind, act_kind, f);
+}
+// per-lane attributes (mi_set_env_attr has refused Acrobot, fast math and the shared generator)
+template <class F>
+int dispatch_kind_attr(int kind, int act_kind, F &&f) {
+    switch (kind) {
+    case MI_ENV_CARTPOLE: return f(CartPoleAttrT<ExactMath>());
+    case MI_ENV_PENDULUM: return act_kind != MI_F32 ? f(PendulumAttrT<ExactMath, ActF64>()) : f(PendulumAttrT<ExactMath>());
+    case MI_ENV_MOUNTAIN_CAR: return f(MountainCarAttrT<ExactMath>());
+    case MI_ENV_MOUNTAIN_CAR_CONTINUOUS:
+        if (act_kind == MI_F64) return f(MountainCarContinuousAttrT<ExactMath, ActF64>());
+        if (act_kind == MI_F64_WEAK) return f(MountainCarContinuousAttrT<ExactMath, ActF64Weak>());
+        return f(MountainCarContinuousAttrT<ExactMath>());
+    }
+    return fail(MI_ERR_UNSUPPORTED, "per-sub-environment attributes: not for this kind");
 }
 
 #ifndef MI_CLASSIC_TU
@@ -2733,10 +2790,11 @@ void epilogue_swap(mi_vecenv *v) {
 template <class E, bool EPI, bool SAMPLE = false>
 void launch_step_mode(mi_vecenv *v, const StepPtrs &p) {
     const dim3 g(v->grid), b(kBlock);
+    const AttrDev at = {v->d_attr, v->attr_mask};
     switch (v->cfg.autoreset_mode) {
-    case MI_AUTORESET_NEXT_STEP: hipLaunchKernelGGL((step_kernel<E, MI_AUTORESET_NEXT_STEP, EPI, SAMPLE>), g, b, 0, v->stream, v->d, p, v->epi); break;
-    case MI_AUTORESET_SAME_STEP: hipLaunchKernelGGL((step_kernel<E, MI_AUTORESET_SAME_STEP, EPI, SAMPLE>), g, b, 0, v->stream, v->d, p, v->epi); break;
-    default: hipLaunchKernelGGL((step_kernel<E, MI_AUTORESET_DISABLED, EPI, SAMPLE>), g, b, 0, v->stream, v->d, p, v->epi); break;
+    case MI_AUTORESET_NEXT_STEP: hipLaunchKernelGGL((step_kernel<E, MI_AUTORESET_NEXT_STEP, EPI, SAMPLE>), g, b, 0, v->stream, v->d, p, v->epi, at); break;
+    case MI_AUTORESET_SAME_STEP: hipLaunchKernelGGL((step_kernel<E, MI_AUTORESET_SAME_STEP, EPI, SAMPLE>), g, b, 0, v->stream, v->d, p, v->epi, at); break;
+    default: hipLaunchKernelGGL((step_kernel<E, MI_AUTORESET_DISABLED, EPI, SAMPLE>), g, b, 0, v->stream, v->d, p, v->epi, at); break;
     }
 }
 template <class E>
@@ -2769,7 +2827,8 @@ int launch_step(mi_vecenv *v, const StepPtrs &p) {
 
 template <class E, int MODE, bool SAMPLE, bool FULL>
 void launch_rollout_variant(mi_vecenv *v, const RolloutPtrs &p, const ActionStream &as, int T) {
-    hipLaunchKernelGGL((rollout_kernel<E, MODE, SAMPLE, FULL>), dim3(v->grid), dim3(kBlock), 0, v->stream, v->d, p, as, T);
+    const AttrDev at = {v->d_attr, v->attr_mask};
+    hipLaunchKernelGGL((rollout_kernel<E, MODE, SAMPLE, FULL>), dim3(v->grid), dim3(kBlock), 0, v->stream, v->d, p, as, T, at);
 }
 
 template <class E>
@@ -2809,6 +2868,7 @@ int launch_rollout(mi_vecenv *v, const RolloutPtrs &p, const ActionStream &as, i
 // ---- the launchers the other translation unit calls (this unit is compiled with the max-ILP scheduler, see the head of the file) ----------------
 namespace mi_classic {
 int step(mi_vecenv *v, const StepPtrs &p, int act_kind) {
+    if (v->attr_mask) return dispatch_kind_attr(v->cfg.kind, act_kind, [&](auto env) -> int { return launch_step<decltype(env)>(v, p); });
     return dispatch_kind_act(v->cfg.kind, (v->cfg.reserved[0] & MI_CFG_FAST_MATH) != 0, act_kind, [&](auto env) -> int { return launch_step<decltype(env)>(v, p); });
 }
 int reset(mi_vecenv *v, const uint8_t *dm, int has_bounds, double b0, double b1, float *dobs) {
@@ -2820,6 +2880,7 @@ int reset(mi_vecenv *v, const uint8_t *dm, int has_bounds, double b0, double b1,
     });
 }
 int rollout(mi_vecenv *v, const RolloutPtrs &p, const ActionStream &as, int T, bool sample, int in_kind) {
+    if (v->attr_mask) return dispatch_kind_attr(v->cfg.kind, in_kind, [&](auto env) -> int { return launch_rollout<decltype(env)>(v, p, as, T, sample); });
     return dispatch_kind_act(v->cfg.kind, (v->cfg.reserved[0] & MI_CFG_FAST_MATH) != 0, in_kind, [&](auto env) -> int { return launch_rollout<decltype(env)>(v, p, as, T, sample); });
 }
 // ---- MI_CFG_SHARED_RNG: MI_ENV_CARTPOLE only (mi_create refuses the bit for every other kind) ---------------------------------------------
@@ -3139,7 +3200,7 @@ void mi_destroy(mi_vecenv *v) {
     (void)hipStreamSynchronize(v->stream);
     void *ptrs[] = {v->d.state, v->d.meta, v->d.rng, v->d.ep_ret, v->d.ep_len, v->d.blk_count, v->d.blk_ret, v->d_out,
                     v->d_pow2, v->d_act_lane, v->d_act_stage, v->d_actions, v->d_mask, v->d_words, v->d_extras, v->d_act_scratch, v->d_obs_scratch,
-                    v->shared.words, v->d_shared_pow2, v->shared.blk_done, v->shared.blk_prefix};
+                    v->shared.words, v->d_shared_pow2, v->shared.blk_done, v->shared.blk_prefix, v->d_attr};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     if (v->h_out) (void)hipHostFree(v->h_out);
@@ -3150,6 +3211,79 @@ void mi_destroy(mi_vecenv *v) {
     if (v->d_epi_partial) (void)hipFree(v->d_epi_partial);
     if (v->own_stream) (void)hipStreamDestroy(v->own_stream);
     delete v;
+}
+
+// Per-sub-environment attributes (include/mi355env.h MI_ATTR_*): the construction values of a kind's attributes and their number, 0 for a kind
+// without.  The order is the one of envs_classic.h *AttrT::attr_default; the constructor's values (mi_config.params) replace the defaults.
+static int attr_defaults(const mi_vecenv *v, double *out) {
+    switch (v->cfg.kind) {
+    case MI_ENV_CARTPOLE: {
+        const double d[] = {9.8, 1.0, 0.1, 0.1 + 1.0, 0.5, 0.1 * 0.5, 10.0, 0.02, 0.0, 12 * 2 * kPi / 360, 2.4};
+        memcpy(out, d, sizeof d);
+        return MI_ATTR_CARTPOLE_COUNT;
+    }
+    case MI_ENV_PENDULUM: {
+        const double d[] = {v->cfg.params[0], 1.0, 1.0, 0.05, 8.0, 2.0};
+        memcpy(out, d, sizeof d);
+        return MI_ATTR_PENDULUM_COUNT;
+    }
+    case MI_ENV_MOUNTAIN_CAR: {
+        const double d[] = {0.001, 0.0025, 0.07, -1.2, 0.6, 0.5, v->cfg.params[0]};
+        memcpy(out, d, sizeof d);
+        return MI_ATTR_MOUNTAIN_CAR_COUNT;
+    }
+    case MI_ENV_MOUNTAIN_CAR_CONTINUOUS: {
+        const double d[] = {-1.0, 1.0, 0.0015, 0.07, -1.2, 0.6, 0.45, v->cfg.params[0]};
+        memcpy(out, d, sizeof d);
+        return MI_ATTR_MOUNTAIN_CAR_CONTINUOUS_COUNT;
+    }
+    }
+    return 0;
+}
+static int attr_check(mi_vecenv *v, int attr, double *defaults) {
+    if (!v) return fail(MI_ERR_INVALID_ARGUMENT, "null env");
+    const int n = attr_defaults(v, defaults);
+    if (!n) return fail(MI_ERR_UNSUPPORTED, "per-sub-environment attributes: CartPole, Pendulum, MountainCar and MountainCarContinuous only");
+    if (v->shared_rng) return fail(MI_ERR_UNSUPPORTED, "per-sub-environment attributes: not with MI_CFG_SHARED_RNG (CartPoleVectorEnv has no set_attr)");
+    if (v->cfg.reserved[0] & MI_CFG_FAST_MATH) return fail(MI_ERR_UNSUPPORTED, "per-sub-environment attributes: not with MI_CFG_FAST_MATH");
+    if (attr < 0 || attr >= n) return fail(MI_ERR_INVALID_ARGUMENT, "attribute id out of range for this kind");
+    if (v->has_pending) return fail(MI_ERR_STATE, "an asynchronous step is pending (mi_step_wait)");
+    return MI_OK;
+}
+
+int mi_set_env_attr(mi_vecenv *v, int attr, const double *values, int on_device) {
+    double defaults[16];
+    if (const int rc = attr_check(v, attr, defaults)) return rc;
+    if (set_device(v)) return MI_ERR_HIP;
+    const size_t N = (size_t)v->cfg.num_envs;
+    if (!v->d_attr)  // every row at once: a later attribute needs no allocation
+        HIP_TRY(hipMalloc(&v->d_attr, sizeof(double) * (size_t)attr_defaults(v, defaults) * N));
+    double *row = v->d_attr + (size_t)attr * N;
+    if (values && on_device) {
+        HIP_TRY(hipMemcpyAsync(row, values, sizeof(double) * N, hipMemcpyDeviceToDevice, v->stream));
+    } else {  // staged: the caller may reuse its array as soon as this returns
+        std::vector<double> host(N, defaults[attr]);
+        if (values) memcpy(host.data(), values, sizeof(double) * N);
+        HIP_TRY(hipMemcpyAsync(row, host.data(), sizeof(double) * N, hipMemcpyHostToDevice, v->stream));
+        HIP_TRY(hipStreamSynchronize(v->stream));
+    }
+    v->attr_mask |= 1u << attr;
+    return MI_OK;
+}
+
+int mi_get_env_attr(mi_vecenv *v, int attr, double *host_out) {
+    double defaults[16];
+    if (const int rc = attr_check(v, attr, defaults)) return rc;
+    if (!host_out) return fail(MI_ERR_INVALID_ARGUMENT, "null argument");
+    if (set_device(v)) return MI_ERR_HIP;
+    const size_t N = (size_t)v->cfg.num_envs;
+    if (!(v->attr_mask & (1u << attr))) {
+        for (size_t i = 0; i < N; i++) host_out[i] = defaults[attr];
+        return MI_OK;
+    }
+    HIP_TRY(hipMemcpyAsync(host_out, v->d_attr + (size_t)attr * N, sizeof(double) * N, hipMemcpyDeviceToHost, v->stream));
+    HIP_TRY(hipStreamSynchronize(v->stream));
+    return MI_OK;
 }
 
 // The reference's stateful vector wrappers as the output stage of the classic-control step kernel (include/mi355env.h mi_step_epilogue).

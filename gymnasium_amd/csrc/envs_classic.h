@@ -53,6 +53,7 @@ struct TwoPi {
 // operations on the same values, hence the same quotient bit for bit, in 5 + 4 per quotient.  The caller guarantees the ranges (ordinary()).
 struct SharedDivisor {
     double b, r;
+    SharedDivisor() = default;  // (a member of a lane's register struct: CartPoleAttrs)
     MI_DEV explicit SharedDivisor(double divisor) : b(divisor) {
         const double r0 = __builtin_amdgcn_rcp(divisor);
         const double e0 = __builtin_fma(-divisor, r0, 1.0);
@@ -894,6 +895,237 @@ struct MountainCarContinuousT {
         terminated = p_ge && v_ge;
         reward = (terminated ? 100.0 : 0.0) - M::sq(a0) * 0.1;  // math.pow(action[0], 2) * 0.1: libm pow, not the correctly rounded a0 * a0
         s[0] = (double)(float)p, s[1] = (double)(float)v;       // np.array([position, velocity], dtype=np.float32)
+        flags |= kStateF32;
+    }
+};
+
+// ---------------------------------------------------------------------------------------------------------
+// Per-sub-environment physics: SyncVectorEnv.set_attr (vector/sync_vector_env.py:343-398) on the attributes the reference's step() reads.
+//
+// The *AttrT types are the environments above with every such attribute a per-lane value instead of a literal; everything else (reset, obs,
+// sampling) is inherited.  engine.hip loads the values once per launch (step_kernel: with the state, in the same trip to memory; rollout_kernel:
+// before the step loop) from AttrDev -- an attribute whose bit is set in the wave-uniform mask comes from its row of [A][N] float64, the others
+// are the construction values (attr_default) -- and hands them to attrs_arrive(), which keeps them, plus what is invariant per lane, in the
+// lane's register struct Trig (derived from the base type's, so obs() and trig_invalidate() see what they always saw).  Reset reads no attribute.
+// The arithmetic is the reference's on the per-lane operands: the short cuts of the base types that rely on the default constants (CartPole's
+// constant divisions, its unscaled division and the short sin / cos routine guaranteed by the 12-degree threshold) are replaced by routines
+// valid for any value, or guarded per lane with the IEEE operation as the fallback.  No two-role rollout (DUO_ROLLOUT = false).
+// ---------------------------------------------------------------------------------------------------------
+struct CartPoleAttrs : NoTrig {
+    double gravity, masspole, total_mass, length, polemass_length, force_mag, tau, theta_threshold, x_threshold;
+    bool semi_implicit;     // kinematics_integrator != "euler" (cartpole.py:185)
+    bool tm_shared;         // total_mass of ordinary size: its quotients may share the refined reciprocal
+    SharedDivisor by_tm;
+};
+template <class M>
+struct CartPoleAttrT : CartPoleT<M> {
+    typedef CartPoleT<M> Base;
+    static constexpr bool DUO_ROLLOUT = false;
+    // cartpole.py:119-136 (ids: include/mi355env.h MI_ATTR_CARTPOLE_*); masscart (1) is stored but read by no step
+    static constexpr int N_ATTR = 11;
+    static MI_DEV double attr_default(int a, const EnvParams &) {
+        constexpr double d[N_ATTR] = {9.8, 1.0, 0.1, 0.1 + 1.0, 0.5, 0.1 * 0.5, 10.0, 0.02, 0.0, 12 * 2 * kPi / 360, 2.4};
+        return d[a];
+    }
+    typedef CartPoleAttrs Trig;
+    static MI_DEV void attrs_arrive(const double v[N_ATTR], Trig &t) {
+        t.gravity = v[0], t.masspole = v[2], t.total_mass = v[3], t.length = v[4], t.polemass_length = v[5];
+        t.force_mag = v[6], t.tau = v[7], t.semi_implicit = v[8] != 0.0, t.theta_threshold = v[9], t.x_threshold = v[10];
+        // 2^-20 <= |total_mass| <= 2^20 and a numerator of ordinary size (SharedDivisor::ordinary) keep v_div_scale a no-op: the shared reciprocal
+        // gives the IEEE quotient bit for bit; any other lane divides the long way
+        const uint32_t e = (uint32_t)(mi_sincos::bits(v[3]) >> 52) & 0x7ffu;
+        t.tm_shared = e >= 1023u - 20u && e <= 1023u + 19u;
+        t.by_tm = SharedDivisor(t.tm_shared ? v[3] : 1.0);
+    }
+    static MI_DEV double by_total_mass(double a, const Trig &t) {
+        double q = t.by_tm.under(a);
+        if (__builtin_expect(!(t.tm_shared & SharedDivisor::ordinary(a)), 0)) q = a / t.total_mass;
+        return q;
+    }
+    // cartpole.py:164-213 with the lane's attributes; all float64
+    static MI_DEV void step(double s[4], uint32_t &, int64_t action, const EnvParams &P, double &reward, bool &terminated, Trig &t) {
+        double x = s[0], x_dot = s[1], theta = s[2], theta_dot = s[3];
+        const double force = action == 1 ? t.force_mag : -t.force_mag;
+        double sintheta, costheta;
+        M::sincos(theta, sintheta, costheta);  // any angle: a threshold beyond 12 degrees leaves the short routine's range
+        const double temp = by_total_mass(force + t.polemass_length * (theta_dot * theta_dot) * sintheta, t);
+        const double thetaacc = (t.gravity * sintheta - costheta * temp) /
+                                (t.length * (4.0 / 3.0 - by_total_mass(t.masspole * (costheta * costheta), t)));
+        const double xacc = temp - by_total_mass(t.polemass_length * thetaacc * costheta, t);
+        if (!t.semi_implicit) {
+            x = x + t.tau * x_dot;
+            x_dot = x_dot + t.tau * xacc;
+            theta = theta + t.tau * theta_dot;
+            theta_dot = theta_dot + t.tau * thetaacc;
+        } else {
+            x_dot = x_dot + t.tau * xacc;
+            x = x + t.tau * x_dot;
+            theta_dot = theta_dot + t.tau * thetaacc;
+            theta = theta + t.tau * theta_dot;
+        }
+        s[0] = x, s[1] = x_dot, s[2] = theta, s[3] = theta_dot;
+        terminated = x < -t.x_threshold || x > t.x_threshold || theta < -t.theta_threshold || theta > t.theta_threshold;
+        const bool sutton_barto = P.p[0] != 0.0;
+        reward = terminated ? (sutton_barto ? -1.0 : 1.0) : (sutton_barto ? 0.0 : 1.0);
+    }
+};
+
+template <class Act>
+struct PendulumAttrs : PendulumTrig {
+    double g3_2l;        // 3 * g / (2 * l)
+    double coef;         // 3.0 / (m * l ** 2), l ** 2 the libm pow of a Python float
+    float coef32;        // ... rounded to float32 where it meets a float32 u (NEP 50)
+    double dt, max_speed;
+    Act lo, hi;          // the torque clip's bounds in the action's type: np.clip(u, -max_torque, max_torque) of a float32 row clips in float32
+};
+template <class M, class AK = ActF32>
+struct PendulumAttrT : PendulumT<M, AK> {
+    typedef PendulumT<M, AK> Base;
+    typedef typename AK::T Act;
+    static constexpr bool DUO_ROLLOUT = false;
+    static constexpr bool USES_POW = true, USES_POWF = AK::KIND == MI_F32;
+    // pendulum.py:102-108: g (the constructor's, EnvParams p[0]), m, l, dt, max_speed, max_torque
+    static constexpr int N_ATTR = 6;
+    static MI_DEV double attr_default(int a, const EnvParams &P) {
+        constexpr double d[N_ATTR] = {10.0, 1.0, 1.0, 0.05, 8.0, 2.0};
+        return a == 0 ? P.p[0] : d[a];
+    }
+    typedef PendulumAttrs<Act> Trig;
+    static MI_DEV void attrs_arrive(const double v[N_ATTR], Trig &t) {
+        const double g = v[0], m = v[1], l = v[2];
+        t.g3_2l = 3 * g / (2 * l);
+        t.coef = 3.0 / (m * M::sq(l));
+        t.coef32 = (float)t.coef;
+        t.dt = v[3], t.max_speed = v[4];
+        t.lo = (Act)-v[5], t.hi = (Act)v[5];
+    }
+    static MI_DEV void step(double s[2], uint32_t &, Act action, const EnvParams &, double &reward, bool &terminated, Trig &t) {
+        Act u = action;
+        u = u < t.lo ? t.lo : u;
+        u = u > t.hi ? t.hi : u;
+        const double th = s[0], thdot = s[1];
+        // pendulum.py:131 on the clipped u (Base::reward_of without its clip)
+        const double an = Base::angle_normalize(th);
+        double cu;
+        if constexpr (AK::KIND == MI_F32)
+            cu = (double)(0.001f * M::sqf(u));
+        else
+            cu = 0.001 * M::sq(u);
+        double sq_an, sq_thdot;
+        M::sq2(an, thdot, sq_an, sq_thdot);
+        reward = -(sq_an + 0.1 * sq_thdot + cu);
+        // pendulum.py:133-137
+        double tu;
+        if constexpr (AK::KIND == MI_F32)
+            tu = (double)(t.coef32 * u);
+        else
+            tu = t.coef * u;
+        if (!t.ok) t.sn = M::sin(th);
+        const double sn = t.sn;
+        t.ok = false;
+        double newthdot = thdot + (t.g3_2l * sn + tu) * t.dt;
+        newthdot = newthdot < -t.max_speed ? -t.max_speed : newthdot;
+        newthdot = newthdot > t.max_speed ? t.max_speed : newthdot;
+        s[0] = th + newthdot * t.dt, s[1] = newthdot;
+        terminated = false;
+    }
+};
+
+struct MountainCarAttrs : NoTrig {
+    double force, gravity, max_speed, min_position, max_position, goal_position, goal_velocity;
+};
+template <class M>
+struct MountainCarAttrT : MountainCarT<M> {
+    static constexpr bool DUO_ROLLOUT = false;
+    // mountain_car.py:108-116: force, gravity, max_speed, min_position, max_position, goal_position, goal_velocity (the constructor's, p[0])
+    static constexpr int N_ATTR = 7;
+    static MI_DEV double attr_default(int a, const EnvParams &P) {
+        constexpr double d[N_ATTR] = {0.001, 0.0025, 0.07, -1.2, 0.6, 0.5, 0.0};
+        return a == 6 ? P.p[0] : d[a];
+    }
+    typedef MountainCarAttrs Trig;
+    static MI_DEV void attrs_arrive(const double v[N_ATTR], Trig &t) {
+        t.force = v[0], t.gravity = v[1], t.max_speed = v[2], t.min_position = v[3], t.max_position = v[4], t.goal_position = v[5], t.goal_velocity = v[6];
+    }
+    // mountain_car.py:132-150, all float64 (np.clip with Python-float bounds of an np.float64: minimum(maximum(x, lo), hi))
+    static MI_DEV void step(double s[2], uint32_t &, int64_t action, const EnvParams &, double &reward, bool &terminated, Trig &t) {
+        double position = s[0], velocity = s[1];
+        velocity += (double)(action - 1) * t.force + M::cos(3 * position) * (-t.gravity);
+        velocity = velocity < -t.max_speed ? -t.max_speed : velocity;
+        velocity = velocity > t.max_speed ? t.max_speed : velocity;
+        position += velocity;
+        position = position < t.min_position ? t.min_position : position;
+        position = position > t.max_position ? t.max_position : position;
+        if (position == t.min_position && velocity < 0) velocity = 0;
+        s[0] = position, s[1] = velocity;
+        terminated = position >= t.goal_position && velocity >= t.goal_velocity;
+        reward = -1.0;
+    }
+};
+
+struct MountainCarContinuousAttrs : NoTrig {
+    double min_action, max_action, power, max_speed, min_position, max_position, goal_position, goal_velocity;
+};
+template <class M, class AK = ActF32>
+struct MountainCarContinuousAttrT : MountainCarContinuousT<M, AK> {
+    typedef typename AK::T Act;
+    static constexpr bool DUO_ROLLOUT = false;
+    // continuous_mountain_car.py:116-126: min_action, max_action, power, max_speed, min_position, max_position, goal_position, goal_velocity (p[0])
+    static constexpr int N_ATTR = 8;
+    static MI_DEV double attr_default(int a, const EnvParams &P) {
+        constexpr double d[N_ATTR] = {-1.0, 1.0, 0.0015, 0.07, -1.2, 0.6, 0.45, 0.0};
+        return a == 7 ? P.p[0] : d[a];
+    }
+    typedef MountainCarContinuousAttrs Trig;
+    static MI_DEV void attrs_arrive(const double v[N_ATTR], Trig &t) {
+        t.min_action = v[0], t.max_action = v[1], t.power = v[2], t.max_speed = v[3];
+        t.min_position = v[4], t.max_position = v[5], t.goal_position = v[6], t.goal_velocity = v[7];
+    }
+    // The scalars of continuous_mountain_car.py:150-178 and what NumPy 2 makes of them, tracked per lane: kind 0 = np.float32, 1 = np.float64,
+    // 2 = Python float (weak: it takes the other operand's type; an np.float32 compared with it compares in float32).  The attributes are
+    // Python floats; action[0] is an np.float32 (float32 rows), an np.float64 (float64 rows) or a Python float (rows of a list, ActF64Weak);
+    // position / velocity are np.float64 right after a reset and np.float32 from the first step on.  `min(max(action[0], min_action),
+    // max_action)` keeps whichever OBJECT wins, so the kind of `force` -- and with it the precision of the velocity update -- varies per lane
+    // and per step once the bounds do.
+    static MI_DEV int promote(int a, int b) { return (a == 1 || b == 1) ? 1 : ((a == 0 || b == 0) ? 0 : 2); }
+    static MI_DEV bool gt(double a, int ka, double b, int kb) {  // a > b in the type NumPy compares them in
+        return promote(ka, kb) == 0 ? ((float)a > (float)b) : (a > b);
+    }
+    static MI_DEV bool ge(double a, int ka, double b, int kb) { return promote(ka, kb) == 0 ? ((float)a >= (float)b) : (a >= b); }
+    static MI_DEV bool eq(double a, int ka, double b, int kb) { return promote(ka, kb) == 0 ? ((float)a == (float)b) : (a == b); }
+    static MI_DEV void step(double s[2], uint32_t &flags, Act a0, const EnvParams &, double &reward, bool &terminated, Trig &t) {
+        constexpr int ka = AK::KIND == MI_F32 ? 0 : (AK::KIND == MI_F64 ? 1 : 2);
+        // force = min(max(action[0], min_action), max_action): max() replaces its first argument when the second compares greater, min() when less
+        double force = (double)a0;
+        int kf = ka;
+        if (gt(t.min_action, 2, force, kf)) force = t.min_action, kf = 2;
+        if (gt(force, kf, t.max_action, 2)) force = t.max_action, kf = 2;
+        const bool state_f32 = (flags & kStateF32) != 0;
+        double p = s[0], v = s[1];
+        int kp = state_f32 ? 0 : 1, kv = kp;
+        // math.cos(3 * position): 3 * np.float32 is a float32 product
+        const double g = 0.0025 * M::cos(state_f32 ? (double)(3.0f * (float)p) : 3 * p);
+        // force * power - g: in force's type (power and g are Python floats)
+        const double dv = kf == 0 ? (double)((float)force * (float)t.power - (float)g) : force * t.power - g;
+        kv = promote(kv, kf);
+        v = kv == 0 ? (double)((float)v + (float)dv) : v + dv;
+        if (gt(v, kv, t.max_speed, 2)) v = t.max_speed, kv = 2;
+        if (gt(-t.max_speed, 2, v, kv)) v = -t.max_speed, kv = 2;
+        kp = promote(kp, kv);
+        p = kp == 0 ? (double)((float)p + (float)v) : p + v;
+        if (gt(p, kp, t.max_position, 2)) p = t.max_position, kp = 2;
+        if (gt(t.min_position, 2, p, kp)) p = t.min_position, kp = 2;
+        if (eq(p, kp, t.min_position, 2) && v < 0) v = 0, kv = 2;
+        terminated = ge(p, kp, t.goal_position, 2) && ge(v, kv, t.goal_velocity, 2);
+        double cost;
+        if constexpr (AK::KIND == MI_F32) {
+            const double a_d = (double)a0;
+            cost = (a_d * a_d) * 0.1;  // math.pow of a float32 value: exact in double
+        } else {
+            cost = M::sq((double)a0) * 0.1;
+        }
+        reward = (terminated ? 100.0 : 0.0) - cost;
+        s[0] = (double)(float)p, s[1] = (double)(float)v;  // np.array([position, velocity], dtype=np.float32)
         flags |= kStateF32;
     }
 };

@@ -42,6 +42,13 @@ class _ClassicControlVectorEnv(HipVectorEnv):
 
         return _native.CFG_FAST_MATH if self.fast_math else 0
 
+    _env_attr_ctor: dict = {}  # set_attr: the constructor's values of the attributes whose ENV_ATTRS default is None
+
+    def _env_attr_refusal(self):
+        if self.ENV_ATTRS is not None and self.fast_math:
+            return "per-sub-environment attributes (set_attr / get_attr) run the exact kernels only: not with fast_math=True"
+        return super()._env_attr_refusal()
+
     # set_state() is this package's own entry (checkpoint / resume; the reference has none), so its domain is stated here: the restated libm
     # sin / cos are glibc's below EXACT_TRIG_RANGE (beyond it glibc switches to Payne-Hanek, docs/classic_kernels.md), and the routines of the
     # environments that wrap or clip their angle leave the test for it out.  _STATE_LIMITS: (columns, largest magnitude accepted).  The limits are
@@ -76,6 +83,9 @@ class CartPoleVectorEnv(_ClassicControlVectorEnv):
     _STATE_LIMITS = (((2,), 1e8),)  # theta
     DEFAULT_MAX_EPISODE_STEPS = 500
     DEFAULT_RNG = "per_env"
+    ENV_ATTRS = (("gravity", 9.8, True), ("masscart", 1.0, True), ("masspole", 0.1, True), ("total_mass", 0.1 + 1.0, True), ("length", 0.5, True),
+                 ("polemass_length", 0.1 * 0.5, True), ("force_mag", 10.0, True), ("tau", 0.02, True), ("kinematics_integrator", "euler", True),
+                 ("theta_threshold_radians", 12 * 2 * math.pi / 360, True), ("x_threshold", 2.4, True))  # cartpole.py:124-136
 
     def __init__(self, num_envs: int = 1, max_episode_steps: int | None = None, sutton_barto_reward: bool = False, rng: str | None = None, **kwargs):
         self._sutton_barto_reward = bool(sutton_barto_reward)
@@ -94,6 +104,11 @@ class CartPoleVectorEnv(_ClassicControlVectorEnv):
 
     def _engine_options(self) -> int:
         return super()._engine_options() | (_native.CFG_SHARED_RNG if self._shared_rng else 0)
+
+    def _env_attr_refusal(self):
+        if self._shared_rng:
+            return "rng='shared' is the reference's NumPy CartPoleVectorEnv, which has no set_attr / get_attr"
+        return super()._env_attr_refusal()
 
     def _short_step_allowed(self) -> bool:
         return not self._shared_rng  # (the shared-generator mode returns float32 rewards: step() below converts)
@@ -204,9 +219,12 @@ class PendulumVectorEnv(_ClassicControlVectorEnv):
     KIND = "pendulum"
     _STATE_LIMITS = (((0,), 1e8),)  # th (never wrapped: pendulum.py:139-150)
     DEFAULT_MAX_EPISODE_STEPS = 200
+    # pendulum.py:103-108; an np.float64 m, l or max_torque would make the float32 torque terms float64 (NEP 50)
+    ENV_ATTRS = (("g", None, True), ("m", 1.0, False), ("l", 1.0, False), ("dt", 0.05, True), ("max_speed", 8, True), ("max_torque", 2.0, False))
 
     def __init__(self, num_envs: int = 1, max_episode_steps: int | None = None, g: float = 10.0, **kwargs):
         self.g = float(g)
+        self._env_attr_ctor = {"g": g}
         super().__init__(num_envs=num_envs, max_episode_steps=max_episode_steps, **kwargs)
 
     def _single_spaces(self):
@@ -246,6 +264,7 @@ class _MountainCarBase(_ClassicControlVectorEnv):
 
     def __init__(self, num_envs: int = 1, max_episode_steps: int | None = None, goal_velocity: float = 0, **kwargs):
         self.goal_velocity = goal_velocity
+        self._env_attr_ctor = {"goal_velocity": goal_velocity}
         super().__init__(num_envs=num_envs, max_episode_steps=max_episode_steps, **kwargs)
 
     def _obs_space(self):
@@ -263,6 +282,8 @@ class _MountainCarBase(_ClassicControlVectorEnv):
 class MountainCarVectorEnv(_MountainCarBase):
     KIND = "mountain_car"
     DEFAULT_MAX_EPISODE_STEPS = 200
+    ENV_ATTRS = (("force", 0.001, True), ("gravity", 0.0025, True), ("max_speed", 0.07, True), ("min_position", -1.2, True),
+                 ("max_position", 0.6, True), ("goal_position", 0.5, True), ("goal_velocity", None, True))  # mountain_car.py:109-116
 
     def _single_spaces(self):
         return self._obs_space(), spaces.Discrete(3)
@@ -271,6 +292,9 @@ class MountainCarVectorEnv(_MountainCarBase):
 class MountainCarContinuousVectorEnv(_MountainCarBase):
     KIND = "mountain_car_continuous"
     DEFAULT_MAX_EPISODE_STEPS = 999
+    # continuous_mountain_car.py:117-126; every one meets the float32 state or action, where an np.float64 would change the rounding (NEP 50)
+    ENV_ATTRS = (("min_action", -1.0, False), ("max_action", 1.0, False), ("power", 0.0015, False), ("max_speed", 0.07, False),
+                 ("min_position", -1.2, False), ("max_position", 0.6, False), ("goal_position", 0.45, False), ("goal_velocity", None, False))
 
     def _single_spaces(self):
         return self._obs_space(), spaces.Box(low=-1.0, high=1.0, shape=(1,), dtype=np.float32)

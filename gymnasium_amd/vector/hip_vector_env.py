@@ -841,6 +841,111 @@ class HipVectorEnv(VectorEnv):
             raise error.Error("policy=\"random\" needs the device-sampled action space")
         return GraphedSteps(self, actions, int(steps), policy)
 
+    # -- per-sub-environment attributes: SyncVectorEnv.get_attr / set_attr (vector/sync_vector_env.py:365-398) ---------------------------
+    # ENV_ATTRS: the attributes the reference's step() reads, in the engine's id order (include/mi355env.h MI_ATTR_*), as (name, default, whether
+    # an np.float64 value is accepted); a default of None is the constructor's value (_env_attr_ctor).  None: no per-lane physics.  Unlike the
+    # reference, set_attr does not create attributes: an unknown name raises AttributeError.
+    ENV_ATTRS: tuple | None = None
+    _env_attr_mask = 0  # bit k: attribute k was set (the engine runs the per-lane kernels once any is)
+
+    def _env_attr_refusal(self) -> str | None:
+        if self.ENV_ATTRS is None:
+            return (f"{type(self).__name__}: per-sub-environment attributes (get_attr / set_attr) exist for CartPole-v1, Pendulum-v1, MountainCar-v0 "
+                    "and MountainCarContinuous-v0 only")
+        return None
+
+    def _env_attr_id(self, name: str) -> int:
+        refusal = self._env_attr_refusal()
+        if refusal:
+            raise error.Error(refusal)
+        names = [a[0] for a in self.ENV_ATTRS]
+        if name not in names:
+            raise AttributeError(f"{type(self).__name__} has no per-sub-environment attribute {name!r}; the supported names are {', '.join(names)} "
+                                 "(the attributes the reference's step() reads: set_attr does not create new ones)")
+        return names.index(name)
+
+    def _env_attr_default(self, k: int):
+        name, default, _ = self.ENV_ATTRS[k]
+        return self._env_attr_ctor[name] if default is None else default
+
+    def get_attr(self, name: str) -> tuple:
+        """The attribute of every sub-environment, as set_attr stored it (Python types kept); before any set_attr the reference's defaults."""
+        self._check_open()
+        self._check_not_pending("get_attr")
+        k = self._env_attr_id(name)
+        vals = self.__dict__.get("_env_attr_values", {}).get(name)
+        if vals is None:
+            return (self._env_attr_default(k),) * self.num_envs
+        if isinstance(vals, str):  # "device": set from a device tensor, read back
+            return tuple(self._engine.get_env_attr(k).tolist())
+        return tuple(vals)
+
+    def set_attr(self, name: str, values) -> None:
+        """Set an attribute of the sub-environments (SyncVectorEnv.set_attr): a list or tuple gives one value per sub-environment, anything else
+        one value for all; a 1-D ndarray or tensor of num_envs entries is per sub-environment too (as ``values.tolist()``; a CUDA tensor is copied
+        on the device, without synchronising).  Takes effect from the next step(); reset() does not undo it.  Python numbers behave as in the
+        reference; NumPy scalars are refused where NumPy 2 would round the reference's arithmetic differently for them (TypeError)."""
+        self._check_open()
+        self._check_not_pending("set_attr")
+        k = self._env_attr_id(name)
+        _, _, f64_ok = self.ENV_ATTRS[k]
+        N = self.num_envs
+        integrator = name == "kinematics_integrator"
+
+        def wrong_length(n):
+            return ValueError("Values must be a list or tuple with length equal to the number of environments. "
+                              f"Got `{n}` values for {N} environments.")
+
+        dev = None
+        if type(values).__module__.split(".")[0] == "torch" and hasattr(values, "dim"):
+            if values.dim() != 1 or values.shape[0] != N:
+                raise wrong_length(values.shape[0] if values.dim() else 1)
+            if values.device.type == "cuda":
+                if integrator:
+                    raise TypeError("set_attr('kinematics_integrator') takes strings, not a tensor")
+                dev = values
+            else:
+                values = values.tolist()
+        elif isinstance(values, np.ndarray):
+            if values.ndim != 1 or values.shape[0] != N:
+                raise wrong_length(values.shape[0] if values.ndim else 1)
+            values = values.tolist()
+        elif not isinstance(values, (list, tuple)):
+            values = [values for _ in range(N)]
+        if dev is None:
+            if len(values) != N:
+                raise wrong_length(len(values))
+            if integrator:
+                row = np.array([0.0 if (isinstance(v, str) and v == "euler") else 1.0 for v in values])
+            else:
+                for v in values:
+                    if isinstance(v, np.generic):
+                        if not (f64_ok and type(v) is np.float64):
+                            why = ("NumPy 2 would round the reference's float32 arithmetic differently for it" if not f64_ok else
+                                   "of the NumPy scalars only np.float64 is accepted here")
+                            raise TypeError(f"set_attr({name!r}): a {type(v).__name__} value -- {why}; pass float(v)")
+                    elif not isinstance(v, (bool, int, float)):
+                        raise TypeError(f"set_attr({name!r}) takes numbers, got {type(v).__name__}")
+                row = np.array([float(v) for v in values], dtype=np.float64)
+        if not hasattr(self._engine.lib, "set_env_attr"):
+            raise error.Error(f"set_attr({name!r}): the engine behind this env has no per-sub-environment attributes (mi_set_env_attr)")
+        if dev is not None:
+            t = self._torch if "_torch" in self.__dict__ else __import__("torch")
+            d = dev.to(dtype=t.float64).contiguous()
+            if self.output == "torch":
+                self._bind_stream()  # the copy is ordered after what produced the tensor on torch's stream
+            else:
+                t.cuda.current_stream(d.device).synchronize()
+            self._engine.set_env_attr(k, d.data_ptr(), on_device=True)
+            if self.output != "torch" or d is not dev:
+                self._engine.synchronize()  # (the engine's stream is not the allocator's: keep `d` alive until the copy ran)
+            stored = "device"
+        else:
+            self._engine.set_env_attr(k, row)
+            stored = list(values)
+        self.__dict__.setdefault("_env_attr_values", {})[name] = stored
+        self._env_attr_mask = self._env_attr_mask | (1 << k)
+
     # -- bookkeeping -----------------------------------------------------------------------------------
     def statistics(self) -> dict:
         """Running totals kept on device: env_steps, reset_steps, episodes, return_sum, length_sum."""
@@ -924,6 +1029,7 @@ class GraphedSteps:
                 raise ValueError("the captured steps read `actions` in place at replay time: pass a contiguous tensor on the env's device with "
                                  "the action space's dtype (int64, or float32 / float64 rows for Box spaces)")
         self.env, self.steps, self.actions = env, steps, actions
+        self.attr_mask = env._env_attr_mask  # which kernels the graph holds (per-lane attributes: set_attr)
         self.graph = t.cuda.CUDAGraph()
         self.results = []
         if policy == "random":  # the per-lane states of the action stream must exist before the capture opens (mi_action_sample with T = 0)
@@ -947,6 +1053,9 @@ class GraphedSteps:
         env = self.env
         env._check_open()
         env._check_not_pending("replay")
+        if env._env_attr_mask != self.attr_mask:
+            raise error.Error("set_attr() has made the env read per-sub-environment attributes since this graph was captured; its kernels do not "
+                              "read them: capture the steps again")
         env._bind_stream()  # statistics() / synchronize() wait on the engine's stream: keep it the one the replay runs on
         self.graph.replay()
         return self.results[-1]

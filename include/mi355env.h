@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define MI355ENV_ABI_VERSION 7
+#define MI355ENV_ABI_VERSION 8
 
 typedef enum mi_status {
     MI_OK = 0,
@@ -343,6 +343,32 @@ int mi_get_state(mi_vecenv *env, double *state, int32_t *elapsed_steps, uint8_t 
 int mi_set_state(mi_vecenv *env, const double *state, const int32_t *elapsed_steps, const uint8_t *flags);
 /* Per-env PCG64 words, same layout as mi_seed (host pointer). */
 int mi_get_rng(mi_vecenv *env, uint64_t *pcg);
+
+/*
+ * Per-sub-environment physics (ABI 8): SyncVectorEnv.set_attr / get_attr (vector/sync_vector_env.py:365-398) on the attributes the scalar env's
+ * step() reads, for CARTPOLE, PENDULUM, MOUNTAIN_CAR and MOUNTAIN_CAR_CONTINUOUS (not with MI_CFG_SHARED_RNG or MI_CFG_FAST_MATH).
+ * mi_set_env_attr: `values` = num_envs float64, one per sub-environment, host (on_device = 0, staged before the call returns) or device memory
+ * (on_device = 1: a device-to-device copy enqueued on the env's stream); NULL restores the construction value.  Takes effect from the next
+ * mi_step / mi_rollout; resets do not undo it and mi_get_state does not include it.  The first call switches the env to the per-lane kernels,
+ * whose values live in device memory updated in place (a HIP graph captured after the switch sees later calls).
+ * mi_get_env_attr: the current values into `host_out` (num_envs float64); synchronises.
+ * The string kinematics_integrator is stored as 0 ("euler") / 1 (anything else: semi-implicit Euler, cartpole.py:185).
+ */
+enum {
+    MI_ATTR_CARTPOLE_GRAVITY = 0, MI_ATTR_CARTPOLE_MASSCART = 1, MI_ATTR_CARTPOLE_MASSPOLE = 2, MI_ATTR_CARTPOLE_TOTAL_MASS = 3,
+    MI_ATTR_CARTPOLE_LENGTH = 4, MI_ATTR_CARTPOLE_POLEMASS_LENGTH = 5, MI_ATTR_CARTPOLE_FORCE_MAG = 6, MI_ATTR_CARTPOLE_TAU = 7,
+    MI_ATTR_CARTPOLE_KINEMATICS_INTEGRATOR = 8, MI_ATTR_CARTPOLE_THETA_THRESHOLD_RADIANS = 9, MI_ATTR_CARTPOLE_X_THRESHOLD = 10,
+    MI_ATTR_CARTPOLE_COUNT = 11,
+    MI_ATTR_PENDULUM_G = 0, MI_ATTR_PENDULUM_M = 1, MI_ATTR_PENDULUM_L = 2, MI_ATTR_PENDULUM_DT = 3, MI_ATTR_PENDULUM_MAX_SPEED = 4,
+    MI_ATTR_PENDULUM_MAX_TORQUE = 5, MI_ATTR_PENDULUM_COUNT = 6,
+    MI_ATTR_MOUNTAIN_CAR_FORCE = 0, MI_ATTR_MOUNTAIN_CAR_GRAVITY = 1, MI_ATTR_MOUNTAIN_CAR_MAX_SPEED = 2, MI_ATTR_MOUNTAIN_CAR_MIN_POSITION = 3,
+    MI_ATTR_MOUNTAIN_CAR_MAX_POSITION = 4, MI_ATTR_MOUNTAIN_CAR_GOAL_POSITION = 5, MI_ATTR_MOUNTAIN_CAR_GOAL_VELOCITY = 6, MI_ATTR_MOUNTAIN_CAR_COUNT = 7,
+    MI_ATTR_MOUNTAIN_CAR_CONTINUOUS_MIN_ACTION = 0, MI_ATTR_MOUNTAIN_CAR_CONTINUOUS_MAX_ACTION = 1, MI_ATTR_MOUNTAIN_CAR_CONTINUOUS_POWER = 2,
+    MI_ATTR_MOUNTAIN_CAR_CONTINUOUS_MAX_SPEED = 3, MI_ATTR_MOUNTAIN_CAR_CONTINUOUS_MIN_POSITION = 4, MI_ATTR_MOUNTAIN_CAR_CONTINUOUS_MAX_POSITION = 5,
+    MI_ATTR_MOUNTAIN_CAR_CONTINUOUS_GOAL_POSITION = 6, MI_ATTR_MOUNTAIN_CAR_CONTINUOUS_GOAL_VELOCITY = 7, MI_ATTR_MOUNTAIN_CAR_CONTINUOUS_COUNT = 8
+};
+int mi_set_env_attr(mi_vecenv *env, int attr, const double *values, int on_device);
+int mi_get_env_attr(mi_vecenv *env, int attr, double *host_out);
 
 /*
  * Stateful vector wrappers as device epilogues of the step path.  All array arguments are DEVICE
