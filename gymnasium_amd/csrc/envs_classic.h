@@ -51,6 +51,8 @@ struct TwoPi {
 // transcendental.  v_div_scale leaves both operands alone unless an exponent is extreme (divisor or quotient near the ends of the range, or a
 // numerator below 2^-969), so for operands of ordinary magnitude the refined reciprocal depends on the divisor only and can be shared: the same
 // operations on the same values, hence the same quotient bit for bit, in 5 + 4 per quotient.  The caller guarantees the ranges (ordinary()).
+// Checked on the device against the IEEE quotient by tests/test_gpu_exact_math.py: divisors of every exponent in [2^-20, 2^20) and either sign,
+// numerators over all of ordinary() and its edges, the call sites' fallback outside it.
 struct SharedDivisor {
     double b, r;
     SharedDivisor() = default;  // (a member of a lane's register struct: CartPoleAttrs)
@@ -194,6 +196,7 @@ MI_DEV bool div_by_constant_in_range(double x) {
 // (v_div_scale scales neither operand and leaves VCC clear, so v_div_fmas is that FMA) and x finite with 2^-969 <= |x| and |x / y| far from the top
 // of the range (v_div_fixup then only gives the quotient the sign of x / y, which a nonzero q0 + e r already has).  NOT for x = 0 (q0 + e r is +0 for
 // x = -0), subnormal or tiny x (v_div_scale would rescale), infinities or NaNs: the caller's range test sends those lanes elsewhere.
+// (tests/test_gpu_unscaled_division.py and tests/test_gpu_exact_math.py: against `/` on the device and against the host's quotient.)
 MI_DEV double div_unscaled(double x, double y) {
     const double r0 = __builtin_amdgcn_rcp(y);
     const double r1 = __builtin_fma(r0, __builtin_fma(-y, r0, 1.0), r0);

@@ -10,9 +10,11 @@
 //   powf: log2 / exp2 in double precision with 16- and 32-entry tables, rounded to float at the end.
 // The per-lane table reads go through pointers so that a kernel can keep the tables in LDS (envs_classic.h); the host harness passes the
 // arrays below.
-// Arguments outside the plain path (0, subnormal, inf, nan, |2 log x| >= 512) fall back to x * x: pow(x, 2.0) is exact there or the
-// environments never produce them.  Tables: pow_tables.h (scripts/gen_pow_tables.py).  Checked against the running libm on millions of
-// arguments by tests/test_pow_exact.py.  Compile with -ffp-contract=off.
+// Arguments outside pow's plain path (0, subnormal, inf, nan, |2 log x| >= 512) fall back to x * x: pow(x, 2.0) is exact there or the
+// environments never produce them.  powf is restated over ALL floats: beyond the float range it returns e_powf.c's inf / +0 / least subnormal, and a
+// subnormal square is exp2's double rounded once (not x * x on the ties).  Tables: pow_tables.h (scripts/gen_pow_tables.py).  Checked against the running libm on millions of
+// arguments by tests/test_pow_exact.py (host build) and tests/test_gpu_exact_math.py (device build; powf over all 2^32 patterns in both).
+// Compile with -ffp-contract=off.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -199,7 +201,10 @@ MI_PW_DEV float squaref(const double *log2_tab, const uint64_t *exp2_tab, float 
     q = fma_(r2, a23, q);
     const double logx = fma_(a01, r2 * r2, q);
     const double ylogx = 2.0 * logx;
-    const bool huge = ((bits(ylogx) >> 47) & 0xffffu) > 0x80beu;  // |y log2 x| >= 126: over / underflow range: x * x
+    // e_powf.c beyond the float range: x^2 > 0x1.ffffffp127 overflows, 2 log2 x <= -150 underflows to +0, below -149 the result is the least subnormal
+    // (__math_may_uflowf: 0x1.4p-75f squared); everything between -- subnormal squares and the top two binades included -- is exp2's double rounded ONCE
+    // to float, which is not x * x on the ties among subnormals (found by the exhaustive device check, tests/hip/exact_math_check.hip)
+    const bool over = ylogx > 0x1.fffffffd1d571p+6, under = ylogx <= -150.0, least = ylogx < -149.0;
     // exp2_inline
     const double kdd0 = ylogx + MI_EXP2F_SHIFT_SCALED;
     const uint64_t ki = bits(kdd0);
@@ -210,8 +215,11 @@ MI_PW_DEV float squaref(const double *log2_tab, const uint64_t *exp2_tab, float 
     const double rr2 = rr * rr;
     const double y2 = fma_k<KASM>(rr, kExp2fPoly[2], 1.0);
     const double y3 = fma_(zq, rr2, y2);
-    const float res = (float)(y3 * from_bits(t));
-    return (special || huge) ? x * x : res;
+    float res = (float)(y3 * from_bits(t));
+    res = least ? 0x1p-149f : res;
+    res = under ? 0.0f : res;
+    res = over ? __builtin_inff() : res;
+    return special ? x * x : res;
 }
 
 // ... and the float32 square.  powf evaluates exp2(2 log2 x) in double precision (relative error 1.27 * 2^-26 at worst, e_powf.c's header) and rounds once,

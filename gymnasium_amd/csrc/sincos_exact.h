@@ -9,7 +9,8 @@
 // 1/128-spaced double-double table (sincos_table.h), same polynomials, and the same fused multiply-adds the compiler contracted (read off
 // the libm binary: each `fma` below is one vfmadd / vfnmadd there, each `*` `+` a separately rounded operation) -- makes the device results
 // equal bit for bit, and with them whole classic-control trajectories (tests/test_sincos_exact.py: millions of arguments against the
-// running libm on the CPU; tests/test_gpu_parity.py: array_equal against the oracle).
+// running libm on the CPU; tests/test_gpu_exact_math.py: the DEVICE build of every form the kernels call, 10^8 arguments against the same
+// libm and against recorded vectors; tests/test_gpu_parity.py: array_equal against the oracle).
 //
 // Range: |x| < 105414350 (0x419921FB): beyond it glibc switches to its 768-bit Payne-Hanek reduction (__branred), which no environment
 // of the path reaches (angles are wrapped or bounded by velocity limits x episode length); there this header falls back to ocml.
@@ -446,7 +447,10 @@ MI_SC_DEV void sincos_pair(const double *T6, double x, double &sn_out, double &c
 // representable) and branch-free: q = trunc(x (1 / Y)) is right or off by one (two roundings), the residual x - q Y is ONE fused
 // multiply-add -- exact whenever the right q is used, because then |x - q Y| < Y -- and a wrong q shows as a residual outside [0, Y)
 // (for x >= 0; mirrored for x < 0), which is redone with the neighbouring q.  ~25 instructions against ~56 of the general library routine
-// (Pendulum's angle_normalize, pendulum.py:281-282).  Checked against the C library on millions of arguments by tests/test_sincos_exact.py.
+// (Pendulum's angle_normalize, pendulum.py:281-282).  Checked against the C library on millions of arguments by tests/test_sincos_exact.py (host
+// build) and tests/test_gpu_exact_math.py (device build), both per binade of the quotient up to 2^52 -- random arguments and the multiples of Y
+// with both neighbours: no mismatch below 2^52 Y, the first ones beyond it.  That is a sample, not a proof, of the advertised limit; what
+// set_state() admits (|theta| <= 1e8, quotients below 2^24) is five orders of magnitude inside it.
 template <class Y>
 MI_SC_DEV double fmod_const(double x, Y) {
     constexpr double y = Y::value;
