@@ -19,7 +19,7 @@ FLAG_NEEDS_RESET, FLAG_STATE_F32 = 1, 2
 CFG_SOLVER_NEWTON = 1  # MI_CFG_SOLVER_NEWTON
 CFG_FAST_MATH = 2  # MI_CFG_FAST_MATH (classic control: device sin / cos and x * x instead of the libm restatements)
 CFG_SHARED_RNG = 4  # MI_CFG_SHARED_RNG (CartPole: the reference's CartPoleVectorEnv semantics -- one generator for all sub-environments)
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 ENV_KINDS = {"cartpole": 0, "pendulum": 1, "acrobot": 2, "mountain_car": 3, "mountain_car_continuous": 4,
              "half_cheetah": 5, "ant": 6, "humanoid": 7, "tabular": 8,
@@ -43,6 +43,8 @@ HOST_SYMBOLS = ["step_async", "step_wait", "host_buffers"]
 # HipVectorEnv.set_attr tells the two apart by whether the entry point is bound.
 HOST_SYMBOLS += ["set_env_attr", "get_env_attr"]
 WRAPPER_SYMBOLS = ["rms_create", "rms_destroy", "rms_get", "rms_set", "normalize_observation", "normalize_reward", "clip_reward", "set_step_epilogue"]
+# The normalisations over a whole trajectory (ABI 9): what the wrappers' rollout() runs over the output of mi_rollout.
+WRAPPER_SYMBOLS += ["wrapper_steps_workspace", "normalize_observation_steps", "normalize_reward_steps"]
 
 
 class MiConfig(C.Structure):
@@ -144,6 +146,9 @@ class NativeLib:
             self.normalize_reward = f("normalize_reward", [vp, vp, vp, vp, vp, vp, vp, i32, dbl, dbl, i32, i32, vp], i32)
             self.clip_reward = f("clip_reward", [i32, vp, vp, i32, vp, vp, vp], i32)
             self.set_step_epilogue = f("set_step_epilogue", [vp, C.POINTER(MiStepEpilogue)], i32)
+            self.wrapper_steps_workspace = f("wrapper_steps_workspace", [i32, i32, i32], C.c_int64)
+            self.normalize_observation_steps = f("normalize_observation_steps", [vp, vp, vp, i32, i32, i32, dbl, i32, vp, vp, C.c_int64], i32)
+            self.normalize_reward_steps = f("normalize_reward_steps", [vp, vp, vp, vp, vp, vp, vp, i32, i32, dbl, dbl, i32, i32, vp, vp, C.c_int64], i32)
             self.step_async = f("step_async", [vp, C.POINTER(MiStepIO)], i32)
             self.step_wait = f("step_wait", [vp], i32)
             self.host_buffers = f("host_buffers", [vp, C.POINTER(MiStepIO)], i32)

@@ -37,4 +37,18 @@ __device__ __forceinline__ void update_column(double &mean, double &var, double 
     mean = new_mean, var = rd<T>(M2 / tot);
 }
 
+// The same update from the batch moments themselves: the whole-trajectory passes (wrappers.hip mi_normalize_*_steps) sum every step before the
+// first update is known, so their sums are shifted by the running mean at ENTRY and the two moments are formed where the sums are folded, in
+// parallel over the steps: m1 = s1 / rows, batch_mean = rd<X>(shift + m1), batch_var = rd<X>(max(s2 / rows - m1 * m1, 0)) -- the variance does
+// not depend on the shift.  Everything after the two batch moments is the update above, operation by operation.
+template <class T>
+__device__ __forceinline__ void update_column_from_moments(double &mean, double &var, double count, double batch_mean, double batch_var, double rows) {
+    const double tot = count + rows;
+    const double delta = rd<T>(batch_mean - mean);
+    const double new_mean = rd<T>(mean + rd<T>(rd<T>(delta * rows) / tot));
+    const double m_a = rd<T>(var * count), m_b = rd<T>(batch_var * rows);
+    const double M2 = rd<T>(rd<T>(m_a + m_b) + rd<T>(rd<T>(rd<T>(rd<T>(delta * delta) * count) * rows) / tot));
+    mean = new_mean, var = rd<T>(M2 / tot);
+}
+
 }  // namespace mi_wrap

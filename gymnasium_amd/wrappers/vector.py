@@ -19,6 +19,12 @@ oracle/wrappers.py is test infrastructure), in one of two forms:
   ``epsilon``, ``min_reward``, ``max_reward``, ``update_running_mean``) are read at every step.
 * STAND-ALONE (any other env of this package, or a wrapper order the epilogue cannot express): passes of csrc/wrappers.hip over the arrays
   the engine produced; with ``output="torch"`` nothing leaves the GPU, NumPy batches are staged through the device.
+
+``rollout(T)`` of a wrapper returns what T consecutive ``step()`` calls through it would have returned, as the time-major device tensors
+of ``HipVectorEnv.rollout``, and leaves its statistics, accumulators and previous-done flags as those calls would have: each wrapper takes the
+trajectory the wrapper below returned and runs its pass over all T steps at once (mi_normalize_observation_steps, mi_normalize_reward_steps,
+mi_clip_reward over T * N elements) -- a fixed number of launches, on the handles ``step()`` uses, so ``step()``, ``rollout()`` and ``reset()``
+interleave like one long sequence of steps.  The scoping rule holds by construction: ``w.rollout`` applies the wrappers up to ``w``.
 """
 from __future__ import annotations
 
@@ -138,6 +144,18 @@ class VectorWrapper:
     def step(self, actions):
         return self.env.step(actions)
 
+    def rollout(self, num_steps, actions=None, **kwargs):
+        """``num_steps`` consecutive ``step()`` calls through this wrapper at once (HipVectorEnv.rollout): here, the wrapped env's own."""
+        return self.env.rollout(num_steps, actions, **kwargs)
+
+    def _workspace(self, steps, rows, dim):
+        """Scratch of the whole-trajectory passes: a tensor from the caching allocator, so that the library neither allocates nor synchronises."""
+        lib = _native.load_library()
+        size = lib.wrapper_steps_workspace(int(steps), int(rows), int(dim))
+        if size < 0:  # MI_ERR_INVALID_ARGUMENT: more than 65535 steps, or a step of 2^31 elements
+            lib.check(int(size))
+        return _torch().empty(size, dtype=_torch().uint8, device=f"cuda:{self._dev()}"), size
+
     def _step_fused(self, actions):
         """step() of a fused wrapper: mark this call as entered through `self` (the outermost fused wrapper of a call wins) and run the
         chain underneath -- the engine's step applies the epilogue of the members up to the entry (HipVectorEnv._sync_epilogue)."""
@@ -245,6 +263,9 @@ class NumpyToTorch(VectorWrapper):
         obs, rewards, terminations, truncations, infos = self.env.step(actions)
         return self._move(obs), self._move(rewards), self._move(terminations), self._move(truncations), self._move(infos)
 
+    def rollout(self, num_steps, actions=None, **kwargs):
+        return self._move(self.env.rollout(num_steps, actions, **kwargs))
+
 
 class NormalizeObservation(VectorWrapper):
     """stateful_observation.py:27-160."""
@@ -301,6 +322,21 @@ class NormalizeObservation(VectorWrapper):
             return self._step_fused(actions)
         obs, reward, terminated, truncated, info = self.env.step(actions)
         return self.observations(obs), reward, terminated, truncated, info
+
+    def rollout(self, num_steps, actions=None, **kwargs):
+        """T x ``step()``: obs_rms is updated from step t's batch, then step t is normalised with it (stateful_observation.py:144-160), for
+        all t in four launches.  float32 trajectories are normalised in place (the tensor is the rollout's own, nobody else holds it)."""
+        torch = _torch()
+        out = dict(self.env.rollout(num_steps, actions, **kwargs))
+        x = out["obs"].contiguous()
+        steps, rows = int(x.shape[0]), int(x.shape[1])
+        res = x if x.dtype == torch.float32 else torch.empty(x.shape, dtype=torch.float32, device=x.device)
+        ws, size = self._workspace(steps, rows, self.obs_rms.dim)
+        lib = self.obs_rms._lib
+        lib.check(lib.normalize_observation_steps(self.obs_rms._h, _stream(), C.c_void_p(x.data_ptr()), self._in_code, steps, rows, float(self.epsilon),
+                                                  int(self._update_running_mean), C.c_void_p(res.data_ptr()), C.c_void_p(ws.data_ptr()), size))
+        out["obs"] = res
+        return out
 
 
 class NormalizeReward(VectorWrapper):
@@ -361,6 +397,24 @@ class NormalizeReward(VectorWrapper):
                                        int(self._update_running_mean), C.c_void_p(out.data_ptr())))
         return obs, self._back(out, was_tensor), terminated, truncated, info
 
+    def rollout(self, num_steps, actions=None, **kwargs):
+        """T x ``step()`` (stateful_reward.py:150-176): one walk over t per sub-environment for the discounted returns and the previous-done
+        flags, return_rms updated step by step from them, every reward divided by the deviation after its own step.  In place."""
+        torch = _torch()
+        out = dict(self.env.rollout(num_steps, actions, **kwargs))
+        r = out["rewards"].to(torch.float64).contiguous()
+        te, tr = out["terminations"].contiguous(), out["truncations"].contiguous()
+        te8, tr8 = te.view(torch.uint8) if te.dtype == torch.bool else te, tr.view(torch.uint8) if tr.dtype == torch.bool else tr
+        steps, rows = int(r.shape[0]), int(r.shape[1])
+        ws, size = self._workspace(steps, rows, 1)
+        lib = self.return_rms._lib
+        lib.check(lib.normalize_reward_steps(self.return_rms._h, _stream(), C.c_void_p(self._acc.data_ptr()), C.c_void_p(self._prev.data_ptr()),
+                                             C.c_void_p(r.data_ptr()), C.c_void_p(te8.data_ptr()), C.c_void_p(tr8.data_ptr()), steps, rows,
+                                             float(self.gamma), float(self.epsilon), int(self._autoreset_mode == AutoresetMode.SAME_STEP),
+                                             int(self._update_running_mean), C.c_void_p(r.data_ptr()), C.c_void_p(ws.data_ptr()), size))
+        out["rewards"] = r
+        return out
+
 
 class ClipReward(VectorWrapper):
     """vectorize_reward.py:115-151 (transform_reward.ClipReward: np.clip(reward, min_reward, max_reward))."""
@@ -401,3 +455,16 @@ class ClipReward(VectorWrapper):
                                               None if lo is None else C.cast(C.byref(lo), C.c_void_p), None if hi is None else C.cast(C.byref(hi), C.c_void_p),
                                               C.c_void_p(out.data_ptr())))
         return obs, self._back(out, was_tensor), terminated, truncated, info
+
+    def rollout(self, num_steps, actions=None, **kwargs):
+        """T x ``step()``: np.clip over the T * N rewards of the trajectory, in place."""
+        torch = _torch()
+        out = dict(self.env.rollout(num_steps, actions, **kwargs))
+        r = out["rewards"].to(torch.float64).contiguous()
+        lo = None if self.min_reward is None else C.c_double(float(self.min_reward))
+        hi = None if self.max_reward is None else C.c_double(float(self.max_reward))
+        self._lib.check(self._lib.clip_reward(self._dev(), _stream(), C.c_void_p(r.data_ptr()), int(r.numel()),
+                                              None if lo is None else C.cast(C.byref(lo), C.c_void_p), None if hi is None else C.cast(C.byref(hi), C.c_void_p),
+                                              C.c_void_p(r.data_ptr())))
+        out["rewards"] = r
+        return out

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define MI355ENV_ABI_VERSION 8
+#define MI355ENV_ABI_VERSION 9
 
 typedef enum mi_status {
     MI_OK = 0,
@@ -407,12 +407,33 @@ int mi_normalize_reward(mi_running_stats *return_rms, void *hip_stream, float *a
 int mi_clip_reward(int device, void *hip_stream, const double *reward, int num_envs, const double *min_reward, const double *max_reward,
                    double *out);
 
+/*
+ * The two normalisations over a whole trajectory (ABI 9): the post-processing of mi_rollout's output, which the wrappers' step path
+ * cannot reach.  Each call equals T consecutive calls of the per-step function above on rows t = 0..T-1 -- the statistics are updated
+ * from step t's batch, then step t is normalised with the updated statistics (stateful_observation.py:144-160,
+ * stateful_reward.py:150-176), and a step without an active row leaves them alone -- in a fixed number of launches: nothing in step t
+ * depends on the normalised values of earlier steps.  Scratch memory is the caller's: `workspace` is a device pointer, 8-byte aligned,
+ * of at least mi_wrapper_steps_workspace(T, rows, dim) bytes (dim = 1 for the reward pass; -1 = bad argument: T in [1, 65535],
+ * rows * dim below 2^31), its contents are not kept between calls.  Nothing is allocated and nothing synchronises.
+ *   obs: [T][num_rows][dim] of obs_dtype, out: [T][num_rows][dim] float32; out may alias obs when obs_dtype is MI_F32.
+ *   reward / terminated / truncated / out: [T][num_envs]; out may alias reward.  accumulated and prev_done are read at entry and hold
+ *   the values after step T at exit.
+ * ClipReward over a trajectory is mi_clip_reward over T * num_envs elements.
+ */
+int64_t mi_wrapper_steps_workspace(int T, int rows, int dim);
+int mi_normalize_observation_steps(mi_running_stats *stats, void *hip_stream, const void *obs, int obs_dtype, int T, int num_rows,
+                                   double epsilon, int update, void *out, void *workspace, int64_t workspace_bytes);
+int mi_normalize_reward_steps(mi_running_stats *return_rms, void *hip_stream, float *accumulated, uint8_t *prev_done, const double *reward,
+                              const uint8_t *terminated, const uint8_t *truncated, int T, int num_envs, double gamma, double epsilon,
+                              int same_step, int update, double *out, void *workspace, int64_t workspace_bytes);
+
 /* The same three wrappers as the OUTPUT STAGE of the step kernel (classic-control kinds): mi_step / mi_step_async then return the wrapped
  * observations and rewards in place of the raw ones -- one extra launch per step (the normalisations need the statistics of the WHOLE batch,
  * stateful_observation.py:146-152) instead of the ten of the stand-alone passes, and no staging for host callers: the values are rewritten
  * before the step's single device-to-host copy.  Reward order: ClipReward (clip_pre) -> NormalizeReward -> ClipReward (clip_post); each part
  * optional.  The handles and arrays stay owned by the caller and must outlive the attachment; NULL detaches.  Fused rollouts (mi_rollout)
- * and resets are not affected (normalise a reset observation with mi_normalize_observation). */
+ * and resets are not affected: normalise a reset observation with mi_normalize_observation, a rollout's trajectory with
+ * mi_normalize_observation_steps / mi_normalize_reward_steps / mi_clip_reward on the same handles and arrays. */
 typedef struct mi_step_epilogue {
     mi_running_stats *obs_rms;     /* NormalizeObservation: float32 statistics of obs_dim columns, or NULL */
     double obs_epsilon;
