@@ -19,7 +19,7 @@ FLAG_NEEDS_RESET, FLAG_STATE_F32 = 1, 2
 CFG_SOLVER_NEWTON = 1  # MI_CFG_SOLVER_NEWTON
 CFG_FAST_MATH = 2  # MI_CFG_FAST_MATH (classic control: device sin / cos and x * x instead of the libm restatements)
 CFG_SHARED_RNG = 4  # MI_CFG_SHARED_RNG (CartPole: the reference's CartPoleVectorEnv semantics -- one generator for all sub-environments)
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 ENV_KINDS = {"cartpole": 0, "pendulum": 1, "acrobot": 2, "mountain_car": 3, "mountain_car_continuous": 4,
              "half_cheetah": 5, "ant": 6, "humanoid": 7, "tabular": 8,
@@ -42,6 +42,9 @@ HOST_SYMBOLS = ["step_async", "step_wait", "host_buffers"]
 # Per-sub-environment attributes (mi_set_env_attr / mi_get_env_attr, ABI 8): product library only -- the checker has no per-lane physics, and
 # HipVectorEnv.set_attr tells the two apart by whether the entry point is bound.
 HOST_SYMBOLS += ["set_env_attr", "get_env_attr"]
+# A rollout that also stores what step() returns besides the trajectory (mi_rollout_infos, ABI 10): product library only -- HipVectorEnv.rollout(infos=True)
+# tells the backends apart by whether the entry point is bound.
+HOST_SYMBOLS += ["rollout_infos"]
 WRAPPER_SYMBOLS = ["rms_create", "rms_destroy", "rms_get", "rms_set", "normalize_observation", "normalize_reward", "clip_reward", "set_step_epilogue"]
 # The normalisations over a whole trajectory (ABI 9): what the wrappers' rollout() runs over the output of mi_rollout.
 WRAPPER_SYMBOLS += ["wrapper_steps_workspace", "normalize_observation_steps", "normalize_reward_steps"]
@@ -68,6 +71,11 @@ class MiStepIO(C.Structure):
 class MiRolloutIO(C.Structure):
     _fields_ = [("actions_in", C.c_void_p), ("actions_out", C.c_void_p), ("obs", C.c_void_p), ("reward", C.c_void_p),
                 ("terminated", C.c_void_p), ("truncated", C.c_void_p), ("actions_in_dtype", C.c_int32), ("reserved", C.c_int32)]
+
+
+class MiRolloutExtra(C.Structure):
+    _fields_ = [("final_obs", C.c_void_p), ("episode_return", C.c_void_p), ("episode_length", C.c_void_p), ("info", C.c_void_p),
+                ("final_info", C.c_void_p)]
 
 
 class MiTabularTable(C.Structure):
@@ -154,6 +162,7 @@ class NativeLib:
             self.host_buffers = f("host_buffers", [vp, C.POINTER(MiStepIO)], i32)
             self.set_env_attr = f("set_env_attr", [vp, i32, vp, i32], i32)
             self.get_env_attr = f("get_env_attr", [vp, i32, vp], i32)
+            self.rollout_infos = f("rollout_infos", [vp, i32, C.POINTER(MiRolloutIO), C.POINTER(MiRolloutExtra)], i32)
 
     def _fn(self, name, argtypes, restype):
         fn = getattr(self.dll, self.prefix + name)
@@ -240,6 +249,7 @@ class Engine:
         self.obs_dtype, self.act_dtype = NP_DTYPES[lay.obs_dtype], NP_DTYPES[lay.act_dtype]
         self._step_io = MiStepIO()
         self._rollout_io = MiRolloutIO()
+        self._rollout_extra = MiRolloutExtra()
 
     def close(self):
         if self.handle is not None:
@@ -354,12 +364,20 @@ class Engine:
     def action_skip(self, draws: int):
         self.lib.check(self.lib.action_skip(self.handle, int(draws)))
 
-    def rollout(self, T, actions_in=None, actions_out=None, obs=None, reward=None, terminated=None, truncated=None, actions_in_dtype=MI_F32):
+    def rollout(self, T, actions_in=None, actions_out=None, obs=None, reward=None, terminated=None, truncated=None, actions_in_dtype=MI_F32, extra=None):
+        """mi_rollout; with ``extra`` -- dict(final_obs, episode_return, episode_length, info, final_info) of device addresses or None --
+        mi_rollout_infos, which stores those [T][N][...] arrays besides."""
         io = self._rollout_io
         io.actions_in_dtype = int(actions_in_dtype)
         io.actions_in, io.actions_out, io.obs = _ptr(actions_in), _ptr(actions_out), _ptr(obs)
         io.reward, io.terminated, io.truncated = _ptr(reward), _ptr(terminated), _ptr(truncated)
-        self.lib.check(self.lib.rollout(self.handle, int(T), C.byref(io)))
+        if extra is None:
+            self.lib.check(self.lib.rollout(self.handle, int(T), C.byref(io)))
+            return
+        ex = self._rollout_extra
+        for name, _ in MiRolloutExtra._fields_:
+            setattr(ex, name, _ptr(extra.get(name)))
+        self.lib.check(self.lib.rollout_infos(self.handle, int(T), C.byref(io), C.byref(ex)))
 
     def stats(self) -> dict:
         st = MiStats()

@@ -817,6 +817,14 @@ struct RolloutPtrs {
     double *reward;
     uint8_t *terminated, *truncated;
 };
+// What a rollout stores besides RolloutPtrs (mi_rollout_extra, same meaning; every member nullable): a kernel argument of its own, taken only by the
+// kernels that store them -- RolloutPtrs, which the two-role and the branch-free kernels take by value, stays what it is.
+struct RolloutExtra {
+    void *final_obs;
+    double *ep_ret;
+    int32_t *ep_len;
+    double *info, *final_info;
+};
 // MI_CFG_SHARED_RNG (include/mi355env.h): CartPoleVectorEnv's ONE generator on the device.  It is kept as a fixed BASE state (what mi_seed gave) plus
 // the number of draws taken since: draw number n of the stream is the output after skipping n steps ahead of the base (Brown's O(log n) jump through
 // the pow2 table), so every lane finds its own draws without a serial pass and nothing but two counters ever changes.
@@ -835,11 +843,14 @@ namespace mi_classic {
 int step(mi_vecenv *v, const mi_internal::StepPtrs &p, int act_kind);                                           // launch_step<E> of the env's kind
 int reset(mi_vecenv *v, const uint8_t *device_mask, int has_bounds, double b0, double b1, float *device_obs);  // reset_kernel<E>
 int rollout(mi_vecenv *v, const mi_internal::RolloutPtrs &p, const mi_internal::ActionStream &as, int T, bool sample, int actions_in_kind);
+// ... and with the per-step extras (mi_rollout_infos): always the one-role kernel, the instantiations that store them
+int rollout_infos(mi_vecenv *v, const mi_internal::RolloutPtrs &p, const mi_internal::RolloutExtra &ex, const mi_internal::ActionStream &as, int T, bool sample,
+                  int actions_in_kind);
 // MI_CFG_SHARED_RNG (CartPole only): reset = [bookkeeping, reset kernel]; step = [scan of the finished sub-environments, step kernel];
 // rollout = T x [policy sample,] step; recount = blk_done from the flag words (after mi_set_state)
 int shared_reset(mi_vecenv *v, float *device_obs);
 int shared_step(mi_vecenv *v, const mi_internal::StepPtrs &p);
-int shared_rollout(mi_vecenv *v, const mi_internal::RolloutPtrs &p, const mi_internal::ActionStream &as, int T, bool sample);
+int shared_rollout(mi_vecenv *v, const mi_internal::RolloutPtrs &p, const mi_internal::ActionStream &as, int T, bool sample, const mi_internal::RolloutExtra *ex = nullptr);
 int shared_recount(mi_vecenv *v);
 }  // namespace mi_classic
 namespace {
@@ -898,6 +909,88 @@ __global__ __launch_bounds__(kBlock) void rollout_kernel(DevEnv d, RolloutPtrs i
             if (FULL || io.reward) io.reward[t * N + i] = o.reward;
             if (FULL || io.terminated) io.terminated[t * N + i] = o.terminated;
             if (FULL || io.truncated) io.truncated[t * N + i] = o.truncated;
+        }
+        store_lane<E>(d, i, L);
+        if (q.have) {  // hand the unconsumed draws back to the env's generator
+#pragma unroll
+            for (int k = 0; k < E::NDRAWS; k++) q.rng.unstep();
+        }
+        store_rng_state(d, i, q.rng);
+        if (SAMPLE && as.lane) {  // (the addresses from an opaque copy of i: the compiler otherwise keeps the load's 64-bit addresses live through the loop)
+            int w = i;
+            hold_opaque(w);
+            as.lane[w] = (uint64_t)(astate >> 64), as.lane[(size_t)d.N + w] = (uint64_t)astate;
+        }
+    }
+    block_accumulate(d, st);
+}
+
+// mi_rollout_infos: rollout_kernel's loop (FULL = false) that also stores, per step, what step() returns besides the trajectory -- the finished episodes'
+// return / length rows and, under SAME_STEP, the final observations; zeros in the rows that finished nothing (RolloutExtra).  A kernel of its own, so that
+// rollout_kernel's instantiations stay the code they are; the one-role kernel on purpose -- the two-role kernel's env role has no registers to spare for
+// a second observation row, and its aux role would have to be handed it through the ring.  Any change to rollout_kernel's loop belongs here too
+// (tests/test_gpu_rollout_infos.py compares the two through step()).
+template <class E, int MODE, bool SAMPLE>
+__global__ __launch_bounds__(kBlock) void rollout_infos_kernel(DevEnv d, RolloutPtrs io, ActionStream as, int T, AttrDev at, RolloutExtra ex) {
+    constexpr bool FULL = false;
+    tables_init<E>();
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    LaneStats st = {0u, 0u, 0u, 0ull, 0.0};
+    if (i < d.N) {
+        Lane<E> L;
+        load_lane<E>(d, i, L);
+        {  // the lane's attributes and what they make invariant, once per launch (no-op for the types without attributes)
+            AttrRequest<E> ar;
+            ar.request(at, d, i);
+            ar.arrive(L.trig);
+        }
+        u128 astate = 0;
+        const u128 ainc = make_u128(as.inc_hi, as.inc_lo);
+        if (SAMPLE) {
+            if (as.lane_valid) {  // the lane's state from the last launch (or act_init_kernel)
+                astate = make_u128(as.lane[i], as.lane[(size_t)d.N + i]);
+            } else {  // skip ahead by (i + 1) draws: one affine map per set bit of (i + 1)
+                astate = make_u128(as.state_hi, as.state_lo);
+                uint32_t delta = (uint32_t)i + 1u;
+                for (int j = 0; delta; j++, delta >>= 1)
+                    if (delta & 1u) astate = as.pow2[j].mult * astate + as.pow2[j].plus;
+            }
+        }
+        (void)ainc;
+        const size_t N = (size_t)d.N;
+        ResetQueue<E> q;
+        q.have = 0u;
+        q.rng = load_rng(d, i);
+        // (per-kind unroll factor: 2 for Acrobot -- its long loop body schedules better as two steps, +4.6 %; 1 = none for the others, where 2 and 4
+        //  measured +-0.1 %; Acrobot x4: -6 %.  profiles/r04_maxilp_classic.txt)
+#pragma unroll E::ROLLOUT_UNROLL
+        for (int t = 0; t < T; t++) {
+            if ((t & (kRefillPeriod - 1)) == 0 && !q.have) q.refill();
+            typename E::Act a;
+            if (SAMPLE) {
+                a = action_of_state<E>(astate);
+                astate = as.jump_n.mult * astate + as.jump_n.plus;
+                if (FULL || io.actions_out) static_cast<typename E::Act *>(io.actions_out)[t * N + i] = a;
+            } else {
+                a = static_cast<const typename E::Act *>(io.actions_in)[t * N + i];
+            }
+            StepOut<E> o;
+            if (MODE == MI_AUTORESET_SAME_STEP) {  // (lane_step writes the row only when the episode ended)
+#pragma unroll
+                for (int k = 0; k < E::OBS; k++) o.final_obs[k] = 0.0f;
+            }
+            if (MODE == MI_AUTORESET_NEXT_STEP)
+                lane_step_fused<E, !SAMPLE>(d, L, a, o, st, q);
+            else
+                lane_step<E, MODE>(d, i, L, a, o, st, &q);
+            if (FULL || io.obs) store_row<E::OBS>(static_cast<float *>(io.obs) + (t * N + i) * E::OBS, o.obs);
+            if (FULL || io.reward) io.reward[t * N + i] = o.reward;
+            if (FULL || io.terminated) io.terminated[t * N + i] = o.terminated;
+            if (FULL || io.truncated) io.truncated[t * N + i] = o.truncated;
+            // lanes are consecutive sub-environments: coalesced rows at [t * N + i], like the stores above
+            if (ex.ep_ret) ex.ep_ret[t * N + i] = o.ep_ret;
+            if (ex.ep_len) ex.ep_len[t * N + i] = o.ep_len;
+            if (MODE == MI_AUTORESET_SAME_STEP && ex.final_obs) store_row<E::OBS>(static_cast<float *>(ex.final_obs) + (t * N + i) * E::OBS, o.final_obs);
         }
         store_lane<E>(d, i, L);
         if (q.have) {  // hand the unconsumed draws back to the env's generator
@@ -1725,8 +1818,10 @@ __global__ __launch_bounds__(kBlock) void mj_reset_kernel(DevEnv d, const uint8_
 
 // fused rollout: T steps per launch, Box action space sampled on device from the batched space's single PCG64 stream
 // (draw number (t*N + i)*NU + u belongs to lane i, component u, step t)
+// ex (mi_rollout_infos; all members NULL for mi_rollout): per step the info row, the finished episodes' return / length and, under SAME_STEP, the final
+// observation and info -- zeros in the rows that finished nothing.
 template <class E, int MODE, bool SAMPLE>
-__global__ __launch_bounds__(kBlock) void mj_rollout_kernel(DevEnv d, RolloutPtrs io, ActionStream as, int T, int obs_dim, int in_f64) {
+__global__ __launch_bounds__(kBlock) void mj_rollout_kernel(DevEnv d, RolloutPtrs io, ActionStream as, int T, int obs_dim, int in_f64, RolloutExtra ex) {
     const int i = blockIdx.x * kBlock + threadIdx.x;
     LaneStats st = {0u, 0u, 0u, 0ull, 0.0};
     if (i < d.N) {
@@ -1741,7 +1836,7 @@ __global__ __launch_bounds__(kBlock) void mj_rollout_kernel(DevEnv d, RolloutPtr
                 if (delta & 1u) astate = as.pow2[j].mult * astate + as.pow2[j].plus;
         }
         const size_t N = (size_t)d.N;
-        double scratch_obs[E::MAX_OBS];
+        double scratch_obs[E::MAX_OBS], scratch_info[E::INFO > 0 ? E::INFO : 1];
         for (int t = 0; t < T; t++) {
             float a[E::NU];
             mjx::ActRow row = {a, false};
@@ -1764,10 +1859,22 @@ __global__ __launch_bounds__(kBlock) void mj_rollout_kernel(DevEnv d, RolloutPtr
             int32_t out_len;
             bool te, tr;
             double *obs = io.obs ? static_cast<double *>(io.obs) + (t * N + i) * obs_dim : scratch_obs;
-            mj_lane_step<E, MODE>(d, i, L, row, obs, nullptr, nullptr, reward, te, tr, out_ret, out_len, st);
+            double *fobs = ex.final_obs ? static_cast<double *>(ex.final_obs) + (t * N + i) * obs_dim : nullptr;
+            double *finfo = ex.final_info ? ex.final_info + (t * N + i) * E::INFO : nullptr;
+            // (the finishing step's info reaches final_info through the info row: without a caller's array a private row serves)
+            double *info = ex.info ? ex.info + (t * N + i) * E::INFO : (finfo ? scratch_info : nullptr);
+            mj_lane_step<E, MODE>(d, i, L, row, obs, fobs, info, reward, te, tr, out_ret, out_len, st, nullptr, finfo);
             if (io.reward) io.reward[t * N + i] = reward;
             if (io.terminated) io.terminated[t * N + i] = te;
             if (io.truncated) io.truncated[t * N + i] = tr;
+            if (ex.ep_ret) ex.ep_ret[t * N + i] = out_ret;
+            if (ex.ep_len) ex.ep_len[t * N + i] = out_len;
+            if (!(te || tr)) {
+                if (fobs)
+                    for (int k = 0; k < obs_dim; k++) fobs[k] = 0.0;
+                if (finfo)
+                    for (int k = 0; k < E::INFO; k++) finfo[k] = 0.0;
+            }
         }
         mj_store<E>(d, i, L);
     }
@@ -2074,8 +2181,10 @@ __global__ __launch_bounds__(kBlock) void tab_reset_kernel(DevEnv d, const uint8
     tab_store(d, i, L);
     if (obs) tab_write_obs(d, L.s, obs, (size_t)i);
 }
-template <int MODE, bool SAMPLE, bool LDS, int TK>
-__global__ __launch_bounds__(kBlock) void tab_rollout_kernel(DevEnv d, RolloutPtrs io, ActionStream as, int T, int lds_bytes) {
+// EX (mi_rollout_infos): the loop also stores the rows of `ex` -- info (the "prob" column; a reset's is 1), the finished episodes' return / length and,
+// under SAME_STEP, the final state and the finishing transition's probability; zeros in the rows that finished nothing.  Without EX `ex` is not read.
+template <int MODE, bool SAMPLE, bool LDS, int TK, bool EX = false>
+__global__ __launch_bounds__(kBlock) void tab_rollout_kernel(DevEnv d, RolloutPtrs io, ActionStream as, int T, int lds_bytes, RolloutExtra ex) {
     // The transition table is read once per env-step through three levels of dependent loads (count / cumulative probabilities -> branch
     // -> successor, reward, flag); out of L2 that latency is the whole step (Taxi: 100 KB of tables).  When the launcher found that the
     // table fits (LDS) the workgroup first copies it into LDS -- layout: the f64 arrays, then the i32 arrays, then the flags --
@@ -2133,11 +2242,28 @@ __global__ __launch_bounds__(kBlock) void tab_rollout_kernel(DevEnv d, RolloutPt
             double reward, out_ret;
             int32_t out_len;
             bool te, tr, has_final;
-            tab_lane_step<MODE, TK>(d, i, L, a, obs, fin, has_final, reward, te, tr, out_ret, out_len, st, &rng);
+            double fin_prob = 0.0;
+            tab_lane_step<MODE, TK>(d, i, L, a, obs, fin, has_final, reward, te, tr, out_ret, out_len, st, &rng, EX ? &fin_prob : nullptr);
             if (io.obs) tab_write_obs<TK>(d, (double)obs, static_cast<int64_t *>(io.obs), t * N + i);
             if (io.reward) io.reward[t * N + i] = reward;
             if (io.terminated) io.terminated[t * N + i] = te;
             if (io.truncated) io.truncated[t * N + i] = tr;
+            if constexpr (EX) {
+                if (ex.ep_ret) ex.ep_ret[t * N + i] = out_ret;
+                if (ex.ep_len) ex.ep_len[t * N + i] = out_len;
+                if (ex.info && TK != kTabBlackjack) ex.info[t * N + i] = L.prob;
+                if (MODE == MI_AUTORESET_SAME_STEP && ex.final_obs) {
+                    int64_t *fo = static_cast<int64_t *>(ex.final_obs);
+                    if (has_final) {
+                        tab_write_obs<TK>(d, (double)fin, fo, t * N + i);
+                    } else if (TK == kTabBlackjack) {
+                        fo[3 * (t * N + i)] = 0, fo[3 * (t * N + i) + 1] = 0, fo[3 * (t * N + i) + 2] = 0;
+                    } else {
+                        fo[t * N + i] = 0;
+                    }
+                }
+                if (MODE == MI_AUTORESET_SAME_STEP && ex.final_info && TK != kTabBlackjack) ex.final_info[t * N + i] = has_final ? fin_prob : 0.0;
+            }
         }
         tab_store<TK>(d, i, L);
         store_rng_state(d, i, rng);
@@ -2862,6 +2988,29 @@ int launch_rollout(mi_vecenv *v, const RolloutPtrs &p, const ActionStream &as, i
     return MI_OK;
 }
 
+template <class E>
+int launch_rollout_infos(mi_vecenv *v, const RolloutPtrs &p, const RolloutExtra &ex, const ActionStream &as, int T, bool sample) {
+    const bool next_step = v->cfg.autoreset_mode == MI_AUTORESET_NEXT_STEP;
+    const AttrDev at = {v->d_attr, v->attr_mask};
+    const dim3 g(v->grid), b(kBlock);
+    if constexpr (E::ACT_KIND == MI_F64 || E::ACT_KIND == MI_F64_WEAK) {
+        if (sample) return fail(MI_ERR_INVALID_ARGUMENT, "the on-device policy samples float32 actions");
+        if (next_step)
+            hipLaunchKernelGGL((rollout_infos_kernel<E, MI_AUTORESET_NEXT_STEP, false>), g, b, 0, v->stream, v->d, p, as, T, at, ex);
+        else
+            hipLaunchKernelGGL((rollout_infos_kernel<E, MI_AUTORESET_SAME_STEP, false>), g, b, 0, v->stream, v->d, p, as, T, at, ex);
+    } else if (next_step && sample)
+        hipLaunchKernelGGL((rollout_infos_kernel<E, MI_AUTORESET_NEXT_STEP, true>), g, b, 0, v->stream, v->d, p, as, T, at, ex);
+    else if (next_step)
+        hipLaunchKernelGGL((rollout_infos_kernel<E, MI_AUTORESET_NEXT_STEP, false>), g, b, 0, v->stream, v->d, p, as, T, at, ex);
+    else if (sample)
+        hipLaunchKernelGGL((rollout_infos_kernel<E, MI_AUTORESET_SAME_STEP, true>), g, b, 0, v->stream, v->d, p, as, T, at, ex);
+    else
+        hipLaunchKernelGGL((rollout_infos_kernel<E, MI_AUTORESET_SAME_STEP, false>), g, b, 0, v->stream, v->d, p, as, T, at, ex);
+    HIP_TRY(hipGetLastError());
+    return MI_OK;
+}
+
 }  // namespace
 
 #ifdef MI_CLASSIC_TU
@@ -2882,6 +3031,10 @@ int reset(mi_vecenv *v, const uint8_t *dm, int has_bounds, double b0, double b1,
 int rollout(mi_vecenv *v, const RolloutPtrs &p, const ActionStream &as, int T, bool sample, int in_kind) {
     if (v->attr_mask) return dispatch_kind_attr(v->cfg.kind, in_kind, [&](auto env) -> int { return launch_rollout<decltype(env)>(v, p, as, T, sample); });
     return dispatch_kind_act(v->cfg.kind, (v->cfg.reserved[0] & MI_CFG_FAST_MATH) != 0, in_kind, [&](auto env) -> int { return launch_rollout<decltype(env)>(v, p, as, T, sample); });
+}
+int rollout_infos(mi_vecenv *v, const RolloutPtrs &p, const RolloutExtra &ex, const ActionStream &as, int T, bool sample, int in_kind) {
+    if (v->attr_mask) return dispatch_kind_attr(v->cfg.kind, in_kind, [&](auto env) -> int { return launch_rollout_infos<decltype(env)>(v, p, ex, as, T, sample); });
+    return dispatch_kind_act(v->cfg.kind, (v->cfg.reserved[0] & MI_CFG_FAST_MATH) != 0, in_kind, [&](auto env) -> int { return launch_rollout_infos<decltype(env)>(v, p, ex, as, T, sample); });
 }
 // ---- MI_CFG_SHARED_RNG: MI_ENV_CARTPOLE only (mi_create refuses the bit for every other kind) ---------------------------------------------
 template <class F>
@@ -2910,7 +3063,7 @@ int shared_step(mi_vecenv *v, const StepPtrs &p) {
         return (int)MI_OK;
     });
 }
-int shared_rollout(mi_vecenv *v, const RolloutPtrs &p, const ActionStream &as, int T, bool sample) {
+int shared_rollout(mi_vecenv *v, const RolloutPtrs &p, const ActionStream &as, int T, bool sample, const RolloutExtra *ex) {
     const size_t N = (size_t)v->cfg.num_envs;
     for (int t = 0; t < T; t++) {
         StepPtrs sp;
@@ -2930,6 +3083,10 @@ int shared_rollout(mi_vecenv *v, const RolloutPtrs &p, const ActionStream &as, i
         sp.reward = p.reward ? p.reward + (size_t)t * N : nullptr;
         sp.terminated = p.terminated ? p.terminated + (size_t)t * N : nullptr;
         sp.truncated = p.truncated ? p.truncated + (size_t)t * N : nullptr;
+        if (ex) {  // (the step kernel writes every row of the two: 0 where no episode ended)
+            sp.ep_ret = ex->ep_ret ? ex->ep_ret + (size_t)t * N : nullptr;
+            sp.ep_len = ex->ep_len ? ex->ep_len + (size_t)t * N : nullptr;
+        }
         if (const int rc = shared_step(v, sp)) return rc;
     }
     return MI_OK;
@@ -2988,9 +3145,12 @@ int launch_mj_step(mi_vecenv *v, MjStepPtrs mp) {
 
 // T vector steps with the cooperative physics: per step [sample actions ->] physics -> glue, all on the env's stream
 template <class E>
-int launch_mj_rollout_coop(mi_vecenv *v, const RolloutPtrs &p, const ActionStream &as, int T, bool sample, int in_f64) {
+int launch_mj_rollout_coop(mi_vecenv *v, const RolloutPtrs &p, const ActionStream &as, int T, bool sample, int in_f64, const RolloutExtra &ex) {
     const size_t N = (size_t)v->cfg.num_envs;
     const dim3 g(v->grid), b(kBlock);
+    // the glue kernel writes a final_obs / final_info row only where an episode ended (mi_step's contract): the other rows are zeros (mi_rollout_extra)
+    if (ex.final_obs) HIP_TRY(hipMemsetAsync(ex.final_obs, 0, (size_t)T * N * v->lay.obs_dim * sizeof(double), v->stream));
+    if (ex.final_info) HIP_TRY(hipMemsetAsync(ex.final_info, 0, (size_t)T * N * E::INFO * sizeof(double), v->stream));
     for (int t = 0; t < T; t++) {
         const void *act;
         if (sample) {
@@ -3010,6 +3170,12 @@ int launch_mj_rollout_coop(mi_vecenv *v, const RolloutPtrs &p, const ActionStrea
         mp.terminated = p.terminated ? p.terminated + (size_t)t * N : nullptr;
         mp.truncated = p.truncated ? p.truncated + (size_t)t * N : nullptr;
         mp.obs_dim = v->lay.obs_dim;
+        mp.final_obs = ex.final_obs ? static_cast<double *>(ex.final_obs) + (size_t)t * N * v->lay.obs_dim : nullptr;
+        mp.ep_ret = ex.ep_ret ? ex.ep_ret + (size_t)t * N : nullptr;
+        mp.ep_len = ex.ep_len ? ex.ep_len + (size_t)t * N : nullptr;
+        // (the finishing step's info reaches final_info through the info row: without a caller's array the env's own staging row serves)
+        mp.info = ex.info ? ex.info + (size_t)t * N * E::INFO : (ex.final_info ? v->d_info : nullptr);
+        mp.final_info = ex.final_info ? ex.final_info + (size_t)t * N * E::INFO : nullptr;
         const int rc = launch_mj_step<E>(v, mp);
         if (rc) return rc;
     }
@@ -3783,11 +3949,18 @@ int mi_action_seed(mi_vecenv *v, const uint64_t pcg[4]) {
     return MI_OK;
 }
 
-int mi_rollout(mi_vecenv *v, int T, const mi_rollout_io *io) {
+// mi_rollout (ex == nullptr) and mi_rollout_infos (ex: the arrays to store besides, at least one of them set).  Every `ex` branch below is an addition:
+// without it the dispatch is what it was before the extras existed.
+static int rollout_impl(mi_vecenv *v, int T, const mi_rollout_io *io, const RolloutExtra *ex) {
     if (!v || !io) return fail(MI_ERR_INVALID_ARGUMENT, "null argument");
     if (!v->was_reset) return fail(MI_ERR_STATE, "rollout before reset");
     if (T < 0) return fail(MI_ERR_INVALID_ARGUMENT, "T must be >= 0");
     if (v->cfg.autoreset_mode == MI_AUTORESET_DISABLED) return fail(MI_ERR_UNSUPPORTED, "rollout needs an autoreset mode");
+    if (ex) {
+        if ((ex->final_obs || ex->final_info) && v->cfg.autoreset_mode != MI_AUTORESET_SAME_STEP)
+            return fail(MI_ERR_INVALID_ARGUMENT, "final_obs / final_info exist under SAME_STEP autoreset only");
+        if ((ex->info || ex->final_info) && v->lay.info_dim == 0) return fail(MI_ERR_INVALID_ARGUMENT, "this env kind has no info columns (layout.info_dim == 0)");
+    }
     const bool sample = io->actions_in == nullptr;
     if (sample && !v->act_seeded) return fail(MI_ERR_STATE, "rollout without actions needs mi_action_seed");
     if (T == 0) return MI_OK;
@@ -3826,27 +3999,39 @@ int mi_rollout(mi_vecenv *v, int T, const mi_rollout_io *io) {
         }
         const int lb = (int)lds;
         const int tk = v->d.tab.nS < 0 ? kTabBlackjack : (v->d.tab_fickle_rows ? kTabFickle : kTabPlain);
-        auto launch = [&](auto mode, auto smp) {
+        auto launch_ex = [&](auto mode, auto smp, auto with_extras) {
             constexpr int M = decltype(mode)::value;
-            constexpr bool S = decltype(smp)::value;
+            constexpr bool S = decltype(smp)::value, X = decltype(with_extras)::value;
+            RolloutExtra e = {};
+            if constexpr (X) e = *ex;
             if (tk == kTabBlackjack)  // (no table)
-                hipLaunchKernelGGL((tab_rollout_kernel<M, S, false, kTabBlackjack>), g, b, 0, v->stream, v->d, p, as, T, lb);
+                hipLaunchKernelGGL((tab_rollout_kernel<M, S, false, kTabBlackjack, X>), g, b, 0, v->stream, v->d, p, as, T, lb, e);
             else if (tk == kTabFickle && lds)
-                hipLaunchKernelGGL((tab_rollout_kernel<M, S, true, kTabFickle>), g, b, lds, v->stream, v->d, p, as, T, lb);
+                hipLaunchKernelGGL((tab_rollout_kernel<M, S, true, kTabFickle, X>), g, b, lds, v->stream, v->d, p, as, T, lb, e);
             else if (tk == kTabFickle)
-                hipLaunchKernelGGL((tab_rollout_kernel<M, S, false, kTabFickle>), g, b, 0, v->stream, v->d, p, as, T, lb);
+                hipLaunchKernelGGL((tab_rollout_kernel<M, S, false, kTabFickle, X>), g, b, 0, v->stream, v->d, p, as, T, lb, e);
             else if (lds)
-                hipLaunchKernelGGL((tab_rollout_kernel<M, S, true, kTabPlain>), g, b, lds, v->stream, v->d, p, as, T, lb);
+                hipLaunchKernelGGL((tab_rollout_kernel<M, S, true, kTabPlain, X>), g, b, lds, v->stream, v->d, p, as, T, lb, e);
             else
-                hipLaunchKernelGGL((tab_rollout_kernel<M, S, false, kTabPlain>), g, b, 0, v->stream, v->d, p, as, T, lb);
+                hipLaunchKernelGGL((tab_rollout_kernel<M, S, false, kTabPlain, X>), g, b, 0, v->stream, v->d, p, as, T, lb, e);
         };
+        auto launch = [&](auto mode, auto smp) { launch_ex(mode, smp, std::false_type()); };
         typedef std::integral_constant<int, MI_AUTORESET_NEXT_STEP> NextT;
         typedef std::integral_constant<int, MI_AUTORESET_SAME_STEP> SameT;
         // the branch-free kernel for the collector's case: one plain table of <= 3 outcomes per (state, action) that fits into LDS in its packed form
         static const bool lean_on = !(getenv("MI355ENV_TAB_LEAN") && getenv("MI355ENV_TAB_LEAN")[0] == '0');  // "0": tab_rollout_kernel (A/B, tests)
         const int kl = v->d.tab.K == 1 ? 1 : 3;
         const size_t lean_lds = tk == kTabPlain && v->d.tab.nS > 0 ? (tab_lean_lds_bytes(v->d.tab.nS, v->d.tab.nA, kl) + 15) & ~(size_t)15 : 0;
-        if (next && sample && lean_on && tk == kTabPlain && !v->d.tab.env_table && v->d.tab.K <= 3 && lean_lds <= 150 * 1024) {
+        if (ex) {  // the general kernel stores the extras; the branch-free kernels below have no such outputs
+            if (next && sample)
+                launch_ex(NextT(), std::true_type(), std::true_type());
+            else if (next)
+                launch_ex(NextT(), std::false_type(), std::true_type());
+            else if (sample)
+                launch_ex(SameT(), std::true_type(), std::true_type());
+            else
+                launch_ex(SameT(), std::false_type(), std::true_type());
+        } else if (next && sample && lean_on && tk == kTabPlain && !v->d.tab.env_table && v->d.tab.K <= 3 && lean_lds <= 150 * 1024) {
             const bool full = p.actions_out && p.obs && p.reward && p.terminated && p.truncated;
             const int nA = v->d.tab.nA, start = v->tab_start_state;
             const bool apow2 = nA >= 2 && (nA & (nA - 1)) == 0;
@@ -3898,22 +4083,25 @@ int mi_rollout(mi_vecenv *v, int T, const mi_rollout_io *io) {
     } else if (is_mj(v->cfg.kind)) {
         rc = dispatch_mj(v->cfg.kind, [&](auto env) -> int {
             using E = decltype(env);
-            if (v->mj_coop) return launch_mj_rollout_coop<E>(v, p, as, T, sample, in_f64);
+            const RolloutExtra e = ex ? *ex : RolloutExtra{};
+            if (v->mj_coop) return launch_mj_rollout_coop<E>(v, p, as, T, sample, in_f64, e);
             const dim3 g(v->grid), b(kBlock);
             const bool next = v->cfg.autoreset_mode == MI_AUTORESET_NEXT_STEP;
             if (next && sample)
-                hipLaunchKernelGGL((mj_rollout_kernel<E, MI_AUTORESET_NEXT_STEP, true>), g, b, 0, v->stream, v->d, p, as, T, v->lay.obs_dim, in_f64);
+                hipLaunchKernelGGL((mj_rollout_kernel<E, MI_AUTORESET_NEXT_STEP, true>), g, b, 0, v->stream, v->d, p, as, T, v->lay.obs_dim, in_f64, e);
             else if (next)
-                hipLaunchKernelGGL((mj_rollout_kernel<E, MI_AUTORESET_NEXT_STEP, false>), g, b, 0, v->stream, v->d, p, as, T, v->lay.obs_dim, in_f64);
+                hipLaunchKernelGGL((mj_rollout_kernel<E, MI_AUTORESET_NEXT_STEP, false>), g, b, 0, v->stream, v->d, p, as, T, v->lay.obs_dim, in_f64, e);
             else if (sample)
-                hipLaunchKernelGGL((mj_rollout_kernel<E, MI_AUTORESET_SAME_STEP, true>), g, b, 0, v->stream, v->d, p, as, T, v->lay.obs_dim, in_f64);
+                hipLaunchKernelGGL((mj_rollout_kernel<E, MI_AUTORESET_SAME_STEP, true>), g, b, 0, v->stream, v->d, p, as, T, v->lay.obs_dim, in_f64, e);
             else
-                hipLaunchKernelGGL((mj_rollout_kernel<E, MI_AUTORESET_SAME_STEP, false>), g, b, 0, v->stream, v->d, p, as, T, v->lay.obs_dim, in_f64);
+                hipLaunchKernelGGL((mj_rollout_kernel<E, MI_AUTORESET_SAME_STEP, false>), g, b, 0, v->stream, v->d, p, as, T, v->lay.obs_dim, in_f64, e);
             HIP_TRY(hipGetLastError());
             return (int)MI_OK;
         });
     } else if (v->shared_rng) {
-        rc = mi_classic::shared_rollout(v, p, as, T, sample);
+        rc = mi_classic::shared_rollout(v, p, as, T, sample, ex);  // (T step launches: the step kernel's own outputs, row t of the caller's arrays)
+    } else if (ex) {
+        rc = mi_classic::rollout_infos(v, p, *ex, as, T, sample, in_kind);
     } else {
         rc = mi_classic::rollout(v, p, as, T, sample, in_kind);
     }
@@ -3924,6 +4112,14 @@ int mi_rollout(mi_vecenv *v, int T, const mi_rollout_io *io) {
         v->act_lane_valid = keep_lanes;  // ... and the lane states with it, where the kernel wrote them
     }
     return MI_OK;
+}
+
+int mi_rollout(mi_vecenv *v, int T, const mi_rollout_io *io) { return rollout_impl(v, T, io, nullptr); }
+
+int mi_rollout_infos(mi_vecenv *v, int T, const mi_rollout_io *io, const mi_rollout_extra *extra) {
+    if (!extra || !(extra->final_obs || extra->episode_return || extra->episode_length || extra->info || extra->final_info)) return rollout_impl(v, T, io, nullptr);
+    const RolloutExtra ex = {extra->final_obs, extra->episode_return, extra->episode_length, extra->info, extra->final_info};
+    return rollout_impl(v, T, io, &ex);
 }
 
 int mi_action_sample(mi_vecenv *v, int T, void *out, int loc) {

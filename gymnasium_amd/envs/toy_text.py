@@ -447,6 +447,17 @@ class TaxiVectorEnv(TabularVectorEnv):
     def _reset_infos(self, mask):
         return self._with_action_mask(super()._reset_infos(mask))
 
+    def _rollout_infos(self, x, obs, dones):
+        """... plus the action masks of the T observations (and, under SAME_STEP, of the final states): a table look-up on the device."""
+        t = self._torch
+        infos = super()._rollout_infos(x, obs, dones)
+        table = t.from_numpy(self._action_mask).to(self._tdev)
+        infos["action_mask"], infos["_action_mask"] = table[obs], t.ones_like(dones)
+        if "final_info" in infos:
+            infos["final_info"]["action_mask"] = t.where(dones[..., None], table[x["final_obs"]], 0).to(t.int8)
+            infos["final_info"]["_action_mask"] = dones
+        return infos
+
 
 # id -> (creator, max_episode_steps, reward_threshold, kwargs): gymnasium/envs/__init__.py:139-171
 class BlackjackVectorEnv(HipVectorEnv):

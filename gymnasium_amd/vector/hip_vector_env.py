@@ -627,13 +627,13 @@ class HipVectorEnv(VectorEnv):
         sub-env / none).  The KEY SET IS STATIC: a key no sub-env supplied in this step is still present (its `_key` mask is all False) --
         deciding otherwise would need the masks on the host, i.e. a synchronisation per step."""
         t, out = self._torch, {}
-        for name, start, width, in_reset in self._info_columns():
-            col = rows[:, start] if width == 0 else rows[:, start:start + width]
+        for name, start, width, in_reset in self._info_columns():  # (`...`: a rollout's matrices have a leading time axis, and so have its masks)
+            col = rows[..., start] if width == 0 else rows[..., start:start + width]
             mask = supplied if (in_reset or reset_rows is None) else (~reset_rows if supplied is None else supplied & ~reset_rows)
             if mask is None:
                 val, mask = (col.clone() if self.copy else col), self._all_true_t
             else:
-                val = t.where(mask if width == 0 else mask[:, None], col, 0.0)
+                val = t.where(mask if width == 0 else mask[..., None], col, 0.0)
             dt = self._info_dtype(name)
             if dt is not None:  # same dtypes as the NumPy infos (_info_dict)
                 val = val.to({np.float32: t.float32, np.int64: t.int64, np.int32: t.int32, np.bool_: t.bool}[dt])
@@ -750,7 +750,7 @@ class HipVectorEnv(VectorEnv):
         return tuple(block)
 
     # -- fused rollouts ---------------------------------------------------------------------------------
-    def rollout(self, num_steps: int, actions=None, *, return_actions: bool = True):
+    def rollout(self, num_steps: int, actions=None, *, return_actions: bool = True, infos: bool = False):
         """``num_steps`` consecutive ``step()`` calls in ONE kernel launch; trajectories are time-major tensors in HBM.
 
         With ``actions=None`` the random policy ``action_space.sample()`` (spaces/multi_discrete.py:176-178,
@@ -758,6 +758,15 @@ class HipVectorEnv(VectorEnv):
         advanced on the host by the number of draws consumed -- so
         ``rollout(T)`` == ``[step(action_space.sample()) for _ in range(T)]`` bit for bit.
         Requires ``output="torch"``.  Returns dict(obs, rewards, terminations, truncations[, actions]).
+
+        ``infos=True`` adds the key ``"infos"``: the fifth element of those ``step()`` calls, as ONE dict with the static key set of the
+        device-resident infos (_build_infos_device) whose tensors have a leading time axis -- the engine's info entries with their ``_key``
+        masks, under SAME_STEP ``final_obs`` / ``_final_obs`` and ``final_info`` / ``_final_info``, with episode statistics ``episode`` =
+        {"r", "l", "t"} and ``_episode`` (mi_rollout_infos: the kernels store these rows per step).  It equals ``torch.stack`` over the
+        ``step()`` calls' dicts wherever the mask is true and is ZERO elsewhere (``final_obs`` included, whose unfinished rows ``step()``
+        leaves stale).  ``"t"`` is a host wall-clock value: ONE ``time.perf_counter()`` reading per rollout call serves all its steps.
+        The env's bookkeeping (pending autoresets, episode clocks and count, the current final_obs / info / episode rows) ends as those
+        ``step()`` calls leave it; nothing synchronises for the kinds whose ``step()`` infos are device-resident.
         """
         self._check_open()
         if self.output != "torch":
@@ -766,6 +775,11 @@ class HipVectorEnv(VectorEnv):
             raise AssertionError("Call reset before using rollout.")
         t, eng, N, T = self._torch, self._engine, self.num_envs, int(num_steps)
         dev = self._tdev
+        if infos:
+            if not hasattr(getattr(eng, "lib", None), "rollout_infos"):
+                raise error.Error("rollout(infos=True): the engine behind this env does not store a rollout's infos (mi_rollout_infos)")
+            if T < 1:
+                raise ValueError(f"rollout(infos=True) needs num_steps >= 1, got {num_steps}")
         self._bind_stream()
         act_dtype = t.int64 if self._discrete else t.float32
         act_shape = (T, N) if self._discrete else (T, N, eng.act_dim)
@@ -788,8 +802,13 @@ class HipVectorEnv(VectorEnv):
         rew = t.empty((T, N), dtype=t.float64, device=dev)
         term = t.empty((T, N), dtype=t.bool, device=dev)
         trunc = t.empty((T, N), dtype=t.bool, device=dev)
-        eng.rollout(T, None if a_in is None else a_in.data_ptr(), None if a_out is None else a_out.data_ptr(),
-                    obs.data_ptr(), rew.data_ptr(), term.data_ptr(), trunc.data_ptr(), actions_in_dtype=in_dtype)
+        extra = self._rollout_extra_buffers(T) if infos else {}
+        if extra:
+            eng.rollout(T, None if a_in is None else a_in.data_ptr(), None if a_out is None else a_out.data_ptr(), obs.data_ptr(), rew.data_ptr(),
+                        term.data_ptr(), trunc.data_ptr(), actions_in_dtype=in_dtype, extra={k: v.data_ptr() for k, v in extra.items()})
+        else:
+            eng.rollout(T, None if a_in is None else a_in.data_ptr(), None if a_out is None else a_out.data_ptr(),
+                        obs.data_ptr(), rew.data_ptr(), term.data_ptr(), trunc.data_ptr(), actions_in_dtype=in_dtype)
         self._act_f64 = in_dtype == _native.MI_F64
         if actions is None and on_stream is None:
             self.action_space.np_random.bit_generator.advance(T * N * eng.act_dim)
@@ -798,6 +817,8 @@ class HipVectorEnv(VectorEnv):
             out["actions"] = a_out
         elif a_in is not None and return_actions:
             out["actions"] = a_in
+        if infos:  # (before the pending-autoreset set moves on: the first step's reset rows come from it)
+            out["infos"] = self._rollout_infos(extra, obs, term | trunc)
         # the vector env's "current" buffers follow the last step, as after T step() calls
         self._obs.copy_(obs[-1]); self._rew.copy_(rew[-1]); self._term.copy_(term[-1]); self._trunc.copy_(trunc[-1])
         if self.autoreset_mode == AutoresetMode.NEXT_STEP:  # the sub-envs that finished in the last step reset in the next one
@@ -806,6 +827,72 @@ class HipVectorEnv(VectorEnv):
             else:
                 self._was_done = (term[-1] | trunc[-1]).cpu().numpy()
         return out
+
+    def _rollout_extra_buffers(self, T: int) -> dict:
+        """The [T, N, ...] device tensors mi_rollout_infos fills for this configuration (keys: the members of mi_rollout_extra)."""
+        t, eng, N, dev = self._torch, self._engine, self.num_envs, self._tdev
+        same = self.autoreset_mode == AutoresetMode.SAME_STEP
+        x = {}
+        if same:
+            x["final_obs"] = t.empty((T,) + tuple(self._obs_shape), dtype=self._obs_tdtype, device=dev)
+        if self.record_episode_statistics:
+            x["episode_return"] = t.empty((T, N), dtype=t.float64, device=dev)
+            x["episode_length"] = t.empty((T, N), dtype=t.int32, device=dev)
+        if eng.info_dim:
+            x["info"] = t.empty((T, N, eng.info_dim), dtype=t.float64, device=dev)
+            if same:
+                x["final_info"] = t.empty((T, N, eng.info_dim), dtype=t.float64, device=dev)
+        return x
+
+    def _rollout_infos(self, x: dict, obs, dones) -> dict:
+        """The infos of the T steps of a rollout from the arrays the engine stored (``x``, _rollout_extra_buffers): _build_infos_device with a
+        leading time axis, including what it does to the env's bookkeeping.  ``dones``: terminations | truncations, [T, N]."""
+        t, N, T = self._torch, self.num_envs, int(dones.shape[0])
+        same = self.autoreset_mode == AutoresetMode.SAME_STEP
+        host_side = not self._device_infos  # (the kinds whose step() infos are assembled on the host keep their bookkeeping there)
+        infos: dict[str, Any] = {}
+        if self.INFO_KEYS and "info" in x:
+            if same:
+                reset_rows = dones
+            else:  # the rows in their autoreset step: the pending set before the call, then every step's finished rows
+                was = t.from_numpy(self._was_done.copy()).to(self._tdev) if host_side else self._was_done_t
+                reset_rows = t.cat([was[None], dones[:-1]])
+            infos.update(self._info_dict_device(x["info"], t.ones_like(dones), reset_rows))
+            self._info.copy_(x["info"][-1])
+        if same:
+            infos["final_obs"], infos["_final_obs"] = x["final_obs"], dones
+            has_finfo = bool(self.INFO_KEYS) and "final_info" in x
+            infos["final_info"], infos["_final_info"] = (self._info_dict_device(x["final_info"], dones, None) if has_finfo else {}), dones
+            # step() leaves the rows of sub-environments that finished nothing untouched: the current buffers end with each row's LAST finish
+            last = (dones * t.arange(1, T + 1, device=dones.device)[:, None]).amax(0)  # 0: never finished in this window
+            pick, cols = (last - 1).clamp_min(0), t.arange(N, device=dones.device)
+            for cur, arr in ((self._final, x["final_obs"]), (self._final_info, x["final_info"] if has_finfo else None)):
+                if cur is not None and arr is not None:
+                    got = arr[pick, cols]
+                    cur.copy_(t.where((last > 0).reshape((N,) + (1,) * (got.dim() - 1)), got, cur))
+        if self.record_episode_statistics:
+            now = time.perf_counter()  # ONE reading for all T steps
+            start = t.from_numpy(self._episode_start.copy()).to(self._tdev) if host_side else self._episode_start_t
+            prev = t.from_numpy(self._prev_dones.copy()).to(self._tdev) if host_side else self._prev_dones_t
+            # restarted[t]: the episode clock of the row was set to `now` by one of the steps before t (NEXT_STEP: in its autoreset step, i.e. the step
+            # after a finish -- the first one from the flags the call found; SAME_STEP: right after the finishing step)
+            first = t.zeros_like(prev) if same else prev
+            restarted = t.cat([first[None], dones[:-1]]).to(t.int32).cumsum(0) > 0
+            started = t.where(restarted, now, start[None])
+            infos["episode"] = {"r": x["episode_return"], "l": x["episode_length"].to(t.int64),
+                                "t": t.where(dones, t.round((now - started) * 1e6) / 1e6, 0.0)}
+            infos["_episode"] = dones
+            moved = (restarted[-1] | dones[-1]) if same else restarted[-1]
+            self._ep_r.copy_(x["episode_return"][-1]), self._ep_l.copy_(x["episode_length"][-1])
+            if host_side:
+                self._episode_start = t.where(moved, now, start).cpu().numpy()
+                self._prev_dones = dones[-1].cpu().numpy()
+                self._episode_count += int(dones.sum().item())
+            else:
+                self._episode_start_t.copy_(t.where(moved, now, start))
+                self._prev_dones_t.copy_(dones[-1])
+                self._episode_count_t.add_(dones.sum())
+        return infos
 
     # -- HIP graphs ------------------------------------------------------------------------------------
     def capture_steps(self, actions=None, steps: int = 1, policy=None):

@@ -212,18 +212,49 @@ class RecordEpisodeStatistics(VectorWrapper):
 
     def step(self, actions):
         obs, rewards, terminations, truncations, infos = self.env.step(actions)
-        if "_episode" in infos:
-            stats, dones = infos.pop("episode"), infos.pop("_episode")
-            if self._stats_key in infos or f"_{self._stats_key}" in infos:
-                raise ValueError(f"Attempted to add episode stats with key '{self._stats_key}' but this key already exists in info: {list(infos.keys())}")
-            infos[self._stats_key], infos[f"_{self._stats_key}"] = stats, dones
+        found = self._rename(infos)
+        if found is not None:
+            stats, dones = found
             # common.py:214-217: the queues take the finished episodes in sub-environment order.  Device-resident infos (output="torch"): the
             # queues live on the host, so this wrapper reads the done mask back every step (the env underneath does not synchronise by itself)
-            host = (lambda x: x.cpu().numpy()) if hasattr(dones, "cpu") else (lambda x: x)
-            idx = np.flatnonzero(host(dones))
-            if idx.size:
-                self.time_queue.extend(host(stats["t"])[idx]), self.return_queue.extend(host(stats["r"])[idx]), self.length_queue.extend(host(stats["l"])[idx])
+            self._extend_queues(stats, dones)
         return obs, rewards, terminations, truncations, infos
+
+    def _rename(self, infos):
+        """infos["episode"] / ["_episode"] under this wrapper's key (common.py:205-213); returns (stats, dones) or None when there are none."""
+        if "_episode" not in infos:
+            return None
+        stats, dones = infos.pop("episode"), infos.pop("_episode")
+        if self._stats_key in infos or f"_{self._stats_key}" in infos:
+            raise ValueError(f"Attempted to add episode stats with key '{self._stats_key}' but this key already exists in info: {list(infos.keys())}")
+        infos[self._stats_key], infos[f"_{self._stats_key}"] = stats, dones
+        return stats, dones
+
+    def _extend_queues(self, stats, dones):
+        """The finished episodes of one step ([N] arrays) or of a rollout ([T, N]: row-major, i.e. step by step and within a step in
+        sub-environment order -- the order T step() calls extend the queues in) onto the three queues."""
+        host = (lambda x: x.cpu().numpy()) if hasattr(dones, "cpu") else (lambda x: np.asarray(x))
+        idx = np.flatnonzero(host(dones).reshape(-1))
+        if idx.size:
+            self.time_queue.extend(host(stats["t"]).reshape(-1)[idx]), self.return_queue.extend(host(stats["r"]).reshape(-1)[idx])
+            self.length_queue.extend(host(stats["l"]).reshape(-1)[idx])
+
+    def rollout(self, num_steps, actions=None, **kwargs):
+        """T x ``step()`` through this wrapper: the wrapped rollout ALWAYS runs with ``infos=True`` (the kernels store every step's
+        finished-episode rows), so ``episode_count`` and the three queues end as those ``step()`` calls leave them -- the queues extended with the
+        finished episodes in the order the calls would have found them, ONE read-back per rollout where ``step()`` has one per step.  The
+        returned dict has the keys the caller asked for: ``"infos"`` (with ``episode`` / ``_episode`` under the wrapper's key) with
+        ``infos=True``, the bare trajectory otherwise, as before."""
+        wanted = bool(kwargs.get("infos", False))
+        kwargs["infos"] = True
+        out = dict(self.env.rollout(num_steps, actions, **kwargs))
+        infos = dict(out.pop("infos"))
+        found = self._rename(infos)
+        if found is not None:
+            self._extend_queues(*found)
+        if wanted:
+            out["infos"] = infos
+        return out
 
 
 class NumpyToTorch(VectorWrapper):

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define MI355ENV_ABI_VERSION 9
+#define MI355ENV_ABI_VERSION 10
 
 typedef enum mi_status {
     MI_OK = 0,
@@ -219,6 +219,23 @@ typedef struct mi_rollout_io {
     int32_t reserved;
 } mi_rollout_io;
 
+/* What step() returns besides obs / reward / flags, for every step of a fused rollout (ABI 10, mi_rollout_infos): device pointers, time-major,
+ * each nullable.  Row [t] of an array holds what mi_step_io's member of the same name holds after the t-th of T consecutive mi_step calls:
+ *   episode_return / episode_length   0 where the sub-environment did not finish an episode at step t
+ *   info                              the scalar env's info; its RESET info in rows that reset at step t (the NEXT_STEP autoreset step, a
+ *                                     finished row under SAME_STEP)
+ *   final_obs / final_info            SAME_STEP only: the last observation / info of the episode, in rows that finished at step t
+ * ONE deliberate difference from mi_step, which leaves the final_obs / final_info rows of sub-environments that finished nothing untouched:
+ * here those rows are written as ZEROS, so every element of every requested array is defined after the call and the caller needs no memset
+ * pass.  The mask of the rows that carry a value is terminated | truncated of the same step (mi_rollout_io). */
+typedef struct mi_rollout_extra {
+    void *final_obs;          /* [T][N][obs_dim] obs_dtype */
+    double *episode_return;   /* [T][N] */
+    int32_t *episode_length;  /* [T][N] */
+    double *info;             /* [T][N][info_dim]; NULL when layout.info_dim == 0 */
+    double *final_info;       /* [T][N][info_dim]; NULL when layout.info_dim == 0 */
+} mi_rollout_extra;
+
 /* Running totals kept on device (the multi-GPU metric all-reduce operates on these three numbers). */
 typedef struct mi_stats {
     uint64_t env_steps;       /* sub-env steps that advanced dynamics (utils/performance.py:88-90 counting) */
@@ -313,6 +330,13 @@ int mi_tabular_load(mi_vecenv *env, const mi_tabular_table *table);
  * bit-for-bit in a single launch. */
 int mi_action_seed(mi_vecenv *env, const uint64_t pcg[4]);
 int mi_rollout(mi_vecenv *env, int T, const mi_rollout_io *io);
+/* mi_rollout that also stores the arrays of `extra` (ABI 10).  extra == NULL, or all its members NULL, IS mi_rollout(env, T, io): the same
+ * dispatch and the same kernels.  With a member set, the classic-control kinds run the one-role rollout kernel's variant that stores them
+ * (never the two-role kernel), ToyText the general tabular kernel (never the branch-free ones), the MuJoCo kinds their rollout path.
+ * final_obs / final_info under NEXT_STEP, and info / final_info for a kind without info columns: MI_ERR_INVALID_ARGUMENT; DISABLED autoreset:
+ * MI_ERR_UNSUPPORTED, like mi_rollout.  The action stream advances as in mi_rollout (one position, shared with mi_step(actions == NULL) and
+ * mi_action_sample); nothing allocates and nothing synchronises. */
+int mi_rollout_infos(mi_vecenv *env, int T, const mi_rollout_io *io, const mi_rollout_extra *extra);
 /* The action stream as a sampler of its own (ABI 7).  All three keep ONE position: whatever draws mi_rollout / mi_step(actions == NULL) /
  * mi_action_sample consume, the next consumer continues where the last one stopped, exactly like successive `action_space.sample()` calls on
  * the reference's seeded space (spaces/space.py:112-122 seed(), spaces/multi_discrete.py:176-178, spaces/box.py:463-465 sample()).
