@@ -45,6 +45,9 @@ HOST_SYMBOLS += ["set_env_attr", "get_env_attr"]
 # A rollout that also stores what step() returns besides the trajectory (mi_rollout_infos, ABI 10): product library only -- HipVectorEnv.rollout(infos=True)
 # tells the backends apart by whether the entry point is bound.
 HOST_SYMBOLS += ["rollout_infos"]
+# action_space.sample(mask=...) / sample(probability=...) on the action stream and the generator's pending 32-bit half (added to ABI 10, which they leave as it is): product library only --
+# the device-sampled space (vector/device_policy.py) tells the backends apart by whether the entry point is bound.
+HOST_SYMBOLS += ["action_sample_masked", "action_sample_weighted", "action_get_buffered", "action_set_buffered"]
 WRAPPER_SYMBOLS = ["rms_create", "rms_destroy", "rms_get", "rms_set", "normalize_observation", "normalize_reward", "clip_reward", "set_step_epilogue"]
 # The normalisations over a whole trajectory (ABI 9): what the wrappers' rollout() runs over the output of mi_rollout.
 WRAPPER_SYMBOLS += ["wrapper_steps_workspace", "normalize_observation_steps", "normalize_reward_steps"]
@@ -163,9 +166,16 @@ class NativeLib:
             self.set_env_attr = f("set_env_attr", [vp, i32, vp, i32], i32)
             self.get_env_attr = f("get_env_attr", [vp, i32, vp], i32)
             self.rollout_infos = f("rollout_infos", [vp, i32, C.POINTER(MiRolloutIO), C.POINTER(MiRolloutExtra)], i32)
+            self.action_sample_masked = f("action_sample_masked", [vp, vp, vp, i32], i32)
+            self.action_sample_weighted = f("action_sample_weighted", [vp, vp, vp, i32], i32)
+            self.action_get_buffered = f("action_get_buffered", [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)], i32)
+            self.action_set_buffered = f("action_set_buffered", [vp, C.c_uint32, C.c_uint32], i32)
 
     def _fn(self, name, argtypes, restype):
-        fn = getattr(self.dll, self.prefix + name)
+        try:
+            fn = getattr(self.dll, self.prefix + name)
+        except AttributeError:  # entry points added without a new ABI number: a build from before them passes the version check
+            raise ImportError(f"{self.path}: no {self.prefix}{name}; the library is older than this binding, rebuild it") from None
         fn.argtypes, fn.restype = argtypes, restype
         return fn
 
@@ -216,11 +226,18 @@ def pcg_words(gen: np.random.Generator) -> np.ndarray:
     return np.array([s >> 64, s & m, i >> 64, i & m], dtype=np.uint64)
 
 
-def set_pcg_words(gen: np.random.Generator, words) -> None:
+def pcg_buffered(gen: np.random.Generator):
+    """(has_uint32, uinteger): the 32-bit half a NumPy PCG64 keeps between two 32-bit draws (what a masked ``choice`` consumes)."""
+    st = gen.bit_generator.state
+    return int(st["has_uint32"]), int(st["uinteger"])
+
+
+def set_pcg_words(gen: np.random.Generator, words, has_uint32: int = 0, uinteger: int = 0) -> None:
+    """Move ``gen`` to {state_hi, state_lo, inc_hi, inc_lo}; ``has_uint32`` / ``uinteger``: its pending 32-bit half (default: none)."""
     st = gen.bit_generator.state
     st["state"]["state"] = (int(words[0]) << 64) | int(words[1])
     st["state"]["inc"] = (int(words[2]) << 64) | int(words[3])
-    st["has_uint32"], st["uinteger"] = 0, 0
+    st["has_uint32"], st["uinteger"] = int(has_uint32), int(uinteger)
     gen.bit_generator.state = st
 
 
@@ -363,6 +380,23 @@ class Engine:
 
     def action_skip(self, draws: int):
         self.lib.check(self.lib.action_skip(self.handle, int(draws)))
+
+    def action_sample_masked(self, mask, out, loc=MI_HOST):
+        """One batch of action_space.sample(mask=...): mask [N][A] int8, out [N] int64 (mi_action_sample_masked)."""
+        self.lib.check(self.lib.action_sample_masked(self.handle, _ptr(mask), _ptr(out), loc))
+
+    def action_sample_weighted(self, prob, out, loc=MI_HOST):
+        """One batch of action_space.sample(probability=...): prob [N][A] float64, out [N] int64 (mi_action_sample_weighted)."""
+        self.lib.check(self.lib.action_sample_weighted(self.handle, _ptr(prob), _ptr(out), loc))
+
+    def action_get_buffered(self):
+        """(has_uint32, uinteger) of the action stream's generator (mi_action_get_buffered); synchronises."""
+        has, val = C.c_uint32(), C.c_uint32()
+        self.lib.check(self.lib.action_get_buffered(self.handle, C.byref(has), C.byref(val)))
+        return int(has.value), int(val.value)
+
+    def action_set_buffered(self, has_uint32: int, uinteger: int):
+        self.lib.check(self.lib.action_set_buffered(self.handle, int(has_uint32), int(uinteger)))
 
     def rollout(self, T, actions_in=None, actions_out=None, obs=None, reward=None, terminated=None, truncated=None, actions_in_dtype=MI_F32, extra=None):
         """mi_rollout; with ``extra`` -- dict(final_obs, episode_return, episode_length, info, final_info) of device addresses or None --

@@ -39,6 +39,7 @@
 #include "envs_classic.h"
 #include "wrappers_internal.h"
 #include "pcg64_dev.h"
+#include "action_mask_internal.h"
 #ifndef MI_CLASSIC_TU
 #include "mjx_kernels.h"
 #include "mjx_coop.h"
@@ -2784,6 +2785,13 @@ struct mi_vecenv {
     // come from them.  attr_mask != 0 ("per-lane mode"): step and rollout run the *AttrT kernels (envs_classic.h); a bit, once set, stays set
     double *d_attr;
     uint32_t attr_mask;
+    // sample(mask=...) / sample(probability=...) on the action stream (action_mask.hip): the pending 32-bit half and the words of the batch in flight,
+    // the per-workgroup counts, the per-row slots; d_arg_stage: where a host caller's masks / probabilities are staged (MI_HOST only)
+    mi_actmask::Ctl *d_act_ctl;
+    uint32_t *d_act_partial, *d_act_slot;
+    void *d_arg_stage;
+    size_t arg_stage_bytes;
+    bool masked_force_repair;  // MI355ENV_MASKED_FORCE_REPAIR=1 at mi_create
 };
 
 namespace {
@@ -2885,6 +2893,8 @@ int raise_device_error(mi_vecenv *v) {  // precondition: the stream is idle (a k
         (void)hipStreamSynchronize(v->stream);
     }
     if (err == kErrInvalidAction) return fail(MI_ERR_INVALID_ARGUMENT, "action outside the action space");
+    if (err == mi_actmask::kErrInvalidSampleArg)
+        return fail(MI_ERR_INVALID_ARGUMENT, "action sampling: a mask value other than 0 / 1, or probabilities outside [0, 1] or not summing to 1; the batch was refused");
     return fail(MI_ERR_STATE, "DISABLED autoreset: a finished sub-environment was stepped without reset");
 }
 int check_device_error(mi_vecenv *v) {
@@ -3299,6 +3309,16 @@ static int create_buffers(mi_vecenv *v, const mi_config *cfg, int device) {
     HIP_TRY(hipMalloc(&d.blk_ret, sizeof(double) * v->grid));
     HIP_TRY(hipMalloc(&v->d_pow2, sizeof(PcgJump) * 64));
     HIP_TRY(hipMalloc(&v->d_act_lane, sizeof(uint64_t) * 2 * N));
+    HIP_TRY(hipMalloc((void **)&v->d_act_ctl, sizeof(mi_actmask::Ctl)));
+    HIP_TRY(hipMemsetAsync(v->d_act_ctl, 0, sizeof(mi_actmask::Ctl), v->stream));
+    if (v->lay.act_dim == 1 && v->lay.act_dtype == MI_I64) {  // the Discrete kinds: mi_action_sample_masked / _weighted never allocate
+        HIP_TRY(hipMalloc((void **)&v->d_act_partial, sizeof(uint32_t) * v->grid));
+        HIP_TRY(hipMalloc((void **)&v->d_act_slot, sizeof(uint32_t) * N));
+    }
+    {
+        const char *fr = getenv("MI355ENV_MASKED_FORCE_REPAIR");  // tests: every masked batch through the repair stage
+        v->masked_force_repair = fr && fr[0] == '1';
+    }
     v->shared_rng = (cfg->reserved[0] & MI_CFG_SHARED_RNG) != 0;
     if (v->shared_rng) {
         HIP_TRY(hipMalloc(&v->shared.words, sizeof(uint64_t) * 8));
@@ -3366,7 +3386,8 @@ void mi_destroy(mi_vecenv *v) {
     (void)hipStreamSynchronize(v->stream);
     void *ptrs[] = {v->d.state, v->d.meta, v->d.rng, v->d.ep_ret, v->d.ep_len, v->d.blk_count, v->d.blk_ret, v->d_out,
                     v->d_pow2, v->d_act_lane, v->d_act_stage, v->d_actions, v->d_mask, v->d_words, v->d_extras, v->d_act_scratch, v->d_obs_scratch,
-                    v->shared.words, v->d_shared_pow2, v->shared.blk_done, v->shared.blk_prefix, v->d_attr};
+                    v->shared.words, v->d_shared_pow2, v->shared.blk_done, v->shared.blk_prefix, v->d_attr,
+                    v->d_act_ctl, v->d_act_partial, v->d_act_slot, v->d_arg_stage};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     if (v->h_out) (void)hipHostFree(v->h_out);
@@ -3933,6 +3954,8 @@ int mi_action_seed(mi_vecenv *v, const uint64_t pcg[4]) {
     v->act_rng.state = make_u128(pcg[0], pcg[1]);
     v->act_rng.inc = inc;
     v->act_lane_valid = false, v->act_on_device = false;  // the host copy IS the position again
+    // a seeded generator has no pending 32-bit half (mi_action_set_buffered hands one over); the two words are adjacent in Ctl
+    HIP_TRY(hipMemsetAsync(&v->d_act_ctl->has_uint32, 0, 2 * sizeof(uint32_t), v->stream));
     if (!same_inc) {
         PcgJump tab[64];
         for (int j = 0; j < 64; j++) tab[j] = pcg_jump(inc, (u128)1 << j);
@@ -4164,6 +4187,75 @@ int mi_action_skip(mi_vecenv *v, int64_t draws) {
     const PcgJump j = pcg_jump(v->act_rng.inc, delta);
     v->act_rng.state = j.mult * v->act_rng.state + j.plus;
     v->act_lane_valid = false;
+    return MI_OK;
+}
+
+// ---- sample(mask=...) / sample(probability=...) (action_mask.hip) ---------------------------------------------------------------------------------
+static mi_actmask::Work actmask_work(const mi_vecenv *v, int A) {
+    mi_actmask::Work w;
+    memset(&w, 0, sizeof w);
+    w.ctl = v->d_act_ctl, w.partial = v->d_act_partial, w.slot = v->d_act_slot, w.lane = v->d_act_lane, w.pow2 = v->d_pow2, w.jump_n = v->jump_n;
+    w.inc_hi = (uint64_t)(v->act_rng.inc >> 64), w.inc_lo = (uint64_t)v->act_rng.inc;
+    w.error = v->d.error, w.N = v->cfg.num_envs, w.A = A, w.force_repair = v->masked_force_repair ? 1 : 0, w.stream = v->stream;
+    return w;
+}
+// weighted == false: `arg` = int8 masks [N][A]; true: float64 probabilities [N][A]
+static int action_sample_arg(mi_vecenv *v, const void *arg, void *out, int loc, bool weighted) {
+    const char *what = weighted ? "mi_action_sample_weighted" : "mi_action_sample_masked";
+    if (!v || !arg || !out) return fail(MI_ERR_INVALID_ARGUMENT, "%s: null argument", what);
+    if (loc != MI_HOST && loc != MI_DEVICE) return fail(MI_ERR_INVALID_ARGUMENT, "%s: loc must be MI_HOST or MI_DEVICE", what);
+    if (v->lay.act_dim != 1 || v->lay.act_dtype != MI_I64 || !v->d_act_slot) return fail(MI_ERR_UNSUPPORTED, "%s: Discrete action spaces only", what);
+    if (!v->act_seeded) return fail(MI_ERR_STATE, "%s needs mi_action_seed", what);
+    const int A = is_tab(v->cfg.kind) ? v->d.tab.nA : kNumActions[v->cfg.kind];
+    if (A < 1 || A > (weighted ? mi_actmask::kMaxWeightedActions : mi_actmask::kMaxMaskActions))
+        return fail(MI_ERR_UNSUPPORTED, weighted ? "%s: up to 7 actions (np.sum's order changes beyond)" : "%s: up to 64 actions", what);
+    if (set_device(v)) return MI_ERR_HIP;
+    if (*v->h_err) return check_device_error(v);  // an earlier asynchronous call left an error: raise it before anything is consumed
+    if (int rc = action_prepare_lanes(v)) return rc;
+    const size_t N = (size_t)v->cfg.num_envs, arg_bytes = N * (size_t)A * (weighted ? sizeof(double) : sizeof(int8_t));
+    const void *d_arg = arg;
+    int64_t *d_out = (int64_t *)out;
+    if (loc == MI_HOST) {
+        if (arg_bytes > v->arg_stage_bytes) {
+            HIP_TRY(hipStreamSynchronize(v->stream));
+            if (v->d_arg_stage) (void)hipFree(v->d_arg_stage);
+            v->d_arg_stage = nullptr, v->arg_stage_bytes = 0;
+            HIP_TRY(hipMalloc(&v->d_arg_stage, arg_bytes));
+            v->arg_stage_bytes = arg_bytes;
+        }
+        HIP_TRY(hipMemcpyAsync(v->d_arg_stage, arg, arg_bytes, hipMemcpyHostToDevice, v->stream));
+        d_arg = v->d_arg_stage, d_out = (int64_t *)v->d_actions;
+    }
+    const mi_actmask::Work w = actmask_work(v, A);
+    HIP_TRY(weighted ? mi_actmask::sample_weighted(w, (const double *)d_arg, d_out) : mi_actmask::sample_masked(w, (const int8_t *)d_arg, d_out));
+    v->act_on_device = true;  // (a refused batch leaves the lane states where they were: still the position)
+    if (loc == MI_HOST) {
+        if (int rc = check_device_error(v)) return rc;  // a refused batch: `out` is not written
+        HIP_TRY(hipMemcpyAsync(out, d_out, N * sizeof(int64_t), hipMemcpyDeviceToHost, v->stream));
+        HIP_TRY(hipStreamSynchronize(v->stream));
+    }
+    return MI_OK;
+}
+
+int mi_action_sample_masked(mi_vecenv *v, const int8_t *mask, void *out, int loc) { return action_sample_arg(v, mask, out, loc, false); }
+int mi_action_sample_weighted(mi_vecenv *v, const double *prob, void *out, int loc) { return action_sample_arg(v, prob, out, loc, true); }
+
+int mi_action_get_buffered(mi_vecenv *v, uint32_t *has_uint32, uint32_t *uinteger) {
+    if (!v || !has_uint32 || !uinteger) return fail(MI_ERR_INVALID_ARGUMENT, "null argument");
+    if (!v->act_seeded) return fail(MI_ERR_STATE, "mi_action_get_buffered needs mi_action_seed");
+    if (set_device(v)) return MI_ERR_HIP;
+    uint32_t w[2];
+    HIP_TRY(hipMemcpyAsync(w, &v->d_act_ctl->has_uint32, sizeof w, hipMemcpyDeviceToHost, v->stream));
+    HIP_TRY(hipStreamSynchronize(v->stream));
+    *has_uint32 = w[0], *uinteger = w[1];
+    return MI_OK;
+}
+
+int mi_action_set_buffered(mi_vecenv *v, uint32_t has_uint32, uint32_t uinteger) {
+    if (!v) return fail(MI_ERR_INVALID_ARGUMENT, "null env");
+    if (!v->act_seeded) return fail(MI_ERR_STATE, "mi_action_set_buffered follows mi_action_seed");
+    if (set_device(v)) return MI_ERR_HIP;
+    HIP_TRY(mi_actmask::set_buffered(actmask_work(v, 0), has_uint32, uinteger));
     return MI_OK;
 }
 

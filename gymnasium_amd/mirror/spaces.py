@@ -160,8 +160,27 @@ class Discrete(Space):
         super().__init__((), dtype, seed)
 
     def sample(self, mask=None, probability=None):
-        if mask is not None or probability is not None:
-            raise error.Error("masked sampling is outside the mirrored path; install gymnasium for it")
+        """Uniform; with ``mask`` (int8 of 0 / 1) uniform among the actions marked 1, ``start`` when there is none; with ``probability`` (float64 in
+        [0, 1] summing to 1) from that distribution (discrete.py:127-196)."""
+        if mask is not None and probability is not None:
+            raise ValueError(f"Only one of `mask` or `probability` can be provided, actual values: mask={mask}, probability={probability}")
+        n = int(self.n)
+        if mask is not None:
+            assert isinstance(mask, np.ndarray), f"The expected type of the sample mask is np.ndarray, actual type: {type(mask)}"
+            assert mask.dtype == np.int8, f"The expected dtype of the sample mask is np.int8, actual dtype: {mask.dtype}"
+            assert mask.shape == (n,), f"The expected shape of the sample mask is {(n,)}, actual shape: {mask.shape}"
+            allowed = mask == 1
+            assert np.all((mask == 0) | allowed), f"All values of the sample mask should be 0 or 1, actual values: {mask}"
+            if not allowed.any():
+                return self.start
+            return self.start + self.dtype.type(self.np_random.choice(np.flatnonzero(allowed)))
+        if probability is not None:
+            assert isinstance(probability, np.ndarray), f"The expected type of the sample probability is np.ndarray, actual type: {type(probability)}"
+            assert probability.dtype == np.float64, f"The expected dtype of the sample probability is np.float64, actual dtype: {probability.dtype}"
+            assert probability.shape == (n,), f"The expected shape of the sample probability is {(n,)}, actual shape: {probability.shape}"
+            assert np.all((probability >= 0) & (probability <= 1)), f"All values of the sample probability should be between 0 and 1, actual values: {probability}"
+            assert np.isclose(np.sum(probability), 1), f"The sum of the sample probability should be equal to 1, actual sum: {np.sum(probability)}"
+            return self.start + self.np_random.choice(np.arange(n, dtype=self.dtype), p=probability)
         return self.start + self.np_random.integers(self.n, dtype=self.dtype.type)
 
     def contains(self, x) -> bool:
@@ -195,9 +214,35 @@ class MultiDiscrete(Space):
         super().__init__(self.nvec.shape, dtype, seed)
 
     def sample(self, mask=None, probability=None):
-        if mask is not None or probability is not None:
-            raise error.Error("masked sampling is outside the mirrored path; install gymnasium for it")
+        """Uniform; with ``mask`` / ``probability`` -- a tuple nested like ``nvec``, one int8 / float64 row per sub-space -- every sub-space in index
+        order from the ONE generator (multi_discrete.py:143-247)."""
+        if mask is not None and probability is not None:
+            raise ValueError(f"Only one of `mask` or `probability` can be provided, actual values: mask={mask}, probability={probability}")
+        if mask is not None:
+            return np.array(self._sample_rows(mask, self.nvec, self.start, False), dtype=self.dtype)
+        if probability is not None:
+            return np.array(self._sample_rows(probability, self.nvec, self.start, True), dtype=self.dtype)
         return (self.np_random.random(self.nvec.shape) * self.nvec).astype(self.dtype) + self.start
+
+    def _sample_rows(self, rows, nvec, start, weighted):
+        name = "probability" if weighted else "mask"
+        if isinstance(nvec, np.ndarray):  # one level of the nesting: a tuple with one entry per element
+            assert isinstance(rows, tuple), f"Expects the {name} to be a tuple for nvec ({nvec}), actual type: {type(rows)}"
+            assert len(rows) == len(nvec), f"Expects the {name} length to be equal to the number of actions, {name} length: {len(rows)}, nvec length: {len(nvec)}"
+            return [self._sample_rows(r, n, s, weighted) for r, n, s in zip(rows, nvec, start)]
+        assert isinstance(rows, np.ndarray), f"Expects the sub {name} to be np.ndarray, actual type: {type(rows)}"
+        assert len(rows) == nvec, f"Expects the {name} length to be equal to the number of actions, {name} length: {len(rows)}, action: {nvec}"
+        if not weighted:
+            assert rows.dtype == np.int8, f"Expects the mask dtype to be np.int8, actual dtype: {rows.dtype}"
+            allowed = rows == 1
+            assert np.all((rows == 0) | allowed), f"Expects all masks values to 0 or 1, actual values: {rows}"
+            return self.np_random.choice(np.flatnonzero(allowed)) + start if allowed.any() else start
+        assert rows.dtype == np.float64, f"Expects the mask dtype to be np.float64, actual dtype: {rows.dtype}"
+        allowed = (rows > 0) & (rows <= 1)
+        assert np.all((rows == 0) | allowed), f"Expects all masks values to be between 0 and 1, actual values: {rows}"
+        total = np.sum(rows)
+        assert np.isclose(total, 1), f"Expects the sum of all mask values to be 1, actual sum: {total}"
+        return self.np_random.choice(np.flatnonzero(allowed), p=(rows / total)[allowed]) + start
 
     def contains(self, x) -> bool:
         if isinstance(x, (list, tuple)):

@@ -13,10 +13,20 @@ sub-environments costs more host time than the step costs the GPU.  The engine r
 * ``np_random`` stays the space's NumPy generator: reading it first returns the draws that were made ahead but not handed out
   (``mi_action_skip``) and moves the generator to the stream's position (``mi_action_get``), so mixing ``sample()``, ``np_random.random()``,
   ``env.rollout()`` and ``env.step(None)`` consumes ONE stream in call order, as in the reference.  ``seed()`` behaves as always.
-* masks / probabilities, spaces the sampler does not cover (unbounded Box, MultiDiscrete with a start) and detached spaces (pickled,
-  deep-copied, the env closed) take the reference's NumPy path.
+* ``sample(mask=...)`` / ``sample(probability=...)`` of the batched Discrete space are drawn by the engine too (``mi_action_sample_masked`` /
+  ``mi_action_sample_weighted``: the reference's ``_apply_mask`` over all rows, spaces/multi_discrete.py:180-249, from the same stream).  Besides the
+  reference's tuple of ``N`` rows they take ONE ``(N, A)`` array or torch tensor (``int8`` / ``float64``) -- what ``info["action_mask"]`` of a
+  HipVectorEnv is -- and a device tensor stays on the device: the call only enqueues.  Host rows are validated on the host with the reference's
+  exception types before anything is consumed; a device batch with an invalid row is refused as a whole and raised at the next synchronising
+  call (``env.synchronize()``), like an action outside the space.  A masked draw consumes 32-bit halves of the generator's outputs and may
+  leave one pending (``has_uint32`` / ``uinteger`` of ``bit_generator.state``): the half travels with the position in both directions.
+  Rows wider than the engine covers (64 actions masked, 7 weighted -- where ``np.sum`` stops being the left-to-right sum) and backends without
+  the entry points take the space's own NumPy path at the stream's position.
+* spaces the sampler does not cover (unbounded Box, MultiDiscrete with a start) and detached spaces (pickled, deep-copied, the env closed) take
+  the reference's NumPy path.
 
-Bit-equality with the NumPy sampler is pinned by tests/test_device_policy.py (host) and tests/test_gpu_device_policy.py (GPU).
+Bit-equality with the NumPy sampler is pinned by tests/test_device_policy.py (host) and tests/test_gpu_device_policy.py (GPU); the masked and
+weighted draws by tests/test_masked_sampling.py and tests/test_gpu_masked_sampling.py.
 """
 from __future__ import annotations
 
@@ -29,6 +39,34 @@ from ..gym_api import spaces
 
 RING_BYTES = 32 << 20  # draw-ahead per refill (at 65 536 CartPoles: 64 batches of 512 KB)
 RING_MAX = 256
+MAX_MASKED_ACTIONS, MAX_WEIGHTED_ACTIONS = 64, 7  # what mi_action_sample_masked / mi_action_sample_weighted cover (include/mi355env.h)
+
+
+def check_rows(arg, weighted: bool, n: int, a: int) -> np.ndarray:
+    """The masks (``int8``) or probabilities (``float64``) of ``n`` sub-spaces of ``a`` actions as ONE contiguous ``(n, a)`` array, from the
+    reference's tuple of rows or from an ``(n, a)`` array -- with the reference's checks (spaces/multi_discrete.py:188-237: type, length, dtype,
+    mask values 0 / 1, probabilities in [0, 1] summing to 1), all of them made before a single value is drawn."""
+    name, want = ("probability", np.float64) if weighted else ("mask", np.int8)
+    if isinstance(arg, np.ndarray) and arg.ndim == 2:
+        assert arg.shape == (n, a), f"Expects a {name} batch of shape {(n, a)}, actual shape: {arg.shape}"
+        assert arg.dtype == want, f"Expects the {name} dtype to be {np.dtype(want)}, actual dtype: {arg.dtype}"
+        rows = np.ascontiguousarray(arg)
+    else:
+        assert isinstance(arg, tuple), f"Expects the {name} to be a tuple of {n} arrays or one {(n, a)} array, actual type: {type(arg)}"
+        assert len(arg) == n, f"Expects one {name} per sub-space, {name} length: {len(arg)}, sub-spaces: {n}"
+        for row in arg:
+            assert isinstance(row, np.ndarray), f"Expects every {name} to be np.ndarray, actual type: {type(row)}"
+            assert row.shape == (a,), f"Expects the {name} length to be equal to the number of actions, {name} shape: {row.shape}, actions: {a}"
+            assert row.dtype == want, f"Expects the {name} dtype to be {np.dtype(want)}, actual dtype: {row.dtype}"
+        rows = np.stack(arg)
+    if weighted:
+        assert np.all((rows == 0) | ((rows > 0) & (rows <= 1))), f"Expects all {name} values to be between 0 and 1, actual values: {rows}"
+        # np.sum of a row: left to right up to 7 elements, pairwise beyond
+        sums = np.add.accumulate(rows, axis=1)[:, -1] if a <= MAX_WEIGHTED_ACTIONS else np.array([np.sum(row) for row in rows])
+        assert np.all(np.isclose(sums, 1)), f"Expects the sum of every {name} row to be 1, actual sums: {sums}"
+    else:
+        assert np.all((rows == 0) | (rows == 1)), f"Expects all {name} values to be 0 or 1, actual values: {rows}"
+    return rows
 
 
 class _DevicePolicyMixin:
@@ -61,13 +99,19 @@ class _DevicePolicyMixin:
             self._hip_ring, self._hip_pos = (), 0
             return
         self._hip_drop_ahead(eng)
-        _native.set_pcg_words(self._np_random, eng.action_get())
+        # the pending 32-bit half: from the engine where masked draws can change it, else the one handed over (64-bit draws leave it alone)
+        half = eng.action_get_buffered() if hasattr(eng.lib, "action_get_buffered") else self.__dict__.get("_hip_half", (0, 0))
+        _native.set_pcg_words(self._np_random, eng.action_get(), *half)
 
     def _hip_to_engine(self, eng):
         """The engine's action stream becomes the position (no-op while it already is)."""
         if self.__dict__.get("_hip_on_engine", False):
             return
-        eng.action_seed(_native.pcg_words(super().np_random))
+        gen = super().np_random
+        eng.action_seed(_native.pcg_words(gen))
+        self._hip_half = _native.pcg_buffered(gen)
+        if self._hip_half != (0, 0) and hasattr(eng.lib, "action_set_buffered"):
+            eng.action_set_buffered(*self._hip_half)
         self._hip_on_engine = True
 
     def hip_use_stream(self):
@@ -97,8 +141,10 @@ class _DevicePolicyMixin:
             if pos < len(ring):
                 d["_hip_pos"] = pos + 1
                 return ring[pos]
+        if mask is not None or probability is not None:
+            return self._hip_sample_with(mask, probability)
         env, eng = self._hip_engine()
-        if eng is None or mask is not None or probability is not None:
+        if eng is None:
             return super().sample(mask, probability)
         pos = self.__dict__.get("_hip_pos", 0)
         ring = self.__dict__.get("_hip_ring", ())
@@ -108,6 +154,10 @@ class _DevicePolicyMixin:
             pos = 0
         self._hip_pos = pos + 1
         return ring[pos]
+
+    def _hip_sample_with(self, mask, probability):
+        """sample(mask=...) / sample(probability=...): the space's own NumPy path (HipMultiDiscrete draws on the engine)."""
+        return super().sample(mask, probability)
 
     def __getstate__(self):
         self._hip_to_host()
@@ -125,7 +175,34 @@ class _DevicePolicyMixin:
 
 
 class HipMultiDiscrete(_DevicePolicyMixin, spaces.MultiDiscrete):
-    pass
+    def _hip_sample_with(self, mask, probability):
+        if mask is not None and probability is not None:
+            raise ValueError(f"Only one of `mask` or `probability` can be provided, actual values: mask={mask}, probability={probability}")
+        if self.nvec.ndim != 1:
+            self._hip_to_host()
+            return super()._hip_sample_with(mask, probability)
+        weighted = probability is not None
+        arg = probability if weighted else mask
+        n, a = int(self.nvec.shape[0]), int(self.nvec.flat[0])
+        env, eng = self._hip_engine()
+        on_engine = (eng is not None and hasattr(eng.lib, "action_sample_masked")
+                     and a <= (MAX_WEIGHTED_ACTIONS if weighted else MAX_MASKED_ACTIONS))
+        if hasattr(arg, "data_ptr") and not isinstance(arg, np.ndarray):  # a torch tensor: what can be checked without reading it is checked here
+            name, want = ("probability", "torch.float64") if weighted else ("mask", "torch.int8")
+            assert tuple(arg.shape) == (n, a), f"Expects a {name} batch of shape {(n, a)}, actual shape: {tuple(arg.shape)}"
+            assert str(arg.dtype) == want, f"Expects the {name} dtype to be {want}, actual dtype: {arg.dtype}"
+            if on_engine and env.output == "torch" and arg.device == env._tdev:
+                self.hip_use_stream()
+                return env._sample_with_rows(arg, weighted, on_device=True)
+            arg = arg.detach().cpu().numpy()
+        rows = check_rows(arg, weighted, n, a)
+        if on_engine:
+            self.hip_use_stream()
+            return env._sample_with_rows(rows, weighted, on_device=False)
+        self._hip_to_host()
+        rows = tuple(rows)
+        out = spaces.MultiDiscrete.sample(self, mask=None if weighted else rows, probability=rows if weighted else None)
+        return env._as_sample(out) if eng is not None else out
 
 
 class HipBox(_DevicePolicyMixin, spaces.Box):

@@ -749,6 +749,39 @@ class HipVectorEnv(VectorEnv):
         eng.action_sample(K, block, _native.MI_HOST)
         return tuple(block)
 
+    def _as_sample(self, batch: np.ndarray):
+        """A batch of actions drawn on the host as what ``action_space.sample()`` of this env returns (``sample_output``)."""
+        if self.sample_output == "torch" and self.output == "torch":
+            return self._torch.from_numpy(batch).to(self._tdev)
+        return batch
+
+    def _sample_with_rows(self, rows, weighted: bool, on_device: bool):
+        """One batch of ``action_space.sample(mask=rows)`` / ``sample(probability=rows)`` from the engine's action stream
+        (mi_action_sample_masked / mi_action_sample_weighted).  ``rows``: the ``(N, A)`` masks (int8) or probabilities (float64), a NumPy array or
+        -- ``on_device`` -- a tensor on the env's device, in which case the call only enqueues and an invalid row surfaces at the next
+        synchronising call."""
+        eng = self._engine
+        fn = eng.action_sample_weighted if weighted else eng.action_sample_masked
+
+        def draw(*args):
+            try:
+                fn(*args)
+            except _native.NativeError as e:
+                if e.code == -1:  # MI_ERR_INVALID_ARGUMENT: an invalid row, here or in an earlier enqueued batch (the reference asserts)
+                    raise AssertionError(e.message) from e
+                raise
+
+        self._bind_stream()
+        if on_device:
+            t = self._torch
+            rows = rows.contiguous()
+            out = t.empty((self.num_envs,), dtype=t.int64, device=self._tdev)
+            draw(rows.data_ptr(), out.data_ptr(), _native.MI_DEVICE)
+            return out if self.sample_output == "torch" else out.cpu().numpy()
+        out = np.empty((self.num_envs,), dtype=np.int64)
+        draw(rows, out, _native.MI_HOST)
+        return self._as_sample(out)
+
     # -- fused rollouts ---------------------------------------------------------------------------------
     def rollout(self, num_steps: int, actions=None, *, return_actions: bool = True, infos: bool = False):
         """``num_steps`` consecutive ``step()`` calls in ONE kernel launch; trajectories are time-major tensors in HBM.

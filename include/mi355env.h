@@ -25,6 +25,8 @@
 extern "C" {
 #endif
 
+/* Entry points that were only ADDED since (mi_action_sample_masked and its three companions) leave the number where it is: nothing an ABI 10
+ * caller uses changed, and a caller that needs them finds out by looking the symbol up. */
 #define MI355ENV_ABI_VERSION 10
 
 typedef enum mi_status {
@@ -349,6 +351,33 @@ int mi_rollout_infos(mi_vecenv *env, int T, const mi_rollout_io *io, const mi_ro
 int mi_action_sample(mi_vecenv *env, int T, void *out, int loc);
 int mi_action_get(mi_vecenv *env, uint64_t pcg[4]);
 int mi_action_skip(mi_vecenv *env, int64_t draws);
+/* `action_space.sample(mask=...)` / `sample(probability=...)` of the batched Discrete space (added to ABI 10; spaces/multi_discrete.py:180-249 _apply_mask
+ * over MultiDiscrete([A] * N): ONE generator, rows visited in index order).  Discrete kinds only (act_dim == 1, MI_I64: CARTPOLE, ACROBOT,
+ * MOUNTAIN_CAR, TABULAR, BLACKJACK; others: MI_ERR_UNSUPPORTED); A = the number of actions.  Both continue the ONE action stream of
+ * mi_action_sample / mi_step(actions == NULL) / mi_rollout and leave its position on the device with the per-lane states valid for it.
+ *   mi_action_sample_masked:   mask[N][A] int8 of 0 / 1, A <= 64.  valid = the indices holding 1, k = their number: k == 0 -> action 0, k == 1 ->
+ *                     valid[0], nothing drawn either way; k >= 2 -> valid[j], j = Generator.choice's bounded integer: Lemire's method on 32-BIT
+ *                     values taken from PCG64's buffered half (the low half of a 64-bit output first, its high half kept for the next 32-bit
+ *                     draw; 64-bit draws neither use nor clear a pending half).  A rejected draw (probability (2^32 mod k) / 2^32) takes one
+ *                     value more.  The batch therefore consumes a data-dependent number of outputs and may leave a half pending.
+ *   mi_action_sample_weighted: prob[N][A] float64, A <= 7 (np.sum is the plain left-to-right sum up to there).  valid = (p > 0) & (p <= 1);
+ *                     cdf = cumsum(p[valid] / sum(p)); cdf /= cdf[-1]; action = valid[searchsorted(cdf, random(), side="right")]: one 64-bit
+ *                     output per row, like the plain sampler.
+ *   out[N] int64.  loc == MI_DEVICE only enqueues on the env's stream: no allocation, no synchronising call, no host-side state that changes
+ *   from call to call; MI_HOST stages the rows and synchronises.
+ *   Invalid rows -- a mask value other than 0 / 1; a probability outside [0, 1] or NaN; !np.isclose(sum(p), 1) (rtol 1e-5, atol 1e-8): the WHOLE
+ *   batch is refused: `out` is not written, position and pending half stay where they were, and the sticky device error word is set --
+ *   MI_HOST returns MI_ERR_INVALID_ARGUMENT at once, MI_DEVICE raises it at the next synchronising call (mi_synchronize, mi_get_stats, the next
+ *   mi_step), the same way as an action outside the space.  A deliberate deviation from the reference, whose assertion fires at the first
+ *   invalid row and leaves its generator mid-batch -- like the whole-batch refusal of MI_CFG_SHARED_RNG.
+ *   MI355ENV_MASKED_FORCE_REPAIR=1 (read at mi_create; tests): every masked batch goes through the stage that otherwise only recomputes the rows
+ *   behind a rejected draw.  Results are identical.
+ *   mi_action_get_buffered / mi_action_set_buffered: the pending half as NumPy names it (bit_generator.state "has_uint32" / "uinteger").  get
+ *   goes with mi_action_get and synchronises like it; set follows mi_action_seed, which clears the half. */
+int mi_action_sample_masked(mi_vecenv *env, const int8_t *mask, void *out, int loc);
+int mi_action_sample_weighted(mi_vecenv *env, const double *prob, void *out, int loc);
+int mi_action_get_buffered(mi_vecenv *env, uint32_t *has_uint32, uint32_t *uinteger);
+int mi_action_set_buffered(mi_vecenv *env, uint32_t has_uint32, uint32_t uinteger);
 
 /* Bookkeeping ------------------------------------------------------------------------------------------ */
 int mi_get_stats(mi_vecenv *env, mi_stats *out);     /* synchronises */
