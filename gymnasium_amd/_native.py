@@ -51,6 +51,9 @@ HOST_SYMBOLS += ["action_sample_masked", "action_sample_weighted", "action_get_b
 WRAPPER_SYMBOLS = ["rms_create", "rms_destroy", "rms_get", "rms_set", "normalize_observation", "normalize_reward", "clip_reward", "set_step_epilogue"]
 # The normalisations over a whole trajectory (ABI 9): what the wrappers' rollout() runs over the output of mi_rollout.
 WRAPPER_SYMBOLS += ["wrapper_steps_workspace", "normalize_observation_steps", "normalize_reward_steps"]
+# ClipAction / RescaleAction over an action block on the device (csrc/action_wrappers.hip; added to ABI 10, which it leaves as it is).
+WRAPPER_SYMBOLS += ["transform_actions"]
+TRANSFORM_CLIP, TRANSFORM_AFFINE_INVERSE, TRANSFORM_MAX_ACT_DIM = 0, 1, 32  # MI_TRANSFORM_*
 
 
 class MiConfig(C.Structure):
@@ -160,6 +163,7 @@ class NativeLib:
             self.wrapper_steps_workspace = f("wrapper_steps_workspace", [i32, i32, i32], C.c_int64)
             self.normalize_observation_steps = f("normalize_observation_steps", [vp, vp, vp, i32, i32, i32, dbl, i32, vp, vp, C.c_int64], i32)
             self.normalize_reward_steps = f("normalize_reward_steps", [vp, vp, vp, vp, vp, vp, vp, i32, i32, dbl, dbl, i32, i32, vp, vp, C.c_int64], i32)
+            self.transform_actions = f("transform_actions", [i32, vp, vp, i32, vp, i32, C.c_int64, i32, i32, vp, vp], i32)
             self.step_async = f("step_async", [vp, C.POINTER(MiStepIO)], i32)
             self.step_wait = f("step_wait", [vp], i32)
             self.host_buffers = f("host_buffers", [vp, C.POINTER(MiStepIO)], i32)

@@ -23,6 +23,8 @@ SOURCES = {  # translation unit -> the headers it depends on
                     "action_mask_internal.h", os.path.join("..", "..", "include", "mi355env.h")],
     # sample(mask=...) / sample(probability=...) on the action stream: kernels of their own behind action_mask_internal.h
     "action_mask.hip": ["action_mask_internal.h", "pcg64_dev.h"],
+    # ClipAction / RescaleAction over an action block in HBM (mi_transform_actions): one elementwise kernel, default flag set
+    "action_wrappers.hip": [os.path.join("..", "..", "include", "mi355env.h")],
 }
 OUT = os.path.join(HERE, "libmi355env.so")
 ARCH = "gfx950"

@@ -25,6 +25,10 @@ of ``HipVectorEnv.rollout``, and leaves its statistics, accumulators and previou
 trajectory the wrapper below returned and runs its pass over all T steps at once (mi_normalize_observation_steps, mi_normalize_reward_steps,
 mi_clip_reward over T * N elements) -- a fixed number of launches, on the handles ``step()`` uses, so ``step()``, ``rollout()`` and ``reset()``
 interleave like one long sequence of steps.  The scoping rule holds by construction: ``w.rollout`` applies the wrappers up to ``w``.
+
+The ACTION wrappers (ClipAction, RescaleAction, TransformAction; gymnasium/wrappers/vector/vectorize_action.py) change what goes INTO the step:
+device tensors are transformed by mi_transform_actions (csrc/action_wrappers.hip) in one launch per ``step()`` / per ``rollout()`` block, NumPy
+batches by one NumPy expression on the host; both give the reference's row-by-row result bit for bit.  They are transparent to the fused unit.
 """
 from __future__ import annotations
 
@@ -499,3 +503,253 @@ class ClipReward(VectorWrapper):
                                               C.c_void_p(r.data_ptr())))
         out["rewards"] = r
         return out
+
+
+# -- action wrappers --------------------------------------------------------------------------------------------------------------------------
+class VectorActionWrapper(VectorWrapper):
+    """gymnasium.vector.VectorActionWrapper (vector_env.py:520-552): ``step(a)`` is ``env.step(self.actions(a))``.  Observations and rewards pass
+    through unchanged, so a fused NormalizeObservation / NormalizeReward / ClipReward unit may extend across it.  ``rollout`` and
+    ``capture_steps`` apply the same transform; everything else forwards, as in the reference."""
+
+    _transparent = True
+
+    def actions(self, actions):
+        raise NotImplementedError
+
+    def step(self, actions):
+        return self.env.step(self.actions(actions))
+
+    def _actions_of_steps(self, block, steps):
+        """``actions()`` of every step of a ``[T, N, ...]`` block, stacked."""
+        torch = _torch()
+        rows = [self.actions(block[t]) for t in range(steps)]
+        return torch.stack(rows) if isinstance(rows[0], torch.Tensor) else np.stack(rows)
+
+    def rollout(self, num_steps, actions=None, **kwargs):
+        """T x ``step()`` through this wrapper.  ``actions`` (``[T, N, A]``) are transformed in one pass and handed to the wrapped ``rollout``;
+        with ``actions=None`` the T batches are ``self.action_space.sample()`` -- host draws from the WRAPPER's space, stacked and uploaded -- so
+        the result equals ``[w.step(w.action_space.sample()) for _ in range(T)]``.  ``"actions"`` of the returned dict holds the batches as this
+        wrapper received or drew them (a device tensor, untransformed)."""
+        torch = _torch()
+        steps = int(num_steps)
+        if steps < 1:
+            return self.env.rollout(num_steps, actions, **kwargs)
+        if actions is None:
+            draws = [self.action_space.sample() for _ in range(steps)]
+            actions = torch.stack(draws) if isinstance(draws[0], torch.Tensor) else np.stack(draws)
+        sent = self._actions_of_steps(actions, steps)
+        out = dict(self.env.rollout(num_steps, sent if isinstance(sent, torch.Tensor) else torch.from_numpy(sent), **kwargs))
+        if "actions" in out:
+            out["actions"] = (actions if isinstance(actions, torch.Tensor) else torch.from_numpy(np.asarray(actions))).to(out["obs"].device)
+        return out
+
+    def _before_capture(self):
+        """Whatever must have run once before a graph capture opens (a capture must not load a kernel)."""
+
+    def capture_steps(self, actions=None, steps: int = 1, policy=None):
+        """HipVectorEnv.capture_steps with this wrapper's transform captured between the policy and the step: ``actions`` (a device tensor read at
+        replay time) or a callable ``policy``.  ``policy="random"`` is refused: the wrapper's space is sampled on the host."""
+        if isinstance(policy, str):
+            raise error.Error(f"capture_steps(policy={policy!r}) through {type(self).__name__}: the wrapper's action space is not sampled on the device; "
+                              "capture a callable policy, or the wrapped env's own steps")
+        if (actions is None) == (policy is None):
+            raise ValueError("capture_steps() takes either `actions` (a device tensor read at replay time) or `policy` (a callable)")
+        if actions is not None and not (hasattr(actions, "is_cuda") and actions.is_cuda):
+            raise ValueError("the captured steps read `actions` at replay time: pass a tensor on the env's device")
+        self._before_capture()
+        inner = (lambda obs: self.actions(actions)) if policy is None else (lambda obs: self.actions(policy(obs)))
+        return self.env.capture_steps(steps=steps, policy=inner)
+
+
+class TransformAction(VectorActionWrapper):
+    """vectorize_action.py:30-110: ``func`` is applied to the batch as given -- a NumPy array or a device tensor goes in, the same kind must come
+    out (a ``func`` of operators and ``torch`` / NumPy ufuncs serves both)."""
+
+    def __init__(self, env, func, action_space=None, single_action_space=None):
+        super().__init__(env)
+        if action_space is None:
+            if single_action_space is not None:
+                self.single_action_space = single_action_space
+                self.action_space = batch_space(single_action_space, self.num_envs)
+        else:
+            self.action_space = action_space
+            if single_action_space is not None:
+                self.single_action_space = single_action_space
+        if self.action_space != batch_space(self.single_action_space, self.num_envs):
+            from ..gym_api import logger
+
+            logger.warn(f"For {env}, the action space and the batched single action space don't match as expected, action_space={env.action_space}, "
+                        f"batched single_action_space={batch_space(self.single_action_space, self.num_envs)}")
+        self.func = func
+
+    def actions(self, actions):
+        return self.func(actions)
+
+
+def _rescale_box(box, new_min, new_max):
+    """wrappers/utils.py:160-266 ``rescale_box``: (the rescaled Box, gradient, intercept), the two arrays in the box's dtype.  Every expression is
+    the reference's own NumPy expression in its dtype -- the bound difference in np.float128 where the platform has it -- because the float32
+    rounding of ``gradient`` and ``intercept`` is what the device then computes with."""
+    if not isinstance(box, spaces.Box):
+        raise TypeError(f"Expected box to be a Box space, got {type(box)}")
+    bounds = []
+    for name, b in (("new_min", new_min), ("new_max", new_max)):
+        if not isinstance(b, np.ndarray):
+            if not (np.issubdtype(type(b), np.integer) or np.issubdtype(type(b), np.floating)):
+                raise TypeError(f"Expected {name} to be an integer, float, or numpy array, got {type(b)}")
+            b = np.full(box.shape, b)
+        if b.shape != box.shape:
+            raise ValueError(f"Expected {name}.shape to be {box.shape}, got {b.shape}")
+        bounds.append(b)
+    new_min, new_max = bounds
+    for new, old in ((new_min, box.low), (new_max, box.high)):
+        if not np.all((new == old)[np.isinf(new) | np.isinf(old)]):
+            raise ValueError("For unbounded components, the target bounds must match the original infinity bounds.")
+    if not np.all(new_min <= new_max):
+        raise ValueError(f"Expected new_min to be less than or equal to new_max, got {new_min} and {new_max}")
+    if not np.all(box.low <= box.high):
+        raise ValueError(f"Expected box.low to be less than or equal to box.high, got {box.low} and {box.high}")
+    wide = getattr(np, "float128", np.float64)
+    min_finite, max_finite = np.isfinite(new_min), np.isfinite(new_max)
+    both = min_finite & max_finite
+    gradient = np.ones_like(new_min, dtype=box.dtype)
+    gradient[both] = (new_max[both] - new_min[both]) / (np.array(box.high[both], dtype=wide) - np.array(box.low[both], dtype=wide))
+    intercept = np.zeros_like(new_min, dtype=box.dtype)
+    intercept[max_finite] = new_max[max_finite] - box.high[max_finite]
+    intercept[min_finite] = gradient[min_finite] * -box.low[min_finite] + new_min[min_finite]  # (where both are finite this one stands)
+    return spaces.Box(low=new_min, high=new_max, shape=box.shape, dtype=box.dtype), gradient, intercept
+
+
+class _BoxTransformAction(VectorActionWrapper):
+    """What ClipAction and RescaleAction share (vectorize_action.py:114-213, VectorizeTransformAction): the reference applies the scalar wrapper's
+    ``func`` row by row and stacks the rows into a float32 ``(N, A)`` array -- or, when the wrapper's batched space equals the env's
+    (``same_out``), into the caller's own array, whose dtype the result then keeps.  Here the rows are transformed at once, in the dtype NumPy's
+    promotion gives a row against the float32 parameters (float32 for float32 / float16 rows, float64 for float64 and integer rows), and
+    rounded once to the dtype they are stored in:
+
+    * NumPy arrays, lists, host tensors: one vectorised NumPy expression; the env receives a NumPy batch.
+    * device tensors: mi_transform_actions (csrc/action_wrappers.hip), one launch over the N * A -- in ``rollout`` the T * N * A -- elements.
+
+    DEVIATION from the reference: the caller's array or tensor is never modified (``same_out`` writes into it there); the result is always a
+    new one."""
+
+    _kind = None
+
+    def _setup(self, single_space, p0, p1):
+        self.single_action_space = single_space
+        self.action_space = batch_space(single_space, self.num_envs)
+        self.same_out = self.action_space == self.env.action_space
+        self._shape = tuple(self.env.single_action_space.shape)
+        self._p0, self._p1 = p0, p1
+        self._q0 = np.ascontiguousarray(p0, dtype=np.float64).reshape(-1)
+        self._q1 = np.ascontiguousarray(p1, dtype=np.float64).reshape(-1)
+
+    def _formula(self, a):
+        raise NotImplementedError
+
+    def actions(self, actions):
+        return self._apply(actions, (self.num_envs,))
+
+    def _actions_of_steps(self, block, steps):
+        return self._apply(block, (steps, self.num_envs))
+
+    def _apply(self, actions, lead):
+        if hasattr(actions, "data_ptr"):
+            if actions.is_cuda:
+                return self._apply_device(actions, lead)
+            actions = actions.numpy()
+        if self.same_out and not isinstance(actions, np.ndarray):
+            raise TypeError(f"{type(self).__name__}: its action space equals the env's, so the result keeps the dtype of the caller's array: pass a NumPy "
+                            f"array, not {type(actions)}")
+        if len(lead) == 1 and isinstance(actions, (list, tuple)) and len(actions) > 0 and all(type(x) in (float, int) for x in actions):
+            a = np.asarray(actions, dtype=np.float32)  # a row that is one Python scalar is weak against the float32 parameters (NEP 50)
+        else:
+            a = np.asarray(actions)
+        if a.ndim == 0:
+            raise TypeError(f"Unable to iterate over the actions of the batched space, got {actions!r}")
+        if a.ndim == len(lead):
+            a = a[..., None]
+        res = self._formula(a)
+        if res.shape != lead + self._shape:
+            raise ValueError(f"actions must give rows of shape {self._shape} for {lead}, got an array of shape {np.shape(actions)}")
+        out_dtype = a.dtype if self.same_out else np.dtype(np.float32)
+        if not np.can_cast(res.dtype, out_dtype, "same_kind"):
+            raise TypeError(f"Cannot cast the transformed actions from {res.dtype} to {out_dtype} according to the rule 'same_kind'")
+        return res.astype(out_dtype)
+
+    def _apply_device(self, x, lead):
+        torch = _torch()
+        dim = int(np.prod(self._shape))
+        if dim > _native.TRANSFORM_MAX_ACT_DIM:
+            raise error.Error(f"{type(self).__name__} on device tensors takes up to {_native.TRANSFORM_MAX_ACT_DIM} action dimensions, the env has {dim}")
+        kept = x.dtype
+        if self.same_out and not kept.is_floating_point:
+            raise TypeError(f"Cannot cast the transformed actions to {kept} according to the rule 'same_kind'")
+        compute = torch.float64 if kept in (torch.float64, torch.int32, torch.int64) else torch.float32
+        if x.dim() == len(lead):
+            x = x.unsqueeze(-1)
+        want = lead + self._shape
+        if tuple(x.shape) != want:
+            try:
+                ok = tuple(torch.broadcast_shapes(tuple(x.shape), self._shape)) == want
+            except RuntimeError:
+                ok = False
+            if not ok:
+                raise ValueError(f"actions must give rows of shape {self._shape} for {lead}, got a tensor of shape {tuple(x.shape)}")
+            x = x.expand(want)
+        x = x.to(compute).contiguous()
+        out = torch.empty(want, dtype=compute if self.same_out else torch.float32, device=x.device)
+        lib = _native.load_library()
+        code = {torch.float32: _native.MI_F32, torch.float64: _native.MI_F64}
+        lib.check(lib.transform_actions(x.device.index, C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream), C.c_void_p(x.data_ptr()),
+                                        code[x.dtype], C.c_void_p(out.data_ptr()), code[out.dtype], x.numel(), dim, self._kind,
+                                        self._q0.ctypes.data, self._q1.ctypes.data))
+        return out.to(kept) if self.same_out and out.dtype != kept else out
+
+    def _before_capture(self):
+        torch = _torch()
+        for dtype in (torch.float32, torch.float64):
+            self._apply_device(torch.zeros((1,) + self._shape, dtype=dtype, device=f"cuda:{self._dev()}"), (1,))
+
+
+class ClipAction(_BoxTransformAction):
+    """vectorize_action.py:216-240 (transform_action.py:79-127): ``np.clip(action, low, high)`` with the env's bounds; the wrapper's own space is
+    unbounded.  NaN stays NaN; a float64 batch is clipped in float64 and then rounded to float32."""
+
+    _kind = _native.TRANSFORM_CLIP
+
+    def __init__(self, env):
+        super().__init__(env)
+        box = self.env.single_action_space
+        if not isinstance(box, spaces.Box):
+            raise TypeError(f"ClipAction requires a Box action space, got {type(box)}")
+        self._setup(spaces.Box(-np.inf, np.inf, shape=box.shape, dtype=box.dtype), box.low, box.high)
+
+    def _formula(self, a):
+        # NOT np.clip over the batch: with the bounds broadcast NumPy takes its constant-bounds loop, `x < lo ? lo : x`, which keeps the -0.0 that
+        # the loop a single row goes through, `x > lo ? x : lo`, turns into the bound +0.0.  The row loop is what the reference runs.
+        c = np.result_type(a.dtype, self._p0.dtype)
+        x, lo, hi = a.astype(c), self._p0.astype(c), self._p1.astype(c)
+        t = np.where((x > lo) | np.isnan(x), x, lo)
+        return np.where((t < hi) | np.isnan(t), t, hi)
+
+
+class RescaleAction(_BoxTransformAction):
+    """vectorize_action.py:243-296 (transform_action.py:130-198): the wrapper's space is ``[min_action, max_action]``, the env receives
+    ``(action - intercept) / gradient``.  ``gradient`` and ``intercept`` are rescale_box's float32 arrays, computed on the host."""
+
+    _kind = _native.TRANSFORM_AFFINE_INVERSE
+
+    def __init__(self, env, min_action, max_action):
+        super().__init__(env)
+        box = self.env.single_action_space
+        if not isinstance(box, spaces.Box):
+            raise TypeError(f"RescaleAction requires a Box action space, got {type(box)}")
+        space, self.gradient, self.intercept = _rescale_box(box, min_action, max_action)
+        if np.any(space.low == space.high):
+            raise error.InvalidBound(f"Min action ({min_action}) must be strictly smaller than max action ({max_action}), the rescaling has no inverse "
+                                     "where they are equal")
+        self._setup(space, self.intercept, self.gradient)
+
+    def _formula(self, a):
+        return (a - self.intercept) / self.gradient

@@ -480,6 +480,23 @@ int mi_normalize_reward_steps(mi_running_stats *return_rms, void *hip_stream, fl
                               const uint8_t *terminated, const uint8_t *truncated, int T, int num_envs, double gamma, double epsilon,
                               int same_step, int update, double *out, void *workspace, int64_t workspace_bytes);
 
+/*
+ * The vector action wrappers (gymnasium/wrappers/vector/vectorize_action.py:183-300) over an action block in device memory, element by element:
+ *   MI_TRANSFORM_CLIP            ClipAction:    np.clip(action, p0, p1)   p0 = low, p1 = high of the wrapped Box (transform_action.py:118-120)
+ *   MI_TRANSFORM_AFFINE_INVERSE  RescaleAction: (action - p0) / p1        p0 = intercept, p1 = gradient of rescale_box (wrappers/utils.py:263-264)
+ * in / out: [elements] device pointers of in_dtype / out_dtype (MI_F32 -> MI_F32, MI_F64 -> MI_F32, MI_F64 -> MI_F64), rows of act_dim entries
+ * (elements = T * num_envs * act_dim); element i uses entry i % act_dim of p0 / p1.  The arithmetic runs in in_dtype -- the reference's rows
+ * promote against float32 bounds to their own dtype -- and is rounded once to out_dtype, so p0 / p1 must hold float32 values.  NaN propagates
+ * as in np.clip.  p0 / p1: HOST pointers of act_dim <= MI_TRANSFORM_MAX_ACT_DIM entries, copied into the kernel's arguments: the call only
+ * enqueues on hip_stream -- no allocation, no synchronisation, no state -- and may be captured into a graph.  out must not overlap in.
+ * (Added to ABI 10, which it leaves as it is.)
+ */
+#define MI_TRANSFORM_CLIP 0
+#define MI_TRANSFORM_AFFINE_INVERSE 1
+#define MI_TRANSFORM_MAX_ACT_DIM 32
+int mi_transform_actions(int device, void *hip_stream, const void *in, int in_dtype, void *out, int out_dtype, int64_t elements, int act_dim,
+                         int kind, const double *p0, const double *p1);
+
 /* The same three wrappers as the OUTPUT STAGE of the step kernel (classic-control kinds): mi_step / mi_step_async then return the wrapped
  * observations and rewards in place of the raw ones -- one extra launch per step (the normalisations need the statistics of the WHOLE batch,
  * stateful_observation.py:146-152) instead of the ten of the stand-alone passes, and no staging for host callers: the values are rewritten
