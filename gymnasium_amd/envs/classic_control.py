@@ -139,6 +139,7 @@ class CartPoleVectorEnv(_ClassicControlVectorEnv):
         date again (_shared_pull) -- the price is one synchronisation per call, paid only by callers that touch ``np_random``."""
         gen = VectorEnvBase.np_random.fget(self)
         if getattr(self, "_shared_rng", False) and getattr(self, "_seeded", False) and getattr(self, "_engine", None) is not None:
+            self._shared_push()  # (draws the caller took from the object since it was handed out last: without this the pull would undo them)
             self._shared_pull(gen)
             self._shared_handed_out = True
         return gen

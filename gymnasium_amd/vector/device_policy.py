@@ -10,9 +10,15 @@ sub-environments costs more host time than the step costs the GPU.  The engine r
   ``output="torch"`` the batch is a device tensor and the loop above enqueues nothing but step kernels, with ``output="numpy"`` it is a
   NumPy view of one pinned device-to-host copy per ``K`` steps.  A fresh block is allocated per refill, so a returned batch is never
   overwritten, exactly like the reference's fresh arrays.
-* ``np_random`` stays the space's NumPy generator: reading it first returns the draws that were made ahead but not handed out
-  (``mi_action_skip``) and moves the generator to the stream's position (``mi_action_get``), so mixing ``sample()``, ``np_random.random()``,
-  ``env.rollout()`` and ``env.step(None)`` consumes ONE stream in call order, as in the reference.  ``seed()`` behaves as always.
+* ``np_random`` is the space's NumPy generator, brought up to date WHEN THE PROPERTY IS READ: reading it first returns the draws that were made
+  ahead but not handed out (``mi_action_skip``) and moves the generator to the stream's position (``mi_action_get``), so mixing ``sample()``,
+  ``np_random.random()``, ``env.rollout()``, ``env.step(None)`` and replays of ``env.capture_steps(policy="random")`` consumes ONE stream in
+  call order, as in the reference.  ``seed()`` behaves as always.  Not covered: a generator object the caller KEPT from an earlier read
+  (``g = space.np_random; space.sample(); g.random()``) is not followed -- read the property again after the space has been used.
+* a replayed graph of the random policy advances the stream on the device without the engine seeing it (``GraphedSteps._before_replay`` /
+  ``_after_replay``): the space hands the position over first (``hip_hold_on_device``), counts what every replay draws (``hip_note_launch``)
+  and remembers that it holds the account (``_hip_held``), so that back-to-back replays cost nothing on the host; every other consumer first
+  hands the sum to the engine (``_hip_settle``: ``mi_action_skip``) and so continues after what the replays drew.
 * ``sample(mask=...)`` / ``sample(probability=...)`` of the batched Discrete space are drawn by the engine too (``mi_action_sample_masked`` /
   ``mi_action_sample_weighted``: the reference's ``_apply_mask`` over all rows, spaces/multi_discrete.py:180-249, from the same stream).  Besides the
   reference's tuple of ``N`` rows they take ONE ``(N, A)`` array or torch tensor (``int8`` / ``float64``) -- what ``info["action_mask"]`` of a
@@ -26,7 +32,8 @@ sub-environments costs more host time than the step costs the GPU.  The engine r
   the reference's NumPy path.
 
 Bit-equality with the NumPy sampler is pinned by tests/test_device_policy.py (host) and tests/test_gpu_device_policy.py (GPU); the masked and
-weighted draws by tests/test_masked_sampling.py and tests/test_gpu_masked_sampling.py.
+weighted draws by tests/test_masked_sampling.py and tests/test_gpu_masked_sampling.py; interleavings of every consumer with graph replays by
+tests/test_stream_interleaving.py and tests/test_gpu_stream_interleaving.py.
 """
 from __future__ import annotations
 
@@ -97,7 +104,9 @@ class _DevicePolicyMixin:
         _, eng = self._hip_engine()
         if eng is None:  # the env is gone: whatever the generator holds is all there is
             self._hip_ring, self._hip_pos = (), 0
+            self._hip_held, self._hip_launched = False, 0
             return
+        self._hip_settle(eng)
         self._hip_drop_ahead(eng)
         # the pending 32-bit half: from the engine where masked draws can change it, else the one handed over (64-bit draws leave it alone)
         half = eng.action_get_buffered() if hasattr(eng.lib, "action_get_buffered") else self.__dict__.get("_hip_half", (0, 0))
@@ -108,7 +117,9 @@ class _DevicePolicyMixin:
         if self.__dict__.get("_hip_on_engine", False):
             return
         gen = super().np_random
-        eng.action_seed(_native.pcg_words(gen))
+        words = _native.pcg_words(gen)
+        eng.action_seed(words)
+        self._hip_inc = (int(words[2]), int(words[3]))  # (a captured graph holds the increment's jump: GraphedSteps compares)
         self._hip_half = _native.pcg_buffered(gen)
         if self._hip_half != (0, 0) and hasattr(eng.lib, "action_set_buffered"):
             eng.action_set_buffered(*self._hip_half)
@@ -119,9 +130,42 @@ class _DevicePolicyMixin:
         Returns the engine, or None when the space is detached."""
         _, eng = self._hip_engine()
         if eng is not None:
+            self._hip_settle(eng)
             self._hip_to_engine(eng)
             self._hip_drop_ahead(eng)
         return eng
+
+    # -- launches the engine does not see (GraphedSteps.replay) --------------------------------------------
+    def _hip_settle(self, eng):
+        """Tell the engine what the launches it did not see have drawn (``hip_note_launch``): its position moves past them
+        (``mi_action_skip``, which also marks the per-lane states for re-initialisation).  No-op when there were none."""
+        if self.__dict__.get("_hip_held", False):
+            self._hip_held = False
+            drawn, self._hip_launched = self.__dict__.get("_hip_launched", 0), 0
+            if drawn:
+                eng.action_skip(drawn)
+
+    def hip_hold_on_device(self):
+        """For a consumer whose launches the engine does not see -- the kernels of a replayed graph read and advance the per-lane states of the
+        stream on the device: besides ``hip_use_stream()``, the engine's own copy becomes the position (``mi_action_get``: the capture, an eager
+        ``step(None)`` or a masked draw may have left it with the lanes) and the lanes are (re-)initialised for it where a seed, a skip or a
+        rollout left them behind (``mi_action_sample`` with T = 0, on the env's current stream).  From here on the space keeps the account:
+        every such launch is noted (``hip_note_launch``), and the next consumer of any other kind first hands the sum to the engine
+        (``_hip_settle``), so ``np_random``, ``sample()``, ``rollout()`` and ``step(None)`` continue after what the launches drew.  While
+        ``_hip_held`` is set a further launch needs nothing from the host.  The ENGINE is not told: while ``_hip_held`` is set its own copy of
+        the position is the one before the launches, so raw engine calls that read or move the stream (``env._engine.action_get()`` /
+        ``action_skip()`` / ``rollout()`` / ``step_bound(None, ...)``) must not be made then -- go through the space or the env, which settle
+        first.  Returns the engine, or None when the space is detached."""
+        eng = self.hip_use_stream()
+        if eng is not None:
+            eng.action_get()
+            eng.action_sample(0, None, _native.MI_DEVICE)
+            self._hip_held, self._hip_launched = True, 0
+        return eng
+
+    def hip_note_launch(self, batches: int):
+        """A launch the engine did not see has drawn ``batches`` batches from the lanes (no engine call: an addition on the host)."""
+        self._hip_launched = self.__dict__.get("_hip_launched", 0) + int(batches) * self._hip_batch_draws
 
     # -- the Space interface ------------------------------------------------------------------------------------
     @property
@@ -130,7 +174,8 @@ class _DevicePolicyMixin:
         return super().np_random
 
     def seed(self, seed=None):
-        self._hip_on_engine = False  # (whatever was drawn ahead belongs to the old stream)
+        self._hip_on_engine = self._hip_held = False  # (whatever was drawn ahead, or by launches since, belongs to the old stream)
+        self._hip_launched = 0
         self._hip_ring, self._hip_pos = (), 0
         return super().seed(seed)
 
@@ -149,6 +194,7 @@ class _DevicePolicyMixin:
         pos = self.__dict__.get("_hip_pos", 0)
         ring = self.__dict__.get("_hip_ring", ())
         if pos >= len(ring):
+            self._hip_settle(eng)
             self._hip_to_engine(eng)
             ring = self._hip_ring = env._draw_action_batches(self._hip_ring_steps)
             pos = 0
@@ -227,7 +273,8 @@ def attach(space, env, act_dim: int):
     new.__dict__.update(space.__dict__)
     space = new
     space._hip_env = weakref.ref(env)
-    space._hip_on_engine = False
+    space._hip_on_engine = space._hip_held = False
+    space._hip_launched = 0
     space._hip_ring, space._hip_pos = (), 0
     space._hip_batch_draws = env.num_envs * act_dim
     bytes_per_batch = env.num_envs * act_dim * (8 if cls is HipMultiDiscrete else 4)

@@ -1137,10 +1137,12 @@ class GraphedSteps:
 
     ``results``: the (obs, rewards, terminations, truncations, infos) tuple of every captured step -- static device tensors that each
     ``replay()`` overwrites (with ``copy=False`` the observation / reward / flag tensors of all steps are the env's own buffers, i.e. they hold
-    the LAST step's values; with ``copy=True`` every step has its own)."""
+    the LAST step's values; with ``copy=True`` every step has its own).  HAZARD: a graph of ``policy="random"`` captures its steps again in the
+    first ``replay()`` after an ``action_space.seed()`` that changed the generator's increment (_before_replay); ``results`` is then a NEW list of
+    new tensors, and tuples kept from earlier replays are written by no launch any more -- silently.  Use what ``replay()`` returns, or read
+    ``graph.results`` afresh after every replay, wherever the action space may be re-seeded."""
 
     def __init__(self, env: "HipVectorEnv", actions, steps: int, policy):
-        t = env._torch
         if steps < 1:
             raise ValueError("steps must be >= 1")
         if actions is not None:
@@ -1148,18 +1150,30 @@ class GraphedSteps:
             if keep is not actions:
                 raise ValueError("the captured steps read `actions` in place at replay time: pass a contiguous tensor on the env's device with "
                                  "the action space's dtype (int64, or float32 / float64 rows for Box spaces)")
-        self.env, self.steps, self.actions = env, steps, actions
+        self.env, self.steps, self.actions, self.policy = env, steps, actions, policy
         self.attr_mask = env._env_attr_mask  # which kernels the graph holds (per-lane attributes: set_attr)
+        self._capture()
+
+    def _prepare_capture(self):
+        """What must hold before the capture opens.  policy="random": the action stream's position is on the engine with nothing drawn ahead, its
+        per-lane states exist on the device (a capture cannot create them) and hold the position; the captured kernels carry the jump of the
+        generator's increment, which is remembered here."""
+        if self.policy == "random":
+            self.env._bind_stream()
+            self.env.action_space.hip_hold_on_device()
+            self._inc = self.env.action_space._hip_inc
+
+    def _capture(self):
+        env, actions, policy = self.env, self.actions, self.policy
+        t = env._torch
         self.graph = t.cuda.CUDAGraph()
         self.results = []
-        if policy == "random":  # the per-lane states of the action stream must exist before the capture opens (mi_action_sample with T = 0)
-            env._bind_stream()
-            env.action_space.hip_use_stream().action_sample(0, None, _native.MI_DEVICE)
+        self._prepare_capture()
         env.synchronize()
         try:
             with t.cuda.graph(self.graph):
                 obs = env._obs
-                for _ in range(steps):
+                for _ in range(self.steps):
                     out = env.step(actions if policy is None else (None if policy == "random" else policy(obs)))
                     obs = out[0]
                     self.results.append(out)
@@ -1167,9 +1181,14 @@ class GraphedSteps:
             env._stream_bound = None  # (the capture bound the engine to the capture stream)
             env._bind_stream()
 
-    def replay(self):
-        """Run the captured steps (one graph launch on torch's current stream, asynchronous like step() with device tensors); returns the
-        last step's tuple."""
+    def _before_replay(self):
+        """The host's part of a replay before the launch.  A graph of the random policy is one more consumer of the action stream
+        (vector/device_policy.py), and one the engine does not see: its kernels read and advance the per-lane states on the device.  So, unless
+        the last consumer was such a replay -- then NOTHING is left to do, no engine call and no synchronisation: back-to-back replays stay
+        launch-bound --, the space hands the stream over first (``hip_hold_on_device``: the NumPy generator's draws and its pending 32-bit half
+        taken over, batches drawn ahead given back, the lanes re-initialised on the replay's stream where ``action_space.seed()``, a skip or a
+        rollout left them behind; from then on the space keeps the account of what the launches draw).  The captured kernels carry the jump of the generator's
+        INCREMENT: after a seed() that changed it the steps are captured again (``results`` are then new tensors; ``replay()`` returns them)."""
         env = self.env
         env._check_open()
         env._check_not_pending("replay")
@@ -1177,8 +1196,28 @@ class GraphedSteps:
             raise error.Error("set_attr() has made the env read per-sub-environment attributes since this graph was captured; its kernels do not "
                               "read them: capture the steps again")
         env._bind_stream()  # statistics() / synchronize() wait on the engine's stream: keep it the one the replay runs on
-        self.graph.replay()
+        if self.policy == "random":
+            space = env.action_space
+            if not space.__dict__.get("_hip_held", False):
+                space.hip_use_stream()  # (the engine is seeded from the generator where a seed() is pending: `_hip_inc` is current after it)
+            if space._hip_inc != self._inc:  # on EVERY replay (a tuple compare): another graph of this env may have taken the stream over since the seed()
+                self._capture()
+            if not space.__dict__.get("_hip_held", False):
+                space.hip_hold_on_device()
+
+    def _after_replay(self):
+        """The host's part of a replay after the launch: the space notes what the launch draws (an addition, no engine call), so that the next
+        consumer of another kind -- ``np_random``, ``sample()``, ``rollout()``, ``step(None)``, ``mi_action_get`` through them -- continues after it."""
+        if self.policy == "random":
+            self.env.action_space.hip_note_launch(self.steps)
         return self.results[-1]
+
+    def replay(self):
+        """Run the captured steps (one graph launch on torch's current stream, asynchronous like step() with device tensors); returns the
+        last step's tuple."""
+        self._before_replay()
+        self.graph.replay()
+        return self._after_replay()
 
 
 def _resolve_device(device) -> int:

@@ -152,3 +152,32 @@ def test_a_draw_from_np_random_against_the_reference_class(oracle_factory):
             assert np.array_equal(r[k], e[k]), (t, k)
     assert np.array_equal(ref.reset()[0], env.reset()[0])
     env.close()
+
+
+def check_two_draws_through_np_random(make_env):
+    """draws through ``env.np_random`` with NO engine call between them.  The getter used to overwrite the host generator with the
+    device's position without first taking over what the caller had drawn: the second draw repeated the first, and neither reached the resets.
+    Known answer: ``default_rng(11)`` drawn like the reference class draws it -- uniform(-0.05, 0.05, (4, n)) per reset (cartpole.py:497)."""
+    n = 4
+    for kept in (False, True):
+        env = make_env(num_envs=n)
+        ref = np.random.default_rng(11)
+        first, _ = env.reset(seed=11)
+        assert np.array_equal(np.asarray(first), ref.uniform(-0.05, 0.05, size=(4, n)).T.astype(np.float32))
+        if kept:  # the same through a reference the caller kept
+            g = env.np_random
+            got = (g.random(), g.random())
+        else:
+            got = (env.np_random.random(), env.np_random.random())
+        want = (ref.random(), ref.random())
+        assert got == want, (kept, got, want)
+        assert got[0] != got[1]
+        nxt, _ = env.reset()  # the draws reached the device: the next reset continues after BOTH
+        assert np.array_equal(np.asarray(nxt), ref.uniform(-0.05, 0.05, size=(4, n)).T.astype(np.float32)), kept
+        assert env.np_random.random() == ref.random()  # ... and the property is up to date after it
+        assert env.np_random.random() == ref.random()
+        env.close()
+
+
+def test_two_draws_through_np_random_without_an_engine_call_between(oracle_factory):
+    check_two_draws_through_np_random(lambda **kw: gymnasium_amd.make_vec("CartPole-v1", rng="shared", _engine_factory=oracle_factory, **kw))

@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 
 import gymnasium_amd
-from test_cartpole_shared_rng import check_seed_sequence_entry_point, check_shared_rng_segments
+from test_cartpole_shared_rng import check_seed_sequence_entry_point, check_shared_rng_segments, check_two_draws_through_np_random
 
 pytestmark = pytest.mark.gpu
 
@@ -16,6 +16,10 @@ def test_numpy_batches_equal_the_reference_vector_env():
 
 def test_seed_sequence_entry_point():
     check_seed_sequence_entry_point(lambda **kw: gymnasium_amd.make_vec("CartPole-v1", rng="shared", device=0, **kw))
+
+
+def test_two_draws_through_np_random_without_an_engine_call_between():
+    check_two_draws_through_np_random(lambda **kw: gymnasium_amd.make_vec("CartPole-v1", rng="shared", device=0, **kw))
 
 
 def test_device_tensors_equal_the_reference_vector_env():
