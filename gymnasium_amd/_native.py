@@ -54,6 +54,10 @@ WRAPPER_SYMBOLS += ["wrapper_steps_workspace", "normalize_observation_steps", "n
 # ClipAction / RescaleAction over an action block on the device (csrc/action_wrappers.hip; added to ABI 10, which it leaves as it is).
 WRAPPER_SYMBOLS += ["transform_actions"]
 TRANSFORM_CLIP, TRANSFORM_AFFINE_INVERSE, TRANSFORM_MAX_ACT_DIM = 0, 1, 32  # MI_TRANSFORM_*
+# RescaleObservation / DtypeObservation / FlattenObservation over an observation block on the device (csrc/observation_wrappers.hip; added to ABI 10 as well).
+WRAPPER_SYMBOLS += ["transform_observations", "one_hot"]
+MI_F16, MI_I32, MI_U8 = 4, 5, 6  # mi_dtype: targets of transform_observations(OBS_CAST) only
+OBS_AFFINE, OBS_CAST, OBS_MAX_DIM, ONE_HOT_MAX_PARTS = 0, 1, 1024, 4  # MI_OBS_*, MI_ONE_HOT_MAX_PARTS
 
 
 class MiConfig(C.Structure):
@@ -164,6 +168,8 @@ class NativeLib:
             self.normalize_observation_steps = f("normalize_observation_steps", [vp, vp, vp, i32, i32, i32, dbl, i32, vp, vp, C.c_int64], i32)
             self.normalize_reward_steps = f("normalize_reward_steps", [vp, vp, vp, vp, vp, vp, vp, i32, i32, dbl, dbl, i32, i32, vp, vp, C.c_int64], i32)
             self.transform_actions = f("transform_actions", [i32, vp, vp, i32, vp, i32, C.c_int64, i32, i32, vp, vp], i32)
+            self.transform_observations = f("transform_observations", [i32, vp, vp, i32, vp, i32, C.c_int64, i32, i32, vp, vp], i32)
+            self.one_hot = f("one_hot", [i32, vp, C.POINTER(vp), i32, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int64, vp], i32)
             self.step_async = f("step_async", [vp, C.POINTER(MiStepIO)], i32)
             self.step_wait = f("step_wait", [vp], i32)
             self.host_buffers = f("host_buffers", [vp, C.POINTER(MiStepIO)], i32)

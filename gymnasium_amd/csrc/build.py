@@ -25,6 +25,8 @@ SOURCES = {  # translation unit -> the headers it depends on
     "action_mask.hip": ["action_mask_internal.h", "pcg64_dev.h"],
     # ClipAction / RescaleAction over an action block in HBM (mi_transform_actions): one elementwise kernel, default flag set
     "action_wrappers.hip": [os.path.join("..", "..", "include", "mi355env.h")],
+    # RescaleObservation / DtypeObservation / FlattenObservation over an observation block in HBM (mi_transform_observations, mi_one_hot): default flag set
+    "observation_wrappers.hip": [os.path.join("..", "..", "include", "mi355env.h")],
 }
 OUT = os.path.join(HERE, "libmi355env.so")
 ARCH = "gfx950"

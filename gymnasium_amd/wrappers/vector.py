@@ -29,6 +29,12 @@ interleave like one long sequence of steps.  The scoping rule holds by construct
 The ACTION wrappers (ClipAction, RescaleAction, TransformAction; gymnasium/wrappers/vector/vectorize_action.py) change what goes INTO the step:
 device tensors are transformed by mi_transform_actions (csrc/action_wrappers.hip) in one launch per ``step()`` / per ``rollout()`` block, NumPy
 batches by one NumPy expression on the host; both give the reference's row-by-row result bit for bit.  They are transparent to the fused unit.
+
+The OBSERVATION and REWARD transforms (RescaleObservation, DtypeObservation, FlattenObservation, TransformObservation, TransformReward;
+gymnasium/wrappers/vector/vectorize_observation.py, vectorize_reward.py) change what comes OUT of the step, statelessly: device tensors go through
+mi_transform_observations / mi_one_hot (csrc/observation_wrappers.hip) in one launch per ``step()`` / ``reset()`` / ``rollout()`` trajectory, NumPy
+batches through one NumPy expression.  They are neither transparent nor fused -- what sits above them sees transformed values -- and refuse
+``capture_steps`` (docs/observation_wrappers.md).
 """
 from __future__ import annotations
 
@@ -753,3 +759,358 @@ class RescaleAction(_BoxTransformAction):
 
     def _formula(self, a):
         return (a - self.intercept) / self.gradient
+
+
+# -- observation and reward transforms --------------------------------------------------------------------------------------------------------
+def _refuse_capture(wrapper, what):
+    raise error.Error(f"capture_steps() through {type(wrapper).__name__} is not supported: the captured steps return the wrapped env's own buffers, so a "
+                      f"replay would hand out the untransformed {what}; capture the wrapped env's steps and apply the transform to what replay() returns")
+
+
+def _stack(rows):
+    torch = _torch()
+    if isinstance(rows[0], tuple):
+        return tuple(_stack([r[k] for r in rows]) for k in range(len(rows[0])))
+    return torch.stack(rows) if isinstance(rows[0], torch.Tensor) else np.stack(rows)
+
+
+class VectorObservationWrapper(VectorWrapper):
+    """gymnasium.vector.VectorObservationWrapper (vector_env.py:520-575): ``reset`` and ``step`` return ``self.observations(obs)`` in place of
+    ``obs``; everything else forwards.  SAME_STEP is refused as in the reference, so ``final_obs`` never needs transforming.  ``rollout`` transforms
+    the trajectory's ``"obs"``; ``capture_steps`` is refused (the captured results would be the untransformed buffers).  Neither transparent nor fused:
+    statistics wrappers stacked above run their stand-alone passes over the transformed observations."""
+
+    def __init__(self, env):
+        super().__init__(env)
+        if "autoreset_mode" not in self.env.metadata:
+            from ..gym_api import logger
+
+            logger.warn(f"Vector environment ({env}) is missing `autoreset_mode` metadata key.")
+        elif self.env.metadata["autoreset_mode"] not in (AutoresetMode.NEXT_STEP, AutoresetMode.DISABLED):
+            raise ValueError(f"Expected autoreset_mode to be NEXT_STEP or DISABLED, got {self.env.metadata['autoreset_mode']}")
+        _close_fusion(self.env)
+
+    def observations(self, observations):
+        raise NotImplementedError
+
+    def reset(self, *, seed=None, options=None):
+        obs, infos = self.env.reset(seed=seed, options=options)
+        return self.observations(obs), infos
+
+    def step(self, actions):
+        obs, rewards, terminations, truncations, infos = self.env.step(actions)
+        return self.observations(obs), rewards, terminations, truncations, infos
+
+    def _observations_of_steps(self, block, steps):
+        """``observations()`` of every step of a ``[T, N, ...]`` block, stacked."""
+        return _stack([self.observations(block[t]) for t in range(steps)])
+
+    def rollout(self, num_steps, actions=None, **kwargs):
+        """T x ``step()`` through this wrapper: the wrapped ``rollout`` with ``"obs"`` transformed; the other keys (``infos=True`` included) pass through."""
+        out = dict(self.env.rollout(num_steps, actions, **kwargs))
+        steps = len(out["obs"][0]) if isinstance(out["obs"], tuple) else int(out["obs"].shape[0])
+        if steps > 0:
+            out["obs"] = self._observations_of_steps(out["obs"], steps)
+        return out
+
+    def capture_steps(self, *args, **kwargs):
+        _refuse_capture(self, "observations")
+
+
+class TransformObservation(VectorObservationWrapper):
+    """vectorize_observation.py:32-111: ``func`` is applied to the batch as given -- a NumPy array or a device tensor goes in, the same kind must come
+    out.  ``rollout`` applies it step by step (a ``func`` may look at the batch's shape)."""
+
+    def __init__(self, env, func, observation_space=None, single_observation_space=None):
+        super().__init__(env)
+        if observation_space is None:
+            if single_observation_space is not None:
+                self.single_observation_space = single_observation_space
+                self.observation_space = batch_space(single_observation_space, self.num_envs)
+        else:
+            self.observation_space = observation_space
+            if single_observation_space is not None:
+                self.single_observation_space = single_observation_space
+        if self.observation_space != batch_space(self.single_observation_space, self.num_envs):
+            from ..gym_api import logger
+
+            logger.warn(f"For {env}, the observation space and the batched single observation space don't match as expected, "
+                        f"observation_space={env.observation_space}, batched single_observation_space={batch_space(self.single_observation_space, self.num_envs)}")
+        self.func = func
+
+    def observations(self, observations):
+        return self.func(observations)
+
+
+_TORCH_CODES = None
+
+
+def _dtype_code(tensor_dtype):
+    """mi_dtype of a torch dtype, or None."""
+    global _TORCH_CODES
+    if _TORCH_CODES is None:
+        torch = _torch()
+        _TORCH_CODES = {torch.float16: _native.MI_F16, torch.float32: _native.MI_F32, torch.float64: _native.MI_F64, torch.int32: _native.MI_I32,
+                        torch.int64: _native.MI_I64, torch.uint8: _native.MI_U8}
+    return _TORCH_CODES.get(tensor_dtype)
+
+
+class _ArrayTransformObservation(VectorObservationWrapper):
+    """What RescaleObservation, DtypeObservation and FlattenObservation share (vectorize_observation.py:114-257, VectorizeTransformObservation): the
+    reference applies the scalar wrapper's ``func`` row by row and concatenates the rows into a new array of the wrapper's space.  Here the rows are
+    transformed at once:
+
+    * NumPy arrays (and host tensors, which come back as host tensors): one vectorised NumPy expression.
+    * device tensors: one launch of csrc/observation_wrappers.hip on ``torch.cuda.current_stream()`` over the N -- in ``rollout`` the T * N -- rows; no
+      synchronisation, no host copy.
+
+    DEVIATION from the reference: the caller's array or tensor is never modified (``same_out`` writes into it there)."""
+
+    def _setup(self, single_space):
+        self.single_observation_space = single_space
+        self.observation_space = batch_space(single_space, self.num_envs)
+        self.same_out = self.observation_space == self.env.observation_space
+
+    def observations(self, observations):
+        return self._apply(observations, 1)
+
+    def _observations_of_steps(self, block, steps):
+        return self._apply(block, 2)
+
+    def _apply(self, obs, lead):
+        """``obs``: ``lead`` leading axes ((N,) or (T, N)), then the single space's shape; a tuple of such parts for a Tuple space."""
+        torch = _torch()
+        first = obs[0] if isinstance(obs, tuple) else obs
+        if isinstance(first, torch.Tensor):
+            if first.is_cuda:
+                return self._device(obs, lead)
+            host = tuple(p.numpy() for p in obs) if isinstance(obs, tuple) else obs.numpy()
+            return torch.from_numpy(np.ascontiguousarray(self._numpy(host, lead)))
+        return self._numpy(obs, lead)
+
+    def _numpy(self, obs, lead):
+        raise NotImplementedError
+
+    def _device(self, obs, lead):
+        raise NotImplementedError
+
+    @staticmethod
+    def _launch_transform(x, out, kind, dim=1, gradient=None, intercept=None):
+        torch = _torch()
+        lib = _native.load_library()
+        lib.check(lib.transform_observations(x.device.index, C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream), C.c_void_p(x.data_ptr()),
+                                             _dtype_code(x.dtype), C.c_void_p(out.data_ptr()), _dtype_code(out.dtype), x.numel(), int(dim), kind,
+                                             None if gradient is None else C.c_void_p(gradient.data_ptr()),
+                                             None if intercept is None else C.c_void_p(intercept.data_ptr())))
+        return out
+
+
+class RescaleObservation(_ArrayTransformObservation):
+    """vectorize_observation.py:400-438 (transform_observation.py:515-565): the wrapper's space is ``[min_obs, max_obs]`` and an observation becomes
+    ``gradient * obs + intercept`` with rescale_box's arrays, in the box's dtype: the product rounded once, then the sum rounded once (NumPy's two
+    ufuncs; never an FMA).  Unbounded components have gradient 1 and intercept 0 and go through the same arithmetic: -0.0 comes out as +0.0, NaN and
+    the infinities propagate."""
+
+    def __init__(self, env, min_obs, max_obs):
+        super().__init__(env)
+        box = self.env.single_observation_space
+        if not isinstance(box, spaces.Box):
+            raise TypeError(f"RescaleObservation requires a Box observation space, got {type(box)}")
+        space, self.gradient, self.intercept = _rescale_box(box, min_obs, max_obs)
+        self._setup(space)
+        self._on_device = {}  # device index -> (gradient, intercept) as tensors of the box's dtype
+
+    def _numpy(self, obs, lead):
+        with np.errstate(invalid="ignore", over="ignore"):  # (inf * 0 and the like: NaN, as IEEE says)
+            res = self.gradient * np.asarray(obs) + self.intercept
+        return res.astype(self.single_observation_space.dtype, copy=False)
+
+    def _device(self, obs, lead):
+        torch = _torch()
+        dtype = getattr(torch, np.dtype(self.single_observation_space.dtype).name)
+        if obs.dtype != dtype or _dtype_code(dtype) not in (_native.MI_F32, _native.MI_F64):
+            raise TypeError(f"RescaleObservation on device tensors computes in the box's dtype, float32 or float64: the space is {dtype}, the tensor {obs.dtype}")
+        dim = self.gradient.size
+        if dim > _native.OBS_MAX_DIM:
+            raise error.Error(f"RescaleObservation on device tensors takes up to {_native.OBS_MAX_DIM} observation components, the env has {dim}")
+        if tuple(obs.shape[lead:]) != tuple(self.gradient.shape):
+            raise ValueError(f"observations must end in the shape {self.gradient.shape} of the space, got a tensor of shape {tuple(obs.shape)}")
+        params = self._on_device.get(obs.device.index)
+        if params is None:  # made once per device (a wrapper built before any GPU is touched, over the CPU checker say, never makes them)
+            params = self._on_device[obs.device.index] = tuple(torch.from_numpy(np.ascontiguousarray(p).reshape(-1)).to(obs.device)
+                                                               for p in (self.gradient, self.intercept))
+        x = obs.contiguous()
+        return self._launch_transform(x, torch.empty_like(x), _native.OBS_AFFINE, dim, *params)
+
+
+def _cast_box(box, dtype):
+    """``Box(box.low, box.high, box.shape, dtype)`` with the bound handling of spaces/box.py:235-367 whichever Box class is in use: an infinite bound becomes
+    the end of a signed integer range and is refused by an unsigned one; without infinite bounds, a bound outside the dtype's range is refused.  (On
+    copies: the reference's Box writes the integer range into the ENV's own bounds.)"""
+    dt = np.dtype(dtype)
+    if dt.kind == "f":
+        ends = (float(np.finfo(dt).min), float(np.finfo(dt).max))
+    else:
+        ends = (0, 1) if dt.kind == "b" else (int(np.iinfo(dt).min), int(np.iinfo(dt).max))
+    low, high = box.low.copy(), box.high.copy()
+    for name, bound, infinite, end, spelled in (("low", low, np.isneginf(low), ends[0], "-np.inf"), ("high", high, np.isposinf(high), ends[1], "np.inf")):
+        if infinite.any():
+            if dt.kind == "i":
+                bound[infinite] = end
+            elif dt.kind in "ub":
+                raise ValueError(f"Box unsigned int dtype don't support `{spelled}`, {name}={bound}")
+        elif bound.dtype != dt:
+            with np.errstate(over="ignore"):  # (the ends of float64 against float32 bounds: +-inf in the comparison)
+                beyond = np.any(bound < end if name == "low" else end < bound)
+            if beyond:
+                raise ValueError(f"Box {name} is out of bounds of the dtype range, {name}={bound}, {'min' if name == 'low' else 'max'} dtype={end}")
+    return spaces.Box(low=low, high=high, shape=box.shape, dtype=dtype)
+
+
+class DtypeObservation(_ArrayTransformObservation):
+    """vectorize_observation.py:441-465 (transform_observation.py:568-635): ``dtype(obs)``, NumPy's C cast, over Box and Discrete observation spaces
+    (a Discrete space becomes ``Box(start, start + n, (), dtype)``).  Float -> float is rounded ONCE (float64 -> float16 does not pass through float32),
+    float -> integer truncates; NaN and values outside the target's range are undefined there, as they are in NumPy.  Device tensors: float32, float64
+    and int64 observations to float16, float32, float64, int32, int64 or uint8; the NumPy path takes whatever NumPy takes."""
+
+    DEVICE_TARGETS = ("float16", "float32", "float64", "int32", "int64", "uint8")
+
+    def __init__(self, env, dtype):
+        super().__init__(env)
+        space = self.env.single_observation_space
+        if not isinstance(space, (spaces.Box, spaces.Discrete)):
+            raise TypeError(f"DtypeObservation requires a Box, Discrete, MultiDiscrete, or MultiBinary space, got {type(space)}")
+        self.dtype = dtype
+        if isinstance(space, spaces.Box):
+            new = _cast_box(space, dtype)
+        else:
+            low, high, dt = space.start, space.start + space.n, np.dtype(dtype)
+            if dt.kind in "iu":  # (spaces/box.py:247-264, 314-331: the scalar bounds' range check)
+                if low < np.iinfo(dt).min:
+                    raise ValueError(f"Box low is out of bounds of the dtype range, low={low}, min dtype={int(np.iinfo(dt).min)}")
+                if high > np.iinfo(dt).max:
+                    raise ValueError(f"Box high is out of bounds of the dtype range, high={high}, max dtype={int(np.iinfo(dt).max)}")
+            new = spaces.Box(low=low, high=high, shape=(), dtype=dtype)
+        self._np_dtype = np.dtype(new.dtype)
+        self._setup(new)
+
+    def _numpy(self, obs, lead):
+        with np.errstate(invalid="ignore", over="ignore"):
+            return np.asarray(obs).astype(self._np_dtype)
+
+    def _device(self, obs, lead):
+        torch = _torch()
+        target = getattr(torch, self._np_dtype.name, None) if self._np_dtype.name in self.DEVICE_TARGETS else None
+        if target is None:
+            raise error.Error(f"DtypeObservation on device tensors casts to {', '.join(self.DEVICE_TARGETS)}; {self._np_dtype.name} is not among them "
+                              "(a NumPy batch takes any dtype)")
+        if _dtype_code(obs.dtype) not in (_native.MI_F32, _native.MI_F64, _native.MI_I64):
+            raise error.Error(f"DtypeObservation on device tensors casts float32, float64 and int64 observations, got {obs.dtype}")
+        x = obs.contiguous()
+        return self._launch_transform(x, torch.empty(x.shape, dtype=target, device=x.device), _native.OBS_CAST)
+
+
+class FlattenObservation(_ArrayTransformObservation):
+    """vectorize_observation.py:295-317 (spaces/utils.py ``flatten_space`` / ``flatten``).  Box: ``np.asarray(x, space.dtype).reshape(N, -1)`` -- for a
+    device tensor a view, nothing is launched.  Discrete (FrozenLake, CliffWalking, Taxi): one-hot rows of the space's dtype, the space
+    ``Box(0, 1, (n,), int64)``.  A Tuple of Discrete spaces (Blackjack): the one-hot segments concatenated, from the tuple of arrays the env returns (a
+    rollout's ``[T, N, parts]`` block is taken apart by its last axis).  DEVIATION: a state outside its space gives a zero segment (the reference raises
+    IndexError, or wraps a negative index)."""
+
+    def __init__(self, env):
+        super().__init__(env)
+        space = self.env.single_observation_space
+        self._parts = None
+        if isinstance(space, spaces.Box):
+            flat = spaces.Box(space.low.flatten(), space.high.flatten(), dtype=space.dtype)
+        else:
+            parts = space.spaces if isinstance(space, spaces.Tuple) else (space,)
+            if not all(isinstance(p, spaces.Discrete) for p in parts) or not 1 <= len(parts) <= _native.ONE_HOT_MAX_PARTS:
+                raise TypeError(f"FlattenObservation of gymnasium_amd flattens Box, Discrete and Tuple spaces of up to {_native.ONE_HOT_MAX_PARTS} Discrete "
+                                f"spaces, got {space}")
+            self._parts = [(int(p.start), int(p.n)) for p in parts]
+            self._is_tuple = isinstance(space, spaces.Tuple)
+            dtype = np.result_type(*[p.dtype for p in parts])
+            if dtype != np.int64:
+                raise TypeError(f"FlattenObservation of gymnasium_amd writes int64 one-hot rows, the space asks for {dtype}")
+            width = sum(n for _, n in self._parts)
+            flat = spaces.Box(np.zeros(width, dtype), np.ones(width, dtype), dtype=dtype)
+        self._setup(flat)
+
+    def _split(self, obs, lead):
+        """The columns of the one-hot segments: the tuple as it is, a ``lead + (parts,)`` block by its last axis, a Discrete batch alone."""
+        if isinstance(obs, tuple):
+            cols = obs
+        elif self._is_tuple:
+            cols = tuple(obs[..., k] for k in range(len(self._parts)))
+        else:
+            cols = (obs,)
+        if len(cols) != len(self._parts) or any(c.ndim != lead for c in cols):
+            raise ValueError(f"observations must have {lead} leading axes and {len(self._parts)} parts, got shapes {[tuple(c.shape) for c in cols]}")
+        return cols
+
+    def _numpy(self, obs, lead):
+        if self._parts is None:
+            x = np.asarray(obs, dtype=self.single_observation_space.dtype)
+            return x.reshape(x.shape[:lead] + (-1,))
+        cols = self._split(tuple(np.asarray(p) for p in obs) if isinstance(obs, tuple) else np.asarray(obs), lead)
+        return np.concatenate([(np.arange(n) == (np.asarray(c, np.int64) - start)[..., None]).astype(np.int64) for c, (start, n) in zip(cols, self._parts)],
+                              axis=-1)
+
+    def _device(self, obs, lead):
+        torch = _torch()
+        if self._parts is None:
+            return obs.reshape(tuple(obs.shape[:lead]) + (-1,))
+        cols = [c.contiguous() for c in self._split(obs, lead)]  # (Blackjack's parts are columns of one [N, 3] buffer: three small copies)
+        if any(c.dtype != torch.int64 for c in cols):
+            raise TypeError(f"FlattenObservation on device tensors takes int64 states, got {[c.dtype for c in cols]}")
+        k, rows = len(cols), cols[0].numel()
+        out = torch.empty(tuple(cols[0].shape) + (sum(n for _, n in self._parts),), dtype=torch.int64, device=cols[0].device)
+        lib = _native.load_library()
+        lib.check(lib.one_hot(out.device.index, C.c_void_p(torch.cuda.current_stream(out.device).cuda_stream), (C.c_void_p * k)(*[c.data_ptr() for c in cols]), k,
+                              (C.c_int64 * k)(*[s for s, _ in self._parts]), (C.c_int32 * k)(*[n for _, n in self._parts]), rows, C.c_void_p(out.data_ptr())))
+        return out
+
+
+class VectorRewardWrapper(VectorWrapper):
+    """gymnasium.vector.VectorRewardWrapper (vector_env.py:602-625): ``step`` returns ``self.rewards(rewards)`` in place of the rewards.  Neither
+    transparent nor fused; ``capture_steps`` is refused like an observation wrapper's."""
+
+    def __init__(self, env):
+        super().__init__(env)
+        _close_fusion(self.env)
+
+    def rewards(self, rewards):
+        raise NotImplementedError
+
+    def step(self, actions):
+        obs, rewards, terminations, truncations, infos = self.env.step(actions)
+        return obs, self.rewards(rewards), terminations, truncations, infos
+
+    def _rewards_of_steps(self, block, steps):
+        return _stack([self.rewards(block[t]) for t in range(steps)])
+
+    def rollout(self, num_steps, actions=None, **kwargs):
+        """T x ``step()`` through this wrapper: the wrapped ``rollout`` with ``"rewards"`` transformed."""
+        out = dict(self.env.rollout(num_steps, actions, **kwargs))
+        if int(out["rewards"].shape[0]) > 0:
+            out["rewards"] = self._rewards_of_steps(out["rewards"], int(out["rewards"].shape[0]))
+        return out
+
+    def capture_steps(self, *args, **kwargs):
+        _refuse_capture(self, "rewards")
+
+
+class TransformReward(VectorRewardWrapper):
+    """vectorize_reward.py:32-70: ``func`` is applied to the reward batch as given (NumPy in, NumPy out; device tensor in, device tensor out); ``rollout``
+    applies it to the ``[T, N]`` rewards at once."""
+
+    def __init__(self, env, func):
+        super().__init__(env)
+        self.func = func
+
+    def rewards(self, rewards):
+        return self.func(rewards)
+
+    def _rewards_of_steps(self, block, steps):
+        return self.func(block)

@@ -91,7 +91,11 @@ typedef enum mi_dtype {
      * promotion (NEP 50): np.float32 + float stays float32 where np.float32 + np.float64 becomes float64.  Only
      * MountainCarContinuous tells the two apart (continuous_mountain_car.py:153-155, its np.float32 state); every other kind treats the
      * value as MI_F64. */
-    MI_F64_WEAK = 3
+    MI_F64_WEAK = 3,
+    /* targets of mi_transform_observations(MI_OBS_CAST) only: no engine buffer holds them */
+    MI_F16 = 4,
+    MI_I32 = 5,
+    MI_U8 = 6
 } mi_dtype;
 
 /*
@@ -496,6 +500,34 @@ int mi_normalize_reward_steps(mi_running_stats *return_rms, void *hip_stream, fl
 #define MI_TRANSFORM_MAX_ACT_DIM 32
 int mi_transform_actions(int device, void *hip_stream, const void *in, int in_dtype, void *out, int out_dtype, int64_t elements, int act_dim,
                          int kind, const double *p0, const double *p1);
+
+/*
+ * The stateless observation transforms of gymnasium/wrappers/vector/vectorize_observation.py over an observation block in device memory
+ * (csrc/observation_wrappers.hip; added to ABI 10, which they leave as it is).  Both calls only enqueue on hip_stream: no allocation, no
+ * synchronisation, no state.  out must not overlap in.
+ *
+ * mi_transform_observations, element by element over in / out: [elements] device pointers of in_dtype / out_dtype:
+ *   MI_OBS_AFFINE  RescaleObservation: gradient * obs + intercept (wrappers/utils.py:260-261), MI_F32 -> MI_F32 or MI_F64 -> MI_F64: the product
+ *                  rounded once, then the sum rounded once, never an FMA.  Rows of obs_dim <= MI_OBS_MAX_DIM entries (elements = T * num_envs *
+ *                  obs_dim); element i uses entry i % obs_dim of gradient / intercept: DEVICE arrays of obs_dim values of in_dtype.
+ *   MI_OBS_CAST    DtypeObservation: NumPy's C cast (transform_observation.py:633) from MI_F32 / MI_F64 / MI_I64 to MI_F16 / MI_F32 / MI_F64 / MI_I32 /
+ *                  MI_I64 / MI_U8.  Float -> float is rounded once to nearest-even (MI_F64 -> MI_F16 does NOT pass through float32), float -> integer
+ *                  truncates (NaN and values outside the target's range: undefined, as in NumPy), integer -> integer keeps the low bits.  obs_dim is
+ *                  not used; gradient and intercept are NULL.
+ *
+ * mi_one_hot, FlattenObservation of a Discrete space or a Tuple of them (spaces/utils.py:167-195): parts = num_parts <= MI_ONE_HOT_MAX_PARTS
+ * device columns of `rows` int64 states (HOST array of device pointers; start / width: HOST arrays, the spaces' start and n), out: device
+ * [rows][W] int64, W = width[0] + ... : column (width[0] + ... + width[k - 1]) + j of a row is 1 iff parts[k][row] - start[k] == j, everything else 0.
+ * A state outside [start, start + n) leaves its segment zero (the reference raises IndexError or wraps a negative index).
+ */
+#define MI_OBS_AFFINE 0
+#define MI_OBS_CAST 1
+#define MI_OBS_MAX_DIM 1024
+#define MI_ONE_HOT_MAX_PARTS 4
+int mi_transform_observations(int device, void *hip_stream, const void *in, int in_dtype, void *out, int out_dtype, int64_t elements, int obs_dim,
+                              int kind, const void *gradient, const void *intercept);
+int mi_one_hot(int device, void *hip_stream, const int64_t *const *parts, int num_parts, const int64_t *start, const int32_t *width, int64_t rows,
+               int64_t *out);
 
 /* The same three wrappers as the OUTPUT STAGE of the step kernel (classic-control kinds): mi_step / mi_step_async then return the wrapped
  * observations and rewards in place of the raw ones -- one extra launch per step (the normalisations need the statistics of the WHOLE batch,
