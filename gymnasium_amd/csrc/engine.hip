@@ -131,6 +131,13 @@ template <class E, class = void>
 struct HasAttrs : std::false_type {};
 template <class E>
 struct HasAttrs<E, std::void_t<decltype(E::N_ATTR)>> : std::true_type {};
+// E::step() itself draws from the sub-environment's generator (envs_classic.h AcrobotAttrT: torque noise): E::step_draws(trig) says whether the lane
+// takes its one next_double this step, E::step_drawn(trig, u) receives it.  Such a type's reset draws are never taken ahead (ResetQueue stays
+// empty between steps), so the generator is always at the reference's position and the draws come in the reference's order.
+template <class E, class = void>
+struct HasStepDraws : std::false_type {};
+template <class E>
+struct HasStepDraws<E, std::void_t<decltype(E::STEP_DRAWS)>> : std::integral_constant<bool, E::STEP_DRAWS> {};
 // The lane's attributes, requested with the rest of its loads and handed to its register struct (Lane::trig) on arrival; empty for the other types.
 template <class E, bool = HasAttrs<E>::value>
 struct AttrRequest {
@@ -282,6 +289,10 @@ MI_DEV void lane_step(const DevEnv &d, int i, Lane<E> &L, typename E::Act a, Ste
     bool te = false, tr = false;
     double rew = 0.0;
     o.has_final = false;
+    [[maybe_unused]] Pcg64 stepped;  // HasStepDraws without a queue: the lane's generator, which the step's own draw moves before a reset reads it
+    if constexpr (HasStepDraws<E>::value) {
+        if (!q) stepped = preloaded ? *preloaded : load_rng(d, i), preloaded = &stepped;
+    }
     if (MODE == MI_AUTORESET_NEXT_STEP && (L.flags & kNeedsReset)) {
         // :279-284 the step after a finished episode resets, ignores the action, returns reward 0 / not done
         lane_autoreset<E>(d, i, L, q, preloaded);
@@ -300,6 +311,16 @@ MI_DEV void lane_step(const DevEnv &d, int i, Lane<E> &L, typename E::Act a, Ste
             E::obs(L.s, L.flags, o.obs, L.trig);
             o.reward = 0.0, o.terminated = false, o.truncated = false, o.ep_ret = 0.0, o.ep_len = 0;
             return;
+        }
+        if constexpr (HasStepDraws<E>::value) {
+            if (E::step_draws(L.trig)) {
+                if (q) {
+                    E::step_drawn(L.trig, q->rng.next_double());
+                } else {  // the generator moves in memory now; a SAME_STEP reset below continues from there
+                    E::step_drawn(L.trig, stepped.next_double());
+                    store_rng_state(d, i, stepped);
+                }
+            }
         }
         E::step(L.s, L.flags, a, d.P, rew, te, L.trig);
         L.elapsed += 1;  // TimeLimit.step (wrappers/common.py:129-133)
@@ -350,6 +371,9 @@ MI_DEV void lane_step_fused(const DevEnv &d, Lane<E> &L, typename E::Act a, Step
             *d.error = kErrInvalidAction;
             a = (typename E::Act)0;
         }
+    }
+    if constexpr (HasStepDraws<E>::value) {  // a lane that steps (not one that resets, or whose action is refused) takes its draw before the dynamics
+        if (!resetting && !invalid && E::step_draws(L.trig)) E::step_drawn(L.trig, q.rng.next_double());
     }
     // the reset candidate (sync_vector_env.py:279-284): the state was formed from the queued draws when they were drawn
     const double (&rs)[E::S] = q.rs;
@@ -737,7 +761,8 @@ __global__ __launch_bounds__(kBlock) void step_kernel(DevEnv d, StepPtrs io, Epi
     StepOut<E> o;
     LaneRequest<E> rq;
     AttrRequest<E> ar;
-    if (i < d.N) rq.template request<SAMPLE>(d, io.actions, io.act_lane, i, MODE != MI_AUTORESET_DISABLED), ar.request(at, d, i);
+    constexpr bool GEN = MODE != MI_AUTORESET_DISABLED || HasStepDraws<E>::value;  // the lane's generator: consumed by a reset, or by the step itself
+    if (i < d.N) rq.template request<SAMPLE>(d, io.actions, io.act_lane, i, GEN), ar.request(at, d, i);
     BlockTotals before = block_totals_load(d);
     tables_init<E>();
     hold_opaque(before.count), hold_opaque(before.ret);
@@ -754,7 +779,7 @@ __global__ __launch_bounds__(kBlock) void step_kernel(DevEnv d, StepPtrs io, Epi
             io.act_lane[i] = (uint64_t)(next >> 64), io.act_lane[(size_t)d.N + i] = (uint64_t)next;
             if (io.actions_out) static_cast<typename E::Act *>(io.actions_out)[i] = a;
         }
-        lane_step<E, MODE>(d, i, L, a, o, st, nullptr, MODE != MI_AUTORESET_DISABLED ? &gen : nullptr);
+        lane_step<E, MODE>(d, i, L, a, o, st, nullptr, GEN ? &gen : nullptr);
         store_lane<E>(d, i, L);
         if (io.obs) store_row<E::OBS>(io.obs + (size_t)i * E::OBS, o.obs);
         if (!EPI && io.reward) io.reward[i] = o.reward;
@@ -892,7 +917,7 @@ __global__ __launch_bounds__(kBlock) void rollout_kernel(DevEnv d, RolloutPtrs i
         //  measured +-0.1 %; Acrobot x4: -6 %.  profiles/r04_maxilp_classic.txt)
 #pragma unroll E::ROLLOUT_UNROLL
         for (int t = 0; t < T; t++) {
-            if ((t & (kRefillPeriod - 1)) == 0 && !q.have) q.refill();
+            if (!HasStepDraws<E>::value && (t & (kRefillPeriod - 1)) == 0 && !q.have) q.refill();
             typename E::Act a;
             if (SAMPLE) {
                 a = action_of_state<E>(astate);
@@ -966,7 +991,7 @@ __global__ __launch_bounds__(kBlock) void rollout_infos_kernel(DevEnv d, Rollout
         //  measured +-0.1 %; Acrobot x4: -6 %.  profiles/r04_maxilp_classic.txt)
 #pragma unroll E::ROLLOUT_UNROLL
         for (int t = 0; t < T; t++) {
-            if ((t & (kRefillPeriod - 1)) == 0 && !q.have) q.refill();
+            if (!HasStepDraws<E>::value && (t & (kRefillPeriod - 1)) == 0 && !q.have) q.refill();
             typename E::Act a;
             if (SAMPLE) {
                 a = action_of_state<E>(astate);
@@ -2833,12 +2858,13 @@ template <class F>
 int dispatch_kind_act(int kind, bool fast_math, int act_kind, F &&f) {
     return fast_math ? dispatch_kind_act_math<FastMath>(kind, act_kind, f) : dispatch_kind_act_math<ExactMath>(kind, act_kind, f);
 }
-// per-lane attributes (mi_set_env_attr has refused Acrobot, fast math and the shared generator)
+// per-lane attributes (mi_set_env_attr has refused fast math and the shared generator)
 template <class F>
 int dispatch_kind_attr(int kind, int act_kind, F &&f) {
     switch (kind) {
     case MI_ENV_CARTPOLE: return f(CartPoleAttrT<ExactMath>());
     case MI_ENV_PENDULUM: return act_kind != MI_F32 ? f(PendulumAttrT<ExactMath, ActF64>()) : f(PendulumAttrT<ExactMath>());
+    case MI_ENV_ACROBOT: return f(AcrobotAttrT<ExactMathBuiltinFma>());  // (the math policy of Acrobot's other kernels, envs_classic.h)
     case MI_ENV_MOUNTAIN_CAR: return f(MountainCarAttrT<ExactMath>());
     case MI_ENV_MOUNTAIN_CAR_CONTINUOUS:
         if (act_kind == MI_F64) return f(MountainCarContinuousAttrT<ExactMath, ActF64>());
@@ -3414,6 +3440,11 @@ static int attr_defaults(const mi_vecenv *v, double *out) {
         memcpy(out, d, sizeof d);
         return MI_ATTR_PENDULUM_COUNT;
     }
+    case MI_ENV_ACROBOT: {
+        const double d[] = {1.0, 1.0, 1.0, 0.5, 0.5, 1.0, 4 * kPi, 9 * kPi, 0.2, 0.0, 0.0};
+        memcpy(out, d, sizeof d);
+        return MI_ATTR_ACROBOT_COUNT;
+    }
     case MI_ENV_MOUNTAIN_CAR: {
         const double d[] = {0.001, 0.0025, 0.07, -1.2, 0.6, 0.5, v->cfg.params[0]};
         memcpy(out, d, sizeof d);
@@ -3430,7 +3461,7 @@ static int attr_defaults(const mi_vecenv *v, double *out) {
 static int attr_check(mi_vecenv *v, int attr, double *defaults) {
     if (!v) return fail(MI_ERR_INVALID_ARGUMENT, "null env");
     const int n = attr_defaults(v, defaults);
-    if (!n) return fail(MI_ERR_UNSUPPORTED, "per-sub-environment attributes: CartPole, Pendulum, MountainCar and MountainCarContinuous only");
+    if (!n) return fail(MI_ERR_UNSUPPORTED, "per-sub-environment attributes: the five classic-control kinds only");
     if (v->shared_rng) return fail(MI_ERR_UNSUPPORTED, "per-sub-environment attributes: not with MI_CFG_SHARED_RNG (CartPoleVectorEnv has no set_attr)");
     if (v->cfg.reserved[0] & MI_CFG_FAST_MATH) return fail(MI_ERR_UNSUPPORTED, "per-sub-environment attributes: not with MI_CFG_FAST_MATH");
     if (attr < 0 || attr >= n) return fail(MI_ERR_INVALID_ARGUMENT, "attribute id out of range for this kind");

@@ -1133,6 +1133,125 @@ struct MountainCarContinuousAttrT : MountainCarContinuousT<M, AK> {
     }
 };
 
+// Acrobot with per-lane attributes.  What depends on the attributes alone is formed once per launch, in the reference's own order of operations
+// (acrobot.py:259-277 evaluates left to right; `x**2` of a Python float is libm's pow, M::sq); the state-dependent part keeps that order too.
+struct AcrobotAttrs : AcrobotTrig {
+    double m1_sq_lc1;    // m1 * lc1**2
+    double sq_l1_lc2;    // l1**2 + lc2**2
+    double l1_lc2_x2;    // 2 * l1 * lc2
+    double l1_lc2;       // l1 * lc2
+    double sq_lc2;       // lc2**2
+    double m2, moi;
+    double m2_lc2_g;     // m2 * lc2 * g
+    double m2_l1_lc2;    // m2 * l1 * lc2  (-m2 * l1 * lc2 is its negation: rounding is symmetric)
+    double m2_l1_lc2_x2; // 2 * m2 * l1 * lc2
+    double m_l_g;        // (m1 * lc1 + m2 * l1) * g
+    double den0;         // m2 * lc2**2 + I2
+    double dt, dt2, dt6; // rk4 over [0, dt] (acrobot.py:451-459): dt - 0, dt / 2.0, dt / 6.0
+    double max_vel_1, max_vel_2;
+    double noise;        // torque_noise_max
+    double u;            // the step's draw from the sub-environment's generator (engine.hip: STEP_DRAWS), read only where noise > 0
+    bool nips;           // book_or_nips == "nips"
+};
+template <class M>
+struct AcrobotAttrT : AcrobotT<M> {
+    typedef AcrobotT<M> Base;
+    typedef int64_t Act;
+    static constexpr bool DUO_ROLLOUT = false;
+    // acrobot.py:147-167 (ids: include/mi355env.h MI_ATTR_ACROBOT_*): LINK_LENGTH_1, LINK_MASS_1, LINK_MASS_2, LINK_COM_POS_1, LINK_COM_POS_2, LINK_MOI,
+    // MAX_VEL_1, MAX_VEL_2, dt, torque_noise_max, book_or_nips (1.0 = "nips")
+    static constexpr int N_ATTR = 11;
+    static MI_DEV double attr_default(int a, const EnvParams &) {
+        constexpr double d[N_ATTR] = {1.0, 1.0, 1.0, 0.5, 0.5, 1.0, 4 * kPi, 9 * kPi, 0.2, 0.0, 0.0};
+        return d[a];
+    }
+    typedef AcrobotAttrs Trig;
+    static MI_DEV void attrs_arrive(const double v[N_ATTR], Trig &t) {
+        const double l1 = v[0], m1 = v[1], m2 = v[2], lc1 = v[3], lc2 = v[4], g = 9.8;
+        double sq_l1, sq_lc1, sq_lc2;
+        M::sq3(l1, lc1, lc2, sq_l1, sq_lc1, sq_lc2);
+        t.m1_sq_lc1 = m1 * sq_lc1;
+        t.sq_l1_lc2 = sq_l1 + sq_lc2;
+        t.l1_lc2_x2 = 2 * l1 * lc2;
+        t.l1_lc2 = l1 * lc2;
+        t.sq_lc2 = sq_lc2;
+        t.m2 = m2, t.moi = v[5];
+        t.m2_lc2_g = m2 * lc2 * g;
+        t.m2_l1_lc2 = m2 * l1 * lc2;
+        t.m2_l1_lc2_x2 = 2 * m2 * l1 * lc2;
+        t.m_l_g = (m1 * lc1 + m2 * l1) * g;
+        t.den0 = m2 * sq_lc2 + v[5];
+        t.dt = v[8] - 0, t.dt2 = t.dt / 2.0, t.dt6 = t.dt / 6.0;
+        t.max_vel_1 = v[6], t.max_vel_2 = v[7];
+        t.noise = v[9], t.u = 0.0;
+        t.nips = v[10] != 0.0;
+    }
+    // The one classic step that draws from the sub-environment's own generator (acrobot.py:207-211): engine.hip takes one next_double for a lane
+    // that is about to step and says so here, and hands it over before the dynamics (lane_step / lane_step_fused: HasStepDraws).
+    static constexpr bool STEP_DRAWS = true;
+    static MI_DEV bool step_draws(const Trig &t) { return t.noise > 0; }  // (false for a NaN, like the reference's `if`)
+    static MI_DEV void step_drawn(Trig &t, double u) { t.u = u; }
+
+    // acrobot.py:244-279 with the lane's attributes.  The divisions are the IEEE ones: d1 is no longer confined to [2.5, 4.5] (Base::dsdt's shared
+    // reciprocal).  The angles stay inside sincos_bounded's domain for the attribute ranges the host admits (classic_control.py ACROBOT_ATTR_RANGES).
+    static MI_DEV void dsdt(const double y[4], double a, double d[4], const Trig &t, bool known = false, double s2k = 0, double c2k = 0) {
+        const double theta1 = y[0], theta2 = y[1], dtheta1 = y[2], dtheta2 = y[3];
+        double c2 = c2k, s2 = s2k;
+        if (!known) M::sincos_bounded(theta2, s2, c2);
+        const double d1 = t.m1_sq_lc1 + t.m2 * (t.sq_l1_lc2 + t.l1_lc2_x2 * c2) + t.moi + t.moi;
+        const double d2 = t.m2 * (t.sq_lc2 + t.l1_lc2 * c2) + t.moi;
+        const double phi2 = t.m2_lc2_g * M::cos_bounded(theta1 + theta2 - kPi / 2.0);
+        double sq_dtheta2, sq_dtheta1, sq_d2;
+        M::sq3(dtheta2, dtheta1, d2, sq_dtheta2, sq_dtheta1, sq_d2);
+        const double phi1 = -t.m2_l1_lc2 * sq_dtheta2 * s2 - t.m2_l1_lc2_x2 * dtheta2 * dtheta1 * s2 + t.m_l_g * M::cos_bounded(theta1 - kPi / 2) + phi2;
+        const double common = a + d2 / d1 * phi1;
+        const double book = common - t.m2_l1_lc2 * sq_dtheta1 * s2 - phi2;  // the java implementation and the book
+        const double nips = common - phi2;                                  // the paper
+        const double ddtheta2 = (t.nips ? nips : book) / (t.den0 - sq_d2 / d1);
+        const double ddtheta1 = -(d2 * ddtheta2 + phi1) / d1;
+        d[0] = dtheta1, d[1] = dtheta2, d[2] = ddtheta1, d[3] = ddtheta2;
+    }
+    // wrap() of acrobot.py:375-393 is one subtraction per turn.  An angle beyond the exact sin / cos range (2^24 turns; no admitted attribute comes
+    // near) would keep a lane in the loop for seconds and an infinite one for ever: such an angle becomes NaN instead.
+    static MI_DEV double wrap(double x) {
+        if (__builtin_expect(!(fabs(x) <= 105414336.0), 0)) return __builtin_nan("");
+        return Base::wrap(x, -kPi, kPi);
+    }
+    static MI_DEV void step(double s[4], uint32_t &flags, Act action, const EnvParams &, double &reward, bool &terminated, Trig &tc) {
+        integrate(s, flags, action, tc);
+        terminated = (-M::cos_bounded(s[0]) - M::cos_bounded(s[1] + s[0])) > 1.0;
+        reward = terminated ? 0.0 : -1.0;
+    }
+    static MI_DEV void integrate(double s[4], uint32_t &flags, Act action, Trig &tc) {
+        const double dt = tc.dt, dt2 = tc.dt2, dt6 = tc.dt6;
+        double a = action == 0 ? -1.0 : (action == 1 ? 0.0 : 1.0);
+        // torque += self.np_random.uniform(-noise, noise): low + (high - low) * next_double (numpy random_uniform)
+        if (tc.noise > 0) a = a + (-tc.noise + (tc.noise - -tc.noise) * tc.u);
+        double k1[4], k2[4], k3[4], k4[4], t[4];
+        dsdt(s, a, k1, tc, tc.ok, tc.s2, tc.c2);
+        tc.ok = false;
+#pragma unroll
+        for (int i = 0; i < 4; i++) t[i] = s[i] + dt2 * k1[i];
+        dsdt(t, a, k2, tc);
+#pragma unroll
+        for (int i = 0; i < 4; i++) t[i] = s[i] + dt2 * k2[i];
+        dsdt(t, a, k3, tc);
+#pragma unroll
+        for (int i = 0; i < 4; i++) t[i] = s[i] + dt * k3[i];
+        dsdt(t, a, k4, tc);
+        double ns[4];
+#pragma unroll
+        for (int i = 0; i < 4; i++) ns[i] = s[i] + dt6 * (k1[i] + 2 * k2[i] + 2 * k3[i] + k4[i]);
+        ns[0] = wrap(ns[0]);
+        ns[1] = wrap(ns[1]);
+        ns[2] = Base::bound(ns[2], -tc.max_vel_1, tc.max_vel_1);
+        ns[3] = Base::bound(ns[3], -tc.max_vel_2, tc.max_vel_2);
+#pragma unroll
+        for (int i = 0; i < 4; i++) s[i] = ns[i];
+        flags &= ~kStateF32;
+    }
+};
+
 typedef CartPoleT<ExactMath> CartPole;
 typedef PendulumT<ExactMath> Pendulum;
 typedef AcrobotT<ExactMathBuiltinFma> Acrobot;

@@ -86,6 +86,7 @@ class CartPoleVectorEnv(_ClassicControlVectorEnv):
     ENV_ATTRS = (("gravity", 9.8, True), ("masscart", 1.0, True), ("masspole", 0.1, True), ("total_mass", 0.1 + 1.0, True), ("length", 0.5, True),
                  ("polemass_length", 0.1 * 0.5, True), ("force_mag", 10.0, True), ("tau", 0.02, True), ("kinematics_integrator", "euler", True),
                  ("theta_threshold_radians", 12 * 2 * math.pi / 360, True), ("x_threshold", 2.4, True))  # cartpole.py:124-136
+    ENV_ATTR_STRINGS = {"kinematics_integrator": ("euler", 0.0, 1.0, False)}  # cartpole.py:185: anything but "euler" is semi-implicit
 
     def __init__(self, num_envs: int = 1, max_episode_steps: int | None = None, sutton_barto_reward: bool = False, rng: str | None = None, **kwargs):
         self._sutton_barto_reward = bool(sutton_barto_reward)
@@ -244,13 +245,101 @@ class PendulumVectorEnv(_ClassicControlVectorEnv):
         return (x, y)
 
 
+# set_attr on Acrobot: the values the engine admits.  Its sin / cos are the reference's only below EXACT_TRIG_RANGE, and with free attributes the
+# angles of the RK4 stages (acrobot.py:455-458) are bounded by nothing but the attributes themselves, so their ranges are limited to a box for
+# which acrobot_stage_angle_bound() shows every stage angle inside that range (tests/test_acrobot_attrs.py evaluates it).  None = no limit on that
+# side; torque_noise_max may also be NaN (no noise, like every value <= 0).
+ACROBOT_ATTR_RANGES = {
+    "LINK_LENGTH_1": (0.0, 1.5), "LINK_MASS_1": (0.0, 2.0), "LINK_MASS_2": (0.0, 2.0), "LINK_COM_POS_1": (0.0, 1.5), "LINK_COM_POS_2": (0.0, 1.5),
+    "LINK_MOI": (0.5, 100.0), "MAX_VEL_1": (0.0, 16.0), "MAX_VEL_2": (0.0, 32.0), "dt": (0.0, 0.25), "torque_noise_max": (None, 4.0),
+}
+ACROBOT_ATTR_STATE_ANGLE = 1e6  # |theta| a state may start a step with (AcrobotVectorEnv._STATE_LIMITS; a stepped state is wrapped to pi)
+
+
+def acrobot_stage_angle_bound(ranges=None, theta0: float = ACROBOT_ATTR_STATE_ANGLE) -> float:
+    """An upper bound on the magnitude of every argument acrobot.py:259-265 hands to sin / cos during one step -- theta2, theta1 - pi/2 and
+    theta1 + theta2 - pi/2 at the four RK4 stages -- for attributes anywhere in ``ranges`` and a state with |theta| <= theta0 whose velocities
+    are within MAX_VEL_1 / MAX_VEL_2.
+
+    With a = m1 lc1^2, b = m2 l1^2, c = m2 l1 lc2, e = m2 lc2^2 + I the mass matrix is [[d1, d2], [d2, e]], d1 = a + b + 2 c cos + e + I,
+    d2 = e + c cos, and ddtheta solves it against (-phi1, torque - book term - phi2).  Its determinant is e (a + b + I) - c^2 cos^2
+    >= e (a + I) + b I (because c^2 <= b (e - I)), hence >= I (a + I + b) and >= e I; with 2 c <= b + e that gives d1 <= 4 det / I, and
+    d2^2 <= e d1 gives |d2| <= 2 det / I, e <= det / I.  So, by Cramer's rule,
+        |ddtheta2| <= (4 |rhs2| + 2 |phi1|) / I,   |ddtheta1| <= (|phi1| + 2 |rhs2|) / I,
+        |phi1| <= J v2^2 + 2 J v1 v2 + H + E,      |rhs2| <= 1 + noise + J v1^2 + E,
+    J = m2 l1 lc2, H = (m1 lc1 + m2 l1) g, E = m2 lc2 g at the top of their ranges, I at the bottom of its range.  The stages chain: the
+    velocities of stage k + 1 are the state's plus dt/2 (dt for the last) times the accelerations of stage k, its angles the state's plus the same
+    multiple of stage k's velocities.  Rounding moves none of this by more than parts in 1e15 (the divisors d1 >= 2 I and e - d2^2/d1 >= I / 4
+    are formed without cancellation to speak of); every acceleration is inflated by 1 % to cover it."""
+    r = ACROBOT_ATTR_RANGES if ranges is None else ranges
+    g = 9.8
+    m1, m2, l1, lc1, lc2 = (r[k][1] for k in ("LINK_MASS_1", "LINK_MASS_2", "LINK_LENGTH_1", "LINK_COM_POS_1", "LINK_COM_POS_2"))
+    moi, dt, noise = r["LINK_MOI"][0], r["dt"][1], max(r["torque_noise_max"][1], 0.0)
+    V = (r["MAX_VEL_1"][1], r["MAX_VEL_2"][1])
+    J, H, E = m2 * l1 * lc2, (m1 * lc1 + m2 * l1) * g, m2 * lc2 * g
+
+    def acc(v1, v2):
+        phi1 = J * v2 * v2 + 2 * J * v1 * v2 + H + E
+        rhs2 = 1.0 + noise + J * v1 * v1 + E
+        return 1.01 * (phi1 + 2 * rhs2) / moi, 1.01 * (4 * rhs2 + 2 * phi1) / moi
+
+    v, angles = V, [theta0, theta0]
+    for h in (dt / 2, dt / 2, dt):  # stages 2, 3, 4 from the derivative of the stage before
+        a = acc(*v)
+        angles = [max(angles[k], theta0 + h * v[k]) for k in range(2)]
+        v = (V[0] + h * a[0], V[1] + h * a[1])
+    return angles[0] + angles[1] + math.pi / 2
+
+
 class AcrobotVectorEnv(_ClassicControlVectorEnv):
+    """``set_attr`` / ``get_attr`` know the attributes acrobot.py's step() reads as numbers -- LINK_LENGTH_1, LINK_MASS_1, LINK_MASS_2,
+    LINK_COM_POS_1, LINK_COM_POS_2, LINK_MOI, MAX_VEL_1, MAX_VEL_2, dt, torque_noise_max -- and the string book_or_nips, within
+    ACROBOT_ATTR_RANGES (ValueError outside).  LINK_LENGTH_2 (read by the renderer only) and the list AVAIL_TORQUE are not supported.  The
+    observation space stays the constructor's, as in the reference (acrobot.py:177-181)."""
+
     KIND = "acrobot"
     _STATE_LIMITS = (((0, 1), 1e6), ((2, 3), 100.0))  # (the velocities too: RK4's intermediate angles grow with their fourth power)
     DEFAULT_MAX_EPISODE_STEPS = 500
+    ENV_ATTRS = (("LINK_LENGTH_1", 1.0, True), ("LINK_MASS_1", 1.0, True), ("LINK_MASS_2", 1.0, True), ("LINK_COM_POS_1", 0.5, True),
+                 ("LINK_COM_POS_2", 0.5, True), ("LINK_MOI", 1.0, True), ("MAX_VEL_1", 4 * math.pi, True), ("MAX_VEL_2", 9 * math.pi, True),
+                 ("dt", 0.2, True), ("torque_noise_max", 0.0, True), ("book_or_nips", "book", True))  # acrobot.py:147-167
+    ENV_ATTR_STRINGS = {"book_or_nips": ("nips", 1.0, 0.0, True)}  # acrobot.py:268
+    _wide_velocities = False  # set_state() gave velocities beyond the attribute box
 
     def __init__(self, num_envs: int = 1, max_episode_steps: int | None = None, **kwargs):
         super().__init__(num_envs=num_envs, max_episode_steps=max_episode_steps, **kwargs)
+
+    def _env_attr_validate(self, name, values):
+        lo, hi = ACROBOT_ATTR_RANGES[name]
+        if hasattr(values, "device"):  # a device tensor: its extremes come back to the host (synchronises)
+            vmin, vmax, nan = float(values.min()), float(values.max()), bool(values.isnan().any())
+        else:
+            arr = np.array([float(v) for v in values], dtype=np.float64)
+            nan = bool(np.isnan(arr).any())
+            vmin, vmax = (float(np.nanmin(arr)), float(np.nanmax(arr))) if not np.isnan(arr).all() else (math.nan, math.nan)
+        if nan and lo is not None:
+            raise ValueError(f"{type(self).__name__}.set_attr({name!r}): NaN is outside the accepted range [{lo:g}, {hi:g}]")
+        if (lo is not None and vmin < lo) or vmax > hi:
+            bad = vmin if (lo is not None and vmin < lo) else vmax
+            rng = f"[{lo:g}, {hi:g}]" if lo is not None else f"<= {hi:g}"
+            raise ValueError(f"{type(self).__name__}.set_attr({name!r}): {bad!r} is outside the accepted range {rng} (the attribute box in which "
+                             f"every RK4 stage angle stays below the exact sin / cos range {self.EXACT_TRIG_RANGE:g}: ACROBOT_ATTR_RANGES)")
+        if self._wide_velocities:
+            raise ValueError(f"{type(self).__name__}.set_attr({name!r}): set_state() gave velocities beyond "
+                             f"({ACROBOT_ATTR_RANGES['MAX_VEL_1'][1]:g}, {ACROBOT_ATTR_RANGES['MAX_VEL_2'][1]:g}), the limits under per-sub-environment attributes")
+
+    def set_state(self, state=None, elapsed_steps=None, flags=None):
+        if state is not None:
+            arr = np.asarray(state, dtype=np.float64)
+            limits = np.array([ACROBOT_ATTR_RANGES["MAX_VEL_1"][1], ACROBOT_ATTR_RANGES["MAX_VEL_2"][1]])
+            wide = bool((np.abs(arr[:, 2:4]) > limits).any())
+            if wide and self._env_attr_mask:
+                raise ValueError(f"{type(self).__name__}.set_state: with per-sub-environment attributes set the velocities must lie within "
+                                 f"({limits[0]:g}, {limits[1]:g}) (ACROBOT_ATTR_RANGES)")
+            super().set_state(state, elapsed_steps, flags)
+            self._wide_velocities = wide
+            return
+        super().set_state(state, elapsed_steps, flags)
 
     def _single_spaces(self):
         high = np.array([1.0, 1.0, 1.0, 1.0, 4 * np.pi, 9 * np.pi], dtype=np.float32)

@@ -55,6 +55,11 @@ def _pcg_words_for_seed(seed: int) -> np.ndarray:
     return _native.pcg_words(gen)
 
 
+class UnknownEnvAttributeError(error.Error, AttributeError):
+    """get_attr / set_attr with a name that is no per-sub-environment attribute of the env's kind.  Both an AttributeError (what the name is) and
+    an error.Error (what every other refusal of get_attr / set_attr raises), so that a caller may catch either."""
+
+
 class HipVectorEnv(VectorEnv):
     """Base class; subclasses set KIND, spaces, default reset bounds and constructor params."""
 
@@ -964,14 +969,16 @@ class HipVectorEnv(VectorEnv):
     # -- per-sub-environment attributes: SyncVectorEnv.get_attr / set_attr (vector/sync_vector_env.py:365-398) ---------------------------
     # ENV_ATTRS: the attributes the reference's step() reads, in the engine's id order (include/mi355env.h MI_ATTR_*), as (name, default, whether
     # an np.float64 value is accepted); a default of None is the constructor's value (_env_attr_ctor).  None: no per-lane physics.  Unlike the
-    # reference, set_attr does not create attributes: an unknown name raises AttributeError.
+    # reference, set_attr does not create attributes: an unknown name raises UnknownEnvAttributeError (an AttributeError and an error.Error).
     ENV_ATTRS: tuple | None = None
+    # the string-valued ones: name -> (string, row value of that string, row value of anything else, strings only).  The engine keeps a number.
+    ENV_ATTR_STRINGS: dict = {}
     _env_attr_mask = 0  # bit k: attribute k was set (the engine runs the per-lane kernels once any is)
 
     def _env_attr_refusal(self) -> str | None:
         if self.ENV_ATTRS is None:
-            return (f"{type(self).__name__}: per-sub-environment attributes (get_attr / set_attr) exist for CartPole-v1, Pendulum-v1, MountainCar-v0 "
-                    "and MountainCarContinuous-v0 only")
+            return (f"{type(self).__name__}: per-sub-environment attributes (get_attr / set_attr) exist for CartPole-v1, Pendulum-v1, Acrobot-v1, "
+                    "MountainCar-v0 and MountainCarContinuous-v0 only")
         return None
 
     def _env_attr_id(self, name: str) -> int:
@@ -980,9 +987,12 @@ class HipVectorEnv(VectorEnv):
             raise error.Error(refusal)
         names = [a[0] for a in self.ENV_ATTRS]
         if name not in names:
-            raise AttributeError(f"{type(self).__name__} has no per-sub-environment attribute {name!r}; the supported names are {', '.join(names)} "
-                                 "(the attributes the reference's step() reads: set_attr does not create new ones)")
+            raise UnknownEnvAttributeError(f"{type(self).__name__} has no per-sub-environment attribute {name!r}; the supported names are "
+                                           f"{', '.join(names)} (the attributes the reference's step() reads: set_attr does not create new ones)")
         return names.index(name)
+
+    def _env_attr_validate(self, name: str, values) -> None:
+        """A kind's own limits on an attribute's values (a list of Python numbers, or a 1-D device tensor): raises ValueError.  None here."""
 
     def _env_attr_default(self, k: int):
         name, default, _ = self.ENV_ATTRS[k]
@@ -1010,7 +1020,7 @@ class HipVectorEnv(VectorEnv):
         k = self._env_attr_id(name)
         _, _, f64_ok = self.ENV_ATTRS[k]
         N = self.num_envs
-        integrator = name == "kinematics_integrator"
+        strings = self.ENV_ATTR_STRINGS.get(name)
 
         def wrong_length(n):
             return ValueError("Values must be a list or tuple with length equal to the number of environments. "
@@ -1021,8 +1031,8 @@ class HipVectorEnv(VectorEnv):
             if values.dim() != 1 or values.shape[0] != N:
                 raise wrong_length(values.shape[0] if values.dim() else 1)
             if values.device.type == "cuda":
-                if integrator:
-                    raise TypeError("set_attr('kinematics_integrator') takes strings, not a tensor")
+                if strings is not None:
+                    raise TypeError(f"set_attr({name!r}) takes strings, not a tensor")
                 dev = values
             else:
                 values = values.tolist()
@@ -1035,8 +1045,13 @@ class HipVectorEnv(VectorEnv):
         if dev is None:
             if len(values) != N:
                 raise wrong_length(len(values))
-            if integrator:
-                row = np.array([0.0 if (isinstance(v, str) and v == "euler") else 1.0 for v in values])
+            if strings is not None:
+                word, hit, miss, strings_only = strings
+                if strings_only:
+                    for v in values:
+                        if not isinstance(v, str):
+                            raise TypeError(f"set_attr({name!r}) takes strings, got {type(v).__name__}")
+                row = np.array([hit if (isinstance(v, str) and v == word) else miss for v in values])
             else:
                 for v in values:
                     if isinstance(v, np.generic):
@@ -1047,6 +1062,8 @@ class HipVectorEnv(VectorEnv):
                     elif not isinstance(v, (bool, int, float)):
                         raise TypeError(f"set_attr({name!r}) takes numbers, got {type(v).__name__}")
                 row = np.array([float(v) for v in values], dtype=np.float64)
+        if strings is None:
+            self._env_attr_validate(name, values if dev is None else dev)
         if not hasattr(self._engine.lib, "set_env_attr"):
             raise error.Error(f"set_attr({name!r}): the engine behind this env has no per-sub-environment attributes (mi_set_env_attr)")
         if dev is not None:

@@ -403,13 +403,20 @@ int mi_get_rng(mi_vecenv *env, uint64_t *pcg);
 
 /*
  * Per-sub-environment physics (ABI 8): SyncVectorEnv.set_attr / get_attr (vector/sync_vector_env.py:365-398) on the attributes the scalar env's
- * step() reads, for CARTPOLE, PENDULUM, MOUNTAIN_CAR and MOUNTAIN_CAR_CONTINUOUS (not with MI_CFG_SHARED_RNG or MI_CFG_FAST_MATH).
+ * step() reads, for the five classic-control kinds (not with MI_CFG_SHARED_RNG or MI_CFG_FAST_MATH).
  * mi_set_env_attr: `values` = num_envs float64, one per sub-environment, host (on_device = 0, staged before the call returns) or device memory
  * (on_device = 1: a device-to-device copy enqueued on the env's stream); NULL restores the construction value.  Takes effect from the next
  * mi_step / mi_rollout; resets do not undo it and mi_get_state does not include it.  The first call switches the env to the per-lane kernels,
  * whose values live in device memory updated in place (a HIP graph captured after the switch sees later calls).
  * mi_get_env_attr: the current values into `host_out` (num_envs float64); synchronises.
  * The string kinematics_integrator is stored as 0 ("euler") / 1 (anything else: semi-implicit Euler, cartpole.py:185).
+ * ACROBOT (acrobot.py:147-167): book_or_nips is stored as 0 ("book", and any other string) / 1 ("nips").  A sub-environment whose
+ * torque_noise_max is > 0 takes one draw from its own generator (the one its resets consume) in every step, before the dynamics; a step that also
+ * resets (SAME_STEP) draws for the step first.  LINK_LENGTH_2 and AVAIL_TORQUE are not attributes here.  Domain: the RK4 stage angles must stay
+ * within the exact sin / cos range above, which holds for masses in [0, 2], LINK_LENGTH_1 and the COM positions in [0, 1.5], LINK_MOI in [0.5, 100],
+ * MAX_VEL_1 in [0, 16], MAX_VEL_2 in [0, 32], dt in [0, 0.25], torque_noise_max <= 4 and state velocities within (16, 32): the host class refuses
+ * anything else (gymnasium_amd/envs/classic_control.py ACROBOT_ATTR_RANGES, where the bound is worked out); a binding of its own should too.  An
+ * angle that leaves that range before wrap() becomes NaN instead of being wrapped one turn at a time.
  */
 enum {
     MI_ATTR_CARTPOLE_GRAVITY = 0, MI_ATTR_CARTPOLE_MASSCART = 1, MI_ATTR_CARTPOLE_MASSPOLE = 2, MI_ATTR_CARTPOLE_TOTAL_MASS = 3,
@@ -422,7 +429,10 @@ enum {
     MI_ATTR_MOUNTAIN_CAR_MAX_POSITION = 4, MI_ATTR_MOUNTAIN_CAR_GOAL_POSITION = 5, MI_ATTR_MOUNTAIN_CAR_GOAL_VELOCITY = 6, MI_ATTR_MOUNTAIN_CAR_COUNT = 7,
     MI_ATTR_MOUNTAIN_CAR_CONTINUOUS_MIN_ACTION = 0, MI_ATTR_MOUNTAIN_CAR_CONTINUOUS_MAX_ACTION = 1, MI_ATTR_MOUNTAIN_CAR_CONTINUOUS_POWER = 2,
     MI_ATTR_MOUNTAIN_CAR_CONTINUOUS_MAX_SPEED = 3, MI_ATTR_MOUNTAIN_CAR_CONTINUOUS_MIN_POSITION = 4, MI_ATTR_MOUNTAIN_CAR_CONTINUOUS_MAX_POSITION = 5,
-    MI_ATTR_MOUNTAIN_CAR_CONTINUOUS_GOAL_POSITION = 6, MI_ATTR_MOUNTAIN_CAR_CONTINUOUS_GOAL_VELOCITY = 7, MI_ATTR_MOUNTAIN_CAR_CONTINUOUS_COUNT = 8
+    MI_ATTR_MOUNTAIN_CAR_CONTINUOUS_GOAL_POSITION = 6, MI_ATTR_MOUNTAIN_CAR_CONTINUOUS_GOAL_VELOCITY = 7, MI_ATTR_MOUNTAIN_CAR_CONTINUOUS_COUNT = 8,
+    MI_ATTR_ACROBOT_LINK_LENGTH_1 = 0, MI_ATTR_ACROBOT_LINK_MASS_1 = 1, MI_ATTR_ACROBOT_LINK_MASS_2 = 2, MI_ATTR_ACROBOT_LINK_COM_POS_1 = 3,
+    MI_ATTR_ACROBOT_LINK_COM_POS_2 = 4, MI_ATTR_ACROBOT_LINK_MOI = 5, MI_ATTR_ACROBOT_MAX_VEL_1 = 6, MI_ATTR_ACROBOT_MAX_VEL_2 = 7,
+    MI_ATTR_ACROBOT_DT = 8, MI_ATTR_ACROBOT_TORQUE_NOISE_MAX = 9, MI_ATTR_ACROBOT_BOOK_OR_NIPS = 10, MI_ATTR_ACROBOT_COUNT = 11
 };
 int mi_set_env_attr(mi_vecenv *env, int attr, const double *values, int on_device);
 int mi_get_env_attr(mi_vecenv *env, int attr, double *host_out);
