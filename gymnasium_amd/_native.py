@@ -48,6 +48,9 @@ HOST_SYMBOLS += ["rollout_infos"]
 # action_space.sample(mask=...) / sample(probability=...) on the action stream and the generator's pending 32-bit half (added to ABI 10, which they leave as it is): product library only --
 # the device-sampled space (vector/device_policy.py) tells the backends apart by whether the entry point is bound.
 HOST_SYMBOLS += ["action_sample_masked", "action_sample_weighted", "action_get_buffered", "action_set_buffered"]
+# RepeatAction / StickyAction of the sub-environments inside the step (mi_set_step_wrappers; added to ABI 10, which it leaves as it is): product library
+# only -- HipVectorEnv.set_step_wrappers tells the backends apart by whether the entry point is bound.
+HOST_SYMBOLS += ["set_step_wrappers"]
 WRAPPER_SYMBOLS = ["rms_create", "rms_destroy", "rms_get", "rms_set", "normalize_observation", "normalize_reward", "clip_reward", "set_step_epilogue"]
 # The normalisations over a whole trajectory (ABI 9): what the wrappers' rollout() runs over the output of mi_rollout.
 WRAPPER_SYMBOLS += ["wrapper_steps_workspace", "normalize_observation_steps", "normalize_reward_steps"]
@@ -180,6 +183,10 @@ class NativeLib:
             self.action_sample_weighted = f("action_sample_weighted", [vp, vp, vp, i32], i32)
             self.action_get_buffered = f("action_get_buffered", [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)], i32)
             self.action_set_buffered = f("action_set_buffered", [vp, C.c_uint32, C.c_uint32], i32)
+            try:
+                self.set_step_wrappers = f("set_step_wrappers", [vp, i32, dbl, i32], i32)
+            except ImportError:  # an ABI 10 build from before the entry point (MI355ENV_LIBRARY, A/B runs): HipVectorEnv.set_step_wrappers refuses
+                pass
 
     def _fn(self, name, argtypes, restype):
         try:
@@ -478,6 +485,11 @@ class Engine:
         out = np.empty(self.num_envs, dtype=np.float64)
         self.lib.check(self.lib.get_env_attr(self.handle, int(attr), _ptr(out)))
         return out
+
+    def set_step_wrappers(self, num_repeats: int, sticky_probability: float, sticky_duration: int):
+        """mi_set_step_wrappers: RepeatAction(num_repeats) / StickyAction(sticky_probability, sticky_duration) around every sub-environment; 0 = no
+        such wrapper."""
+        self.lib.check(self.lib.set_step_wrappers(self.handle, int(num_repeats), float(sticky_probability), int(sticky_duration)))
 
     def get_rng(self) -> np.ndarray:
         words = np.empty((self.num_envs, 4), dtype=np.uint64)

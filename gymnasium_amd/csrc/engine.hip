@@ -90,6 +90,16 @@ struct AttrDev {
     const double *rows;  // [A][N] component-major, like DevEnv::state
     uint32_t mask;       // wave-uniform
 };
+// The per-sub-environment action wrappers of the reference (wrappers/stateful_action.py) folded into the step (mi_set_step_wrappers): the last
+// argument of step_wrapped_kernel / rollout_wrapped_kernel, which the env runs instead of step_kernel / rollout_kernel / rollout_infos_kernel then.
+// Everything but the two arrays is wave-uniform.
+struct WrapDev {
+    int repeats;            // RepeatAction(env, repeats): inner steps per step(); 0: no such wrapper
+    int sticky_duration;    // StickyAction(env, p, duration); 0: no such wrapper
+    double sticky_p;
+    uint64_t *last_action;  // [N] StickyAction.last_action: the bits of the lane's last effective action (E::Act)
+    uint32_t *sticky_word;  // [N] bit 31: last_action is not None; bits 0..30: repeats_taken (is_sticky_actions <=> > 0; num_repeats is then the duration)
+};
 }  // namespace mi_internal
 using namespace mi_internal;
 namespace {
@@ -431,6 +441,120 @@ MI_DEV void lane_step_fused(const DevEnv &d, Lane<E> &L, typename E::Act a, Step
     o.terminated = !resetting && te, o.truncated = !resetting && tr;
     o.ep_ret = done ? ep_ret : 0.0, o.ep_len = done ? ep_len : 0;
     o.has_final = false;
+}
+
+// ---- RepeatAction / StickyAction of the scalar envs (wrappers/stateful_action.py:16-220) inside the lane's step -----------------------------------
+// The reference wraps every sub-environment: SyncVectorEnv(StickyAction(RepeatAction(TimeLimit(env), k), p, d)).  Both sit BELOW the vector level, so a
+// finished lane stops repeating while its neighbours go on, and the sticky draw comes from the lane's own generator -- the one its resets consume --
+// before the step.  The kernels that run it are their own (step_wrapped_kernel, rollout_wrapped_kernel): the others are the code they were.
+// StickyAction's state of one lane, in registers for the launch
+template <class E>
+struct WrapLane {
+    typename E::Act last;
+    uint32_t word;
+};
+template <class A>
+MI_DEV uint64_t action_bits(A a) {
+    uint64_t b = 0;
+    __builtin_memcpy(&b, &a, sizeof a);
+    return b;
+}
+template <class E>
+MI_DEV void load_wrap_lane(const WrapDev &w, int i, WrapLane<E> &s) {
+    uint64_t b = 0;
+    s.word = 0u;
+    if (w.sticky_duration) b = w.last_action[i], s.word = w.sticky_word[i];
+    __builtin_memcpy(&s.last, &b, sizeof s.last);
+}
+template <class E>
+MI_DEV void store_wrap_lane(const WrapDev &w, int i, const WrapLane<E> &s) {
+    if (w.sticky_duration) w.last_action[i] = action_bits(s.last), w.sticky_word[i] = s.word;
+}
+constexpr uint32_t kStickyHasLast = 1u << 31;
+
+// lane_step with the two wrappers around E::step.  The plain form of lane_step (branches, not lane_step_fused's selects): the repeat loop has a
+// wave-uniform trip count (w.repeats), and a lane whose episode ended inside it is masked off for the remaining trips (`active`), so the wavefront
+// stays in step.  Order of the generator's draws, as in the reference: the sticky draw (StickyAction.action, :118-142), then each inner step's own
+// draw (STEP_DRAWS), then a SAME_STEP reset's.  Nothing is drawn ahead: with a queue (rollouts) the generator is q->rng and the queue is filled
+// only by the reset that empties it; without (step_kernel) it is a copy of `preloaded` that goes back to memory when it moved.
+template <class E, int MODE>
+MI_DEV void lane_step_wrapped(const DevEnv &d, const WrapDev &w, WrapLane<E> &sl, int i, Lane<E> &L, typename E::Act a, StepOut<E> &o, LaneStats &st,
+                              ResetQueue<E> *q, const Pcg64 *preloaded) {
+    o.has_final = false;
+    Pcg64 own;
+    if (!q) own = preloaded ? *preloaded : load_rng(d, i);
+    if (MODE == MI_AUTORESET_NEXT_STEP && (L.flags & kNeedsReset)) {
+        // sync_vector_env.py:279-284: the step after a finished episode resets (StickyAction.reset clears its state, :107-116), ignores the action
+        // -- action() is not called: no draw --, repeats nothing and returns reward 0
+        lane_autoreset<E>(d, i, L, q, &own);
+        st.reset_steps++;
+        sl.word = 0u;
+        E::obs(L.s, L.flags, o.obs, L.trig);
+        o.reward = 0.0, o.terminated = false, o.truncated = false, o.ep_ret = 0.0, o.ep_len = 0;
+        L.flags &= ~kNeedsReset;
+        return;
+    }
+    if ((MODE == MI_AUTORESET_DISABLED && (L.flags & kNeedsReset)) || !E::valid(a)) {
+        // lane_step's two refusals: the lane, its generator and its sticky state are left untouched.  The action is validated AS GIVEN -- stricter than
+        // the reference, which never looks at an action that a sticky one replaces.
+        *d.error = (MODE == MI_AUTORESET_DISABLED && (L.flags & kNeedsReset)) ? kErrDisabledStepped : kErrInvalidAction;
+        E::obs(L.s, L.flags, o.obs, L.trig);
+        o.reward = 0.0, o.terminated = false, o.truncated = false, o.ep_ret = 0.0, o.ep_len = 0;
+        return;
+    }
+    Pcg64 &g = q ? q->rng : own;
+    bool drew = false;
+    if (w.sticky_duration) {  // StickyAction.action (:118-142) with an int duration: num_repeats = duration whenever a series runs
+        uint32_t taken = sl.word & ~kStickyHasLast;
+        bool stick = taken != 0u;  // already stuck: no draw
+        if (!stick && (sl.word & kStickyHasLast)) stick = g.next_double() < w.sticky_p, drew = true;  // np_random.uniform() < p, float64
+        a = stick ? sl.last : a;
+        taken = stick ? taken + 1u : 0u;
+        taken = taken == (uint32_t)w.sticky_duration ? 0u : taken;  // the series is over: is_sticky_actions, num_repeats, repeats_taken cleared
+        sl.last = a, sl.word = kStickyHasLast | taken;
+    }
+    // RepeatAction.step (:197-220) over TimeLimit.step (wrappers/common.py:129-133): elapsed counts INNER steps
+    const int trips = w.repeats > 0 ? w.repeats : 1;
+    double total = 0.0, rew = 0.0;
+    bool te = false, tr = false, active = true;
+    for (int j = 0; j < trips; j++) {
+        if (active) {
+            if constexpr (HasStepDraws<E>::value) {
+                if (E::step_draws(L.trig)) E::step_drawn(L.trig, g.next_double()), drew = true;
+            }
+            E::step(L.s, L.flags, a, d.P, rew, te, L.trig);
+            L.elapsed += 1;
+            tr = d.max_steps > 0 && (int)L.elapsed >= d.max_steps;
+            total += rew;  // total_reward = 0.0; total_reward += float(reward), in inner order
+            active = !(te || tr);
+        }
+    }
+    if (w.repeats > 0) rew = total;  // (without RepeatAction the one reward as it is, the sign of a zero included)
+    // what the vector level sees (RecordEpisodeStatistics, mi_stats): ONE step of this sub-environment with the summed reward
+    L.ep_ret += rew, L.ep_len += 1;
+    st.env_steps++;
+    const bool done = te || tr;
+    o.ep_ret = done ? L.ep_ret : 0.0;
+    o.ep_len = done ? L.ep_len : 0;
+    if (done) {
+        st.episodes++;
+        st.return_sum += L.ep_ret;
+        st.length_sum += (uint64_t)L.ep_len;
+    }
+    if (MODE == MI_AUTORESET_SAME_STEP && done) {
+        E::obs(L.s, L.flags, o.final_obs, L.trig);  // the last INNER observation
+        o.has_final = true;
+        lane_autoreset<E>(d, i, L, q, &own);  // (without a queue: continues from `own` and stores it)
+        sl.word = 0u;
+    } else if (!q && drew) {
+        store_rng_state(d, i, own);
+    }
+    E::obs(L.s, L.flags, o.obs, L.trig);
+    o.reward = rew, o.terminated = te, o.truncated = tr;
+    if (done && MODE != MI_AUTORESET_SAME_STEP)
+        L.flags |= kNeedsReset;
+    else
+        L.flags &= ~kNeedsReset;
 }
 
 template <int W>
@@ -798,6 +922,48 @@ __global__ __launch_bounds__(kBlock) void step_kernel(DevEnv d, StepPtrs io, Epi
     block_accumulate(d, st, before);
 }
 
+// mi_set_step_wrappers: step_kernel (without an epilogue) with RepeatAction / StickyAction around E::step -- lane_step_wrapped in place of lane_step, and
+// StickyAction's two words per lane requested and stored with the rest of the lane.  The generator is always loaded: the sticky draw needs it.
+template <class E, int MODE, bool SAMPLE>
+__global__ __launch_bounds__(kBlock) void step_wrapped_kernel(DevEnv d, StepPtrs io, AttrDev at, WrapDev w) {
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    LaneStats st = {0u, 0u, 0u, 0ull, 0.0};
+    StepOut<E> o;
+    LaneRequest<E> rq;
+    AttrRequest<E> ar;
+    WrapLane<E> sl;
+    if (i < d.N) rq.template request<SAMPLE>(d, io.actions, io.act_lane, i, true), ar.request(at, d, i), load_wrap_lane(w, i, sl);
+    BlockTotals before = block_totals_load(d);
+    tables_init<E>();
+    hold_opaque(before.count), hold_opaque(before.ret);
+    if (i < d.N) {
+        Lane<E> L;
+        Pcg64 gen;
+        rq.arrive(L, gen);
+        ar.arrive(L.trig);
+        typename E::Act a = rq.a;
+        if constexpr (SAMPLE) {
+            const u128 astate = make_u128(rq.ag[0], rq.ag[1]);
+            a = action_of_state<E>(astate);
+            const u128 next = io.act_jump.mult * astate + io.act_jump.plus;
+            io.act_lane[i] = (uint64_t)(next >> 64), io.act_lane[(size_t)d.N + i] = (uint64_t)next;
+            if (io.actions_out) static_cast<typename E::Act *>(io.actions_out)[i] = a;  // the policy's action, not the effective one
+        }
+        lane_step_wrapped<E, MODE>(d, w, sl, i, L, a, o, st, nullptr, &gen);
+        store_lane<E>(d, i, L);
+        store_wrap_lane(w, i, sl);
+        if (io.obs) store_row<E::OBS>(io.obs + (size_t)i * E::OBS, o.obs);
+        if (io.reward) io.reward[i] = o.reward;
+        if (io.terminated) io.terminated[i] = o.terminated;
+        if (io.truncated) io.truncated[i] = o.truncated;
+        if (MODE == MI_AUTORESET_SAME_STEP && io.final_obs && o.has_final)
+            store_row<E::OBS>(io.final_obs + (size_t)i * E::OBS, o.final_obs);
+        if (io.ep_ret) io.ep_ret[i] = o.ep_ret;
+        if (io.ep_len) io.ep_len[i] = o.ep_len;
+    }
+    block_accumulate(d, st, before);
+}
+
 template <class E>
 __global__ __launch_bounds__(kBlock) void reset_kernel(DevEnv d, const uint8_t *mask, int has_bounds, double b0, double b1,
                                                        float *obs) {
@@ -1029,6 +1195,74 @@ __global__ __launch_bounds__(kBlock) void rollout_infos_kernel(DevEnv d, Rollout
             hold_opaque(w);
             as.lane[w] = (uint64_t)(astate >> 64), as.lane[(size_t)d.N + w] = (uint64_t)astate;
         }
+    }
+    block_accumulate(d, st);
+}
+
+// mi_set_step_wrappers: the loop of rollout_infos_kernel with lane_step_wrapped as its step, for mi_rollout (ex: all null) and mi_rollout_infos alike.
+// The generator and StickyAction's state stay in registers for the launch; nothing is drawn ahead (lane_step_wrapped), so the generator that goes back
+// to memory is at the reference's position.  actions_out are the policy's actions, not the effective ones.
+template <class E, int MODE, bool SAMPLE>
+__global__ __launch_bounds__(kBlock) void rollout_wrapped_kernel(DevEnv d, RolloutPtrs io, ActionStream as, int T, AttrDev at, RolloutExtra ex, WrapDev w) {
+    tables_init<E>();
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    LaneStats st = {0u, 0u, 0u, 0ull, 0.0};
+    if (i < d.N) {
+        Lane<E> L;
+        load_lane<E>(d, i, L);
+        {
+            AttrRequest<E> ar;
+            ar.request(at, d, i);
+            ar.arrive(L.trig);
+        }
+        u128 astate = 0;
+        if (SAMPLE) {
+            if (as.lane_valid) {  // the lane's state from the last launch (or act_init_kernel)
+                astate = make_u128(as.lane[i], as.lane[(size_t)d.N + i]);
+            } else {  // skip ahead by (i + 1) draws: one affine map per set bit of (i + 1)
+                astate = make_u128(as.state_hi, as.state_lo);
+                uint32_t delta = (uint32_t)i + 1u;
+                for (int j = 0; delta; j++, delta >>= 1)
+                    if (delta & 1u) astate = as.pow2[j].mult * astate + as.pow2[j].plus;
+            }
+        }
+        const size_t N = (size_t)d.N;
+        ResetQueue<E> q;
+        q.have = 0u;
+        q.rng = load_rng(d, i);
+        WrapLane<E> sl;
+        load_wrap_lane(w, i, sl);
+        for (int t = 0; t < T; t++) {
+            typename E::Act a;
+            if (SAMPLE) {
+                a = action_of_state<E>(astate);
+                astate = as.jump_n.mult * astate + as.jump_n.plus;
+                if (io.actions_out) static_cast<typename E::Act *>(io.actions_out)[t * N + i] = a;
+            } else {
+                a = static_cast<const typename E::Act *>(io.actions_in)[t * N + i];
+            }
+            StepOut<E> o;
+            if (MODE == MI_AUTORESET_SAME_STEP) {  // (lane_step_wrapped writes the row only when the episode ended)
+#pragma unroll
+                for (int k = 0; k < E::OBS; k++) o.final_obs[k] = 0.0f;
+            }
+            lane_step_wrapped<E, MODE>(d, w, sl, i, L, a, o, st, &q, nullptr);
+            if (io.obs) store_row<E::OBS>(static_cast<float *>(io.obs) + (t * N + i) * E::OBS, o.obs);
+            if (io.reward) io.reward[t * N + i] = o.reward;
+            if (io.terminated) io.terminated[t * N + i] = o.terminated;
+            if (io.truncated) io.truncated[t * N + i] = o.truncated;
+            if (ex.ep_ret) ex.ep_ret[t * N + i] = o.ep_ret;
+            if (ex.ep_len) ex.ep_len[t * N + i] = o.ep_len;
+            if (MODE == MI_AUTORESET_SAME_STEP && ex.final_obs) store_row<E::OBS>(static_cast<float *>(ex.final_obs) + (t * N + i) * E::OBS, o.final_obs);
+        }
+        store_lane<E>(d, i, L);
+        store_wrap_lane(w, i, sl);
+        if (q.have) {  // (a reset's refill is consumed by that reset: never taken, kept for the invariant)
+#pragma unroll
+            for (int k = 0; k < E::NDRAWS; k++) q.rng.unstep();
+        }
+        store_rng_state(d, i, q.rng);
+        if (SAMPLE && as.lane) as.lane[i] = (uint64_t)(astate >> 64), as.lane[N + i] = (uint64_t)astate;
     }
     block_accumulate(d, st);
 }
@@ -2666,6 +2900,12 @@ __global__ void seed_sequence_kernel(DevEnv d, uint64_t first_seed, const uint8_
 // its next draw; a batch later the lane is N * D draws further on (jump).  Kept on the device, the stream needs nothing from the host between
 // steps: a captured HIP graph replays sampled steps, and a loop of step(sample()) enqueues no host-to-device traffic.
 // ---------------------------------------------------------------------------------------------------------
+// mi_reset with StickyAction on: the rows that reset forget their last action and leave a running series (mi_set_step_wrappers)
+__global__ __launch_bounds__(kBlock) void sticky_clear_kernel(uint32_t *sticky_word, const uint8_t *mask, int N) {
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i < N && (!mask || mask[i])) sticky_word[i] = 0u;
+}
+
 __global__ __launch_bounds__(kBlock) void act_init_kernel(ActionStream as, uint64_t *act_lane, int N, int D) {
     const int i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= N) return;
@@ -2810,6 +3050,12 @@ struct mi_vecenv {
     // come from them.  attr_mask != 0 ("per-lane mode"): step and rollout run the *AttrT kernels (envs_classic.h); a bit, once set, stays set
     double *d_attr;
     uint32_t attr_mask;
+    // mi_set_step_wrappers: RepeatAction / StickyAction of the sub-environments inside the step.  wrap_on: the *_wrapped_kernel entry points run, with
+    // `wrap` as their last argument (its two arrays are allocated by the first call that switches StickyAction on).  per_lane: some call has switched
+    // them on -- from then on the env stays on the per-lane types (envs_classic.h *AttrT) and their one-role kernels, as after mi_set_env_attr.
+    WrapDev wrap;
+    bool wrap_on, per_lane;
+    int wrap_act_kind;  // StickyAction: the element type of the action rows it has seen (last_action is kept in that type); -1: none yet
     // sample(mask=...) / sample(probability=...) on the action stream (action_mask.hip): the pending 32-bit half and the words of the batch in flight,
     // the per-workgroup counts, the per-row slots; d_arg_stage: where a host caller's masks / probabilities are staged (MI_HOST only)
     mi_actmask::Ctl *d_act_ctl;
@@ -2959,9 +3205,30 @@ void launch_step_mode(mi_vecenv *v, const StepPtrs &p) {
     default: hipLaunchKernelGGL((step_kernel<E, MI_AUTORESET_DISABLED, EPI, SAMPLE>), g, b, 0, v->stream, v->d, p, v->epi, at); break;
     }
 }
+template <class E, bool SAMPLE>
+void launch_step_wrapped_mode(mi_vecenv *v, const StepPtrs &p) {
+    const dim3 g(v->grid), b(kBlock);
+    const AttrDev at = {v->d_attr, v->attr_mask};
+    switch (v->cfg.autoreset_mode) {
+    case MI_AUTORESET_NEXT_STEP: hipLaunchKernelGGL((step_wrapped_kernel<E, MI_AUTORESET_NEXT_STEP, SAMPLE>), g, b, 0, v->stream, v->d, p, at, v->wrap); break;
+    case MI_AUTORESET_SAME_STEP: hipLaunchKernelGGL((step_wrapped_kernel<E, MI_AUTORESET_SAME_STEP, SAMPLE>), g, b, 0, v->stream, v->d, p, at, v->wrap); break;
+    default: hipLaunchKernelGGL((step_wrapped_kernel<E, MI_AUTORESET_DISABLED, SAMPLE>), g, b, 0, v->stream, v->d, p, at, v->wrap); break;
+    }
+}
 template <class E>
 int launch_step(mi_vecenv *v, const StepPtrs &p) {
-    if (!v->has_epi) {
+    if (v->wrap_on) {  // (mi_set_step_wrappers and mi_set_step_epilogue refuse each other; the env is on the per-lane types: the others have no such kernels)
+        if constexpr (!HasAttrs<E>::value) {
+            return fail(MI_ERR_STATE, "mi_set_step_wrappers: the wrapped kernels exist for the per-lane types");
+        } else if constexpr (E::ACT_KIND == MI_F32 || E::ACT_KIND == MI_I64) {
+            if (p.act_lane)
+                launch_step_wrapped_mode<E, true>(v, p);
+            else
+                launch_step_wrapped_mode<E, false>(v, p);
+        } else {
+            launch_step_wrapped_mode<E, false>(v, p);
+        }
+    } else if (!v->has_epi) {
         // the on-device policy draws the space's own dtype (float32 rows / int64): the float64-row instantiations never sample (the caller, step_enqueue,
         // sends a wrapped step that samples through the stand-alone sampler + this kernel with p.actions set instead)
         if constexpr (E::ACT_KIND == MI_F32 || E::ACT_KIND == MI_I64) {
@@ -2987,6 +3254,28 @@ int launch_step(mi_vecenv *v, const StepPtrs &p) {
     return MI_OK;
 }
 
+// mi_rollout / mi_rollout_infos with mi_set_step_wrappers on: one kernel stores whatever is asked for
+template <class E>
+int launch_rollout_wrapped(mi_vecenv *v, const RolloutPtrs &p, const RolloutExtra &ex, const ActionStream &as, int T, bool sample) {
+    const bool next_step = v->cfg.autoreset_mode == MI_AUTORESET_NEXT_STEP;
+    const AttrDev at = {v->d_attr, v->attr_mask};
+    const dim3 g(v->grid), b(kBlock);
+    constexpr bool F64 = E::ACT_KIND == MI_F64 || E::ACT_KIND == MI_F64_WEAK;  // float64 action rows are always the caller's (the sampler draws float32)
+    if (F64 && sample) return fail(MI_ERR_INVALID_ARGUMENT, "the on-device policy samples float32 actions");
+    if constexpr (!HasAttrs<E>::value) {  // (the env is on the per-lane types once the wrappers were on: the others have no such kernels)
+        return fail(MI_ERR_STATE, "mi_set_step_wrappers: the wrapped kernels exist for the per-lane types");
+    } else {
+    if constexpr (!F64) {
+        if (sample && next_step) hipLaunchKernelGGL((rollout_wrapped_kernel<E, MI_AUTORESET_NEXT_STEP, true>), g, b, 0, v->stream, v->d, p, as, T, at, ex, v->wrap);
+        if (sample && !next_step) hipLaunchKernelGGL((rollout_wrapped_kernel<E, MI_AUTORESET_SAME_STEP, true>), g, b, 0, v->stream, v->d, p, as, T, at, ex, v->wrap);
+    }
+    if (!sample && next_step) hipLaunchKernelGGL((rollout_wrapped_kernel<E, MI_AUTORESET_NEXT_STEP, false>), g, b, 0, v->stream, v->d, p, as, T, at, ex, v->wrap);
+    if (!sample && !next_step) hipLaunchKernelGGL((rollout_wrapped_kernel<E, MI_AUTORESET_SAME_STEP, false>), g, b, 0, v->stream, v->d, p, as, T, at, ex, v->wrap);
+    HIP_TRY(hipGetLastError());
+    return MI_OK;
+    }
+}
+
 template <class E, int MODE, bool SAMPLE, bool FULL>
 void launch_rollout_variant(mi_vecenv *v, const RolloutPtrs &p, const ActionStream &as, int T) {
     const AttrDev at = {v->d_attr, v->attr_mask};
@@ -2997,6 +3286,7 @@ template <class E>
 int launch_rollout(mi_vecenv *v, const RolloutPtrs &p, const ActionStream &as, int T, bool sample) {
     const bool next_step = v->cfg.autoreset_mode == MI_AUTORESET_NEXT_STEP;
     const bool full = p.obs && p.reward && p.terminated && p.truncated && (!sample || p.actions_out);
+    if (v->wrap_on) return launch_rollout_wrapped<E>(v, p, RolloutExtra{}, as, T, sample);
     if constexpr (E::ACT_KIND == MI_F64 || E::ACT_KIND == MI_F64_WEAK) {  // float64 action rows are always the caller's (the sampler draws float32)
         if (sample) return fail(MI_ERR_INVALID_ARGUMENT, "the on-device policy samples float32 actions");
         if (next_step)
@@ -3029,6 +3319,7 @@ int launch_rollout_infos(mi_vecenv *v, const RolloutPtrs &p, const RolloutExtra 
     const bool next_step = v->cfg.autoreset_mode == MI_AUTORESET_NEXT_STEP;
     const AttrDev at = {v->d_attr, v->attr_mask};
     const dim3 g(v->grid), b(kBlock);
+    if (v->wrap_on) return launch_rollout_wrapped<E>(v, p, ex, as, T, sample);
     if constexpr (E::ACT_KIND == MI_F64 || E::ACT_KIND == MI_F64_WEAK) {
         if (sample) return fail(MI_ERR_INVALID_ARGUMENT, "the on-device policy samples float32 actions");
         if (next_step)
@@ -3053,7 +3344,7 @@ int launch_rollout_infos(mi_vecenv *v, const RolloutPtrs &p, const RolloutExtra 
 // ---- the launchers the other translation unit calls (this unit is compiled with the max-ILP scheduler, see the head of the file) ----------------
 namespace mi_classic {
 int step(mi_vecenv *v, const StepPtrs &p, int act_kind) {
-    if (v->attr_mask) return dispatch_kind_attr(v->cfg.kind, act_kind, [&](auto env) -> int { return launch_step<decltype(env)>(v, p); });
+    if (v->attr_mask || v->per_lane) return dispatch_kind_attr(v->cfg.kind, act_kind, [&](auto env) -> int { return launch_step<decltype(env)>(v, p); });
     return dispatch_kind_act(v->cfg.kind, (v->cfg.reserved[0] & MI_CFG_FAST_MATH) != 0, act_kind, [&](auto env) -> int { return launch_step<decltype(env)>(v, p); });
 }
 int reset(mi_vecenv *v, const uint8_t *dm, int has_bounds, double b0, double b1, float *dobs) {
@@ -3065,11 +3356,11 @@ int reset(mi_vecenv *v, const uint8_t *dm, int has_bounds, double b0, double b1,
     });
 }
 int rollout(mi_vecenv *v, const RolloutPtrs &p, const ActionStream &as, int T, bool sample, int in_kind) {
-    if (v->attr_mask) return dispatch_kind_attr(v->cfg.kind, in_kind, [&](auto env) -> int { return launch_rollout<decltype(env)>(v, p, as, T, sample); });
+    if (v->attr_mask || v->per_lane) return dispatch_kind_attr(v->cfg.kind, in_kind, [&](auto env) -> int { return launch_rollout<decltype(env)>(v, p, as, T, sample); });
     return dispatch_kind_act(v->cfg.kind, (v->cfg.reserved[0] & MI_CFG_FAST_MATH) != 0, in_kind, [&](auto env) -> int { return launch_rollout<decltype(env)>(v, p, as, T, sample); });
 }
 int rollout_infos(mi_vecenv *v, const RolloutPtrs &p, const RolloutExtra &ex, const ActionStream &as, int T, bool sample, int in_kind) {
-    if (v->attr_mask) return dispatch_kind_attr(v->cfg.kind, in_kind, [&](auto env) -> int { return launch_rollout_infos<decltype(env)>(v, p, ex, as, T, sample); });
+    if (v->attr_mask || v->per_lane) return dispatch_kind_attr(v->cfg.kind, in_kind, [&](auto env) -> int { return launch_rollout_infos<decltype(env)>(v, p, ex, as, T, sample); });
     return dispatch_kind_act(v->cfg.kind, (v->cfg.reserved[0] & MI_CFG_FAST_MATH) != 0, in_kind, [&](auto env) -> int { return launch_rollout_infos<decltype(env)>(v, p, ex, as, T, sample); });
 }
 // ---- MI_CFG_SHARED_RNG: MI_ENV_CARTPOLE only (mi_create refuses the bit for every other kind) ---------------------------------------------
@@ -3412,7 +3703,7 @@ void mi_destroy(mi_vecenv *v) {
     (void)hipStreamSynchronize(v->stream);
     void *ptrs[] = {v->d.state, v->d.meta, v->d.rng, v->d.ep_ret, v->d.ep_len, v->d.blk_count, v->d.blk_ret, v->d_out,
                     v->d_pow2, v->d_act_lane, v->d_act_stage, v->d_actions, v->d_mask, v->d_words, v->d_extras, v->d_act_scratch, v->d_obs_scratch,
-                    v->shared.words, v->d_shared_pow2, v->shared.blk_done, v->shared.blk_prefix, v->d_attr,
+                    v->shared.words, v->d_shared_pow2, v->shared.blk_done, v->shared.blk_prefix, v->d_attr, v->wrap.last_action, v->wrap.sticky_word,
                     v->d_act_ctl, v->d_act_partial, v->d_act_slot, v->d_arg_stage};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
@@ -3504,9 +3795,38 @@ int mi_get_env_attr(mi_vecenv *v, int attr, double *host_out) {
     return MI_OK;
 }
 
+// RepeatAction / StickyAction of the sub-environments (include/mi355env.h mi_set_step_wrappers; device side: lane_step_wrapped).
+int mi_set_step_wrappers(mi_vecenv *v, int num_repeats, double sticky_probability, int sticky_duration) {
+    if (!v) return fail(MI_ERR_INVALID_ARGUMENT, "null env");
+    if (v->cfg.kind < 0 || v->cfg.kind >= kClassicKinds) return fail(MI_ERR_UNSUPPORTED, "mi_set_step_wrappers: the five classic-control kinds only");
+    if (v->shared_rng) return fail(MI_ERR_UNSUPPORTED, "mi_set_step_wrappers: not with MI_CFG_SHARED_RNG (CartPoleVectorEnv has no sub-environments to wrap)");
+    if (v->cfg.reserved[0] & MI_CFG_FAST_MATH) return fail(MI_ERR_UNSUPPORTED, "mi_set_step_wrappers: not with MI_CFG_FAST_MATH");
+    if (v->has_epi) return fail(MI_ERR_UNSUPPORTED, "mi_set_step_wrappers: not with a step epilogue attached (mi_set_step_epilogue)");
+    if (v->has_pending) return fail(MI_ERR_STATE, "an asynchronous step is pending (mi_step_wait)");
+    if (num_repeats < 0 || sticky_duration < 0 || sticky_duration >= (1 << 30))
+        return fail(MI_ERR_INVALID_ARGUMENT, "mi_set_step_wrappers: num_repeats and sticky_duration must be >= 0 (0: no such wrapper)");
+    if (sticky_duration && !(sticky_probability >= 0.0 && sticky_probability < 1.0))
+        return fail(MI_ERR_INVALID_ARGUMENT, "mi_set_step_wrappers: sticky_probability must be in [0, 1)");
+    if (set_device(v)) return MI_ERR_HIP;
+    const size_t N = (size_t)v->cfg.num_envs;
+    if (sticky_duration) {
+        if (!v->wrap.last_action) HIP_TRY(hipMalloc(&v->wrap.last_action, sizeof(uint64_t) * N));
+        if (!v->wrap.sticky_word) HIP_TRY(hipMalloc(&v->wrap.sticky_word, sizeof(uint32_t) * N));
+        // a newly constructed StickyAction: last_action None, not stuck
+        HIP_TRY(hipMemsetAsync(v->wrap.last_action, 0, sizeof(uint64_t) * N, v->stream));
+        HIP_TRY(hipMemsetAsync(v->wrap.sticky_word, 0, sizeof(uint32_t) * N, v->stream));
+    }
+    v->wrap.repeats = num_repeats, v->wrap.sticky_duration = sticky_duration, v->wrap.sticky_p = sticky_duration ? sticky_probability : 0.0;
+    v->wrap_on = num_repeats > 0 || sticky_duration > 0;
+    v->wrap_act_kind = -1;
+    if (v->wrap_on) v->per_lane = true;
+    return MI_OK;
+}
+
 // The reference's stateful vector wrappers as the output stage of the classic-control step kernel (include/mi355env.h mi_step_epilogue).
 int mi_set_step_epilogue(mi_vecenv *v, const mi_step_epilogue *e) {
     if (!v) return fail(MI_ERR_INVALID_ARGUMENT, "null env");
+    if (v->wrap_on && e) return fail(MI_ERR_UNSUPPORTED, "mi_set_step_epilogue: not with mi_set_step_wrappers on (use the mi_normalize_* passes)");
     if (v->shared_rng && e) return fail(MI_ERR_UNSUPPORTED, "MI_CFG_SHARED_RNG: the step epilogue belongs to the per-sub-environment step kernel");
     if (set_device(v)) return MI_ERR_HIP;
     HIP_TRY(hipStreamSynchronize(v->stream));
@@ -3690,6 +4010,10 @@ int mi_reset(mi_vecenv *v, const uint8_t *mask, const double *bounds, void *obs,
         rc = mi_classic::shared_reset(v, (float *)dobs);
     }
     if (rc) return rc;
+    if (v->wrap_on && v->wrap.sticky_duration) {  // StickyAction.reset (stateful_action.py:107-116) of the rows that reset
+        hipLaunchKernelGGL(sticky_clear_kernel, dim3(v->grid), dim3(kBlock), 0, v->stream, v->wrap.sticky_word, dm, v->cfg.num_envs);
+        HIP_TRY(hipGetLastError());
+    }
     v->was_reset = true;
     if (loc == MI_HOST) {
         if (obs && !pinned_obs) HIP_TRY(hipMemcpyAsync(obs, v->d_obs, v->obs_bytes, hipMemcpyDeviceToHost, v->stream));
@@ -3778,6 +4102,16 @@ static int action_sample_device(mi_vecenv *v, int T, void *dst) {
     return MI_OK;
 }
 
+// StickyAction keeps each lane's last action in the element type it came in (WrapDev::last_action): a batch of another type would replay those bits
+// as a value of its own type, so it is refused until the wrappers are set again.
+static int sticky_action_kind(mi_vecenv *v, int act_kind) {
+    if (!v->wrap_on || !v->wrap.sticky_duration) return MI_OK;
+    if (v->wrap_act_kind >= 0 && v->wrap_act_kind != act_kind)
+        return fail(MI_ERR_UNSUPPORTED, "StickyAction is on: the element type of the action rows (float32 / float64 / Python floats) must not change between steps");
+    v->wrap_act_kind = act_kind;
+    return MI_OK;
+}
+
 // Enqueue one vector step.  loc == MI_HOST: actions go through the pinned staging block (one H2D), the kernel writes the device output
 // block, and ONE D2H brings back the prefix of it that the caller asked for -- or, for the classic kinds, the kernel works on the pinned block
 // directly and there is no copy at all; nothing is synchronised here.
@@ -3799,6 +4133,7 @@ static int step_enqueue(mi_vecenv *v, const mi_step_io *io, int loc) {
     if (box && io->actions_dtype != MI_F32 && io->actions_dtype != MI_F64 && io->actions_dtype != MI_F64_WEAK)
         return fail(MI_ERR_INVALID_ARGUMENT, "actions_dtype must be MI_F32, MI_F64 or MI_F64_WEAK");
     const int act_kind = (box && !sample) ? io->actions_dtype : (int)MI_F32;
+    if (int rc = sticky_action_kind(v, act_kind)) return rc;
     const size_t act_bytes = act_kind == MI_F32 ? v->act_bytes : v->act_bytes_max;
     StepPtrs p;
     memset(&p, 0, sizeof p);
@@ -4031,6 +4366,7 @@ static int rollout_impl(mi_vecenv *v, int T, const mi_rollout_io *io, const Roll
         return fail(MI_ERR_INVALID_ARGUMENT, "actions_in_dtype must be MI_F32, MI_F64 or MI_F64_WEAK");
     const int in_kind = (box && !sample) ? io->actions_in_dtype : (int)MI_F32, in_f64 = in_kind != MI_F32;
     if (in_f64 && io->actions_out) return fail(MI_ERR_INVALID_ARGUMENT, "actions_out echoes float32 rows: not with float64 actions_in");
+    if (int rc = sticky_action_kind(v, in_kind)) return rc;
     ActionStream as;
     memset(&as, 0, sizeof as);
     if (sample) {

@@ -45,6 +45,10 @@ class InvalidBound(Error):
     """Raised when the clipping an array with invalid upper and/or lower bound (gymnasium/error.py:62-63)."""
 
 
+class InvalidProbability(Error):
+    """Raised when a probability argument is outside its interval (gymnasium/error.py: StickyAction's repeat_action_probability)."""
+
+
 class AlreadyPendingCallError(Exception):
     """gymnasium/error.py:72-80: an asynchronous call (`step_async`) is outstanding and another call is made before its `step_wait`."""
 

@@ -96,7 +96,7 @@ class HipVectorEnv(VectorEnv):
 
     def _can_fuse(self) -> bool:
         return (self.FUSES_WRAPPERS and self._engine_factory is None and hasattr(self._engine.lib, "set_step_epilogue")
-                and not self._fusion_state()["closed"])
+                and not self._fusion_state()["closed"] and self._step_wrappers == (0, 0.0, 0))
 
     def _fuse(self, wrapper, slot: str) -> int:
         """Register ``wrapper`` as the next member of the fused unit; returns its position in the chain."""
@@ -506,6 +506,8 @@ class HipVectorEnv(VectorEnv):
             except _native.NativeError as e:
                 if e.code in (-1, -5):
                     raise AssertionError(e.message) from e
+                if e.code == -4:  # MI_ERR_UNSUPPORTED: StickyAction is on and the element type of the action rows changed
+                    raise error.Error(e.message) from e
                 raise
             if self.copy:
                 return self._obs.clone(), self._rew.clone(), self._term.clone(), self._trunc.clone(), {}
@@ -545,6 +547,8 @@ class HipVectorEnv(VectorEnv):
                 raise AssertionError(e.message) from e
             if e.code == -5:
                 raise AssertionError(e.message) from e
+            if e.code == -4:  # MI_ERR_UNSUPPORTED: StickyAction is on and the element type of the action rows changed
+                raise error.Error(e.message) from e
             raise
         del keep
         infos = self._build_infos()
@@ -1083,6 +1087,36 @@ class HipVectorEnv(VectorEnv):
         self.__dict__.setdefault("_env_attr_values", {})[name] = stored
         self._env_attr_mask = self._env_attr_mask | (1 << k)
 
+    # -- RepeatAction / StickyAction of the sub-environments (gymnasium_amd.wrappers.RepeatAction / StickyAction; mi_set_step_wrappers) ------
+    _step_wrappers = (0, 0.0, 0)  # (num_repeats, sticky probability, sticky duration) the engine runs; 0 = no such wrapper
+
+    def _step_wrappers_refusal(self) -> str | None:
+        if self.KIND not in ("cartpole", "pendulum", "acrobot", "mountain_car", "mountain_car_continuous"):
+            return (f"{type(self).__name__}: RepeatAction / StickyAction of the sub-environments exist for CartPole-v1, Pendulum-v1, Acrobot-v1, "
+                    "MountainCar-v0 and MountainCarContinuous-v0 only (the MuJoCo and ToyText kernels have no such step)")
+        if getattr(self, "_shared_rng", False):
+            return "rng='shared' is the reference's NumPy CartPoleVectorEnv: it has no sub-environments that a scalar wrapper could wrap"
+        if getattr(self, "fast_math", False):
+            return "RepeatAction / StickyAction of the sub-environments run the exact kernels only: not with fast_math=True"
+        st = self.__dict__.get("_fused")
+        if st is not None and st["chain"]:
+            return "vector wrappers are already fused into this env's step kernel: RepeatAction / StickyAction go directly over the env, the vector wrappers above them"
+        if not hasattr(getattr(self._engine, "lib", None), "set_step_wrappers"):
+            return "the engine behind this env has no per-sub-environment action wrappers (mi_set_step_wrappers)"
+        return None
+
+    def set_step_wrappers(self, num_repeats: int = 0, sticky_probability: float = 0.0, sticky_duration: int = 0) -> None:
+        """What ``wrappers.RepeatAction`` / ``wrappers.StickyAction`` switch on: every sub-environment steps as if it were wrapped in
+        ``RepeatAction(env, num_repeats)`` and, outside it, ``StickyAction(env, sticky_probability, sticky_duration)`` (0: no such wrapper; all
+        three 0: the plain step again).  Each call constructs the wrappers anew: no sub-environment has a last action."""
+        self._check_open()
+        self._check_not_pending("set_step_wrappers")
+        refusal = self._step_wrappers_refusal()
+        if refusal:
+            raise error.Error(refusal)
+        self._engine.set_step_wrappers(num_repeats, sticky_probability, sticky_duration)
+        self._step_wrappers = (int(num_repeats), float(sticky_probability), int(sticky_duration))
+
     # -- bookkeeping -----------------------------------------------------------------------------------
     def statistics(self) -> dict:
         """Running totals kept on device: env_steps, reset_steps, episodes, return_sum, length_sum."""
@@ -1169,6 +1203,7 @@ class GraphedSteps:
                                  "the action space's dtype (int64, or float32 / float64 rows for Box spaces)")
         self.env, self.steps, self.actions, self.policy = env, steps, actions, policy
         self.attr_mask = env._env_attr_mask  # which kernels the graph holds (per-lane attributes: set_attr)
+        self.step_wrappers = env._step_wrappers  # ... and whose parameters they carry (RepeatAction / StickyAction: set_step_wrappers)
         self._capture()
 
     def _prepare_capture(self):
@@ -1212,6 +1247,9 @@ class GraphedSteps:
         if env._env_attr_mask != self.attr_mask:
             raise error.Error("set_attr() has made the env read per-sub-environment attributes since this graph was captured; its kernels do not "
                               "read them: capture the steps again")
+        if env._step_wrappers != getattr(self, "step_wrappers", env._step_wrappers):
+            raise error.Error("RepeatAction / StickyAction of the sub-environments were switched since this graph was captured; its kernels carry the "
+                              "old setting: capture the steps again")
         env._bind_stream()  # statistics() / synchronize() wait on the engine's stream: keep it the one the replay runs on
         if self.policy == "random":
             space = env.action_space

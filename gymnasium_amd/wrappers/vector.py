@@ -267,6 +267,82 @@ class RecordEpisodeStatistics(VectorWrapper):
         return out
 
 
+# -- the reference's per-sub-environment action wrappers (gymnasium/wrappers/stateful_action.py), run by the engine's step itself ---------------------
+_InvalidProbability = getattr(error, "InvalidProbability", error.Error)
+_InvalidBound = getattr(error, "InvalidBound", error.Error)
+
+
+def _bare_env(env, what):
+    """``env`` if it is a HipVectorEnv with nothing around it; error.Error otherwise."""
+    if isinstance(env, VectorWrapper) or not hasattr(env, "set_step_wrappers"):
+        raise error.Error(f"{what} wraps every SUB-environment, below the vector level: it goes directly over the classic-control HipVectorEnv "
+                          f"(gymnasium_amd.make_vec(...)), and the vector wrappers go above it; got {type(env).__name__}")
+    return env
+
+
+class RepeatAction(VectorWrapper):
+    """``SyncVectorEnv`` over scalar envs each wrapped in ``gymnasium.wrappers.RepeatAction(env, num_repeats)`` (stateful_action.py:145-220; the
+    reference has no vector version): a ``step()`` runs up to ``num_repeats`` inner steps of every sub-environment with the same action IN ONE
+    LAUNCH -- a sub-environment stops after the inner step that terminates or truncates it (TimeLimit counts inner steps) while its neighbours
+    go on --, returns the last inner observation and ``0.0 + r1 + r2 ...``.  Episode statistics count what the vector level sees: one step
+    per ``step()``.  The NEXT_STEP autoreset step repeats nothing.  Goes directly over the env of the five classic-control ids;
+    ``StickyAction`` may go over it, every vector wrapper goes above both.  ``step``, ``step(None)``, ``rollout`` and ``capture_steps`` all follow."""
+
+    def __init__(self, env, num_repeats: int):
+        if not np.issubdtype(type(num_repeats), np.integer):
+            raise TypeError(f"The num_repeats is expected to be an integer, actual type: {type(num_repeats)}")
+        if num_repeats < 1:
+            raise ValueError(f"The num_repeats value needs to be equal or greater than one, actual value: {num_repeats}")
+        base = _bare_env(env, "RepeatAction")
+        if base._step_wrappers != (0, 0.0, 0):
+            raise error.Error("this env already runs RepeatAction / StickyAction: switch them off first (env.set_step_wrappers())")
+        super().__init__(env)
+        base.set_step_wrappers(int(num_repeats), 0.0, 0)
+        _close_fusion(env)
+        self.num_repeats = num_repeats
+
+
+class StickyAction(VectorWrapper):
+    """``SyncVectorEnv`` over scalar envs each wrapped in ``gymnasium.wrappers.StickyAction(env, repeat_action_probability,
+    repeat_action_duration)`` (stateful_action.py:16-142, Machado et al. 2018; the reference has no vector version).  Before a step, a
+    sub-environment that has a last action and is not inside a series draws ``np_random.uniform()`` from ITS OWN generator (the one its resets
+    consume: ``get_rng_state()`` shows it) and with that probability repeats its last action for ``repeat_action_duration`` steps; every reset
+    of a sub-environment clears its state.  Goes directly over the env of the five classic-control ids or over ``RepeatAction`` (one decision per
+    outer step); every vector wrapper goes above.  Two deliberate differences: actions are validated as given (the reference never looks at an
+    action that a sticky one replaces), and the element type of the action batch (float32 / float64 rows) must not change between steps.
+    ``repeat_action_duration`` is an int: a (low, high) range is drawn by ``Generator.integers`` from PCG64's buffered 32-bit half, which the
+    sub-environments' generators on the device do not carry -- refused, not approximated."""
+
+    def __init__(self, env, repeat_action_probability: float, repeat_action_duration=1):
+        if not 0 <= repeat_action_probability < 1:
+            raise _InvalidProbability(f"`repeat_action_probability` should be in the interval [0,1). Received {repeat_action_probability}")
+        rng = (repeat_action_duration, repeat_action_duration) if isinstance(repeat_action_duration, int) else repeat_action_duration
+        if not isinstance(rng, tuple):
+            raise ValueError(f"`repeat_action_duration` should be either an integer or a tuple. Received {rng}")
+        if len(rng) != 2:
+            raise ValueError(f"`repeat_action_duration` should be a tuple or a list of two integers. Received {rng}")
+        if rng[0] > rng[1]:
+            raise _InvalidBound(f"`repeat_action_duration` is not a valid bound. Received {rng}")
+        if np.any(np.array(rng) < 1):
+            raise ValueError(f"`repeat_action_duration` should be larger or equal than 1. Received {rng}")
+        if rng[0] != rng[1]:
+            raise error.Error(f"`repeat_action_duration` = {rng}: a range is drawn with Generator.integers, which takes PCG64's buffered 32-bit half; the "
+                              "sub-environments' generators on the device do not carry that half, so only an int duration is supported")
+        inner = env
+        repeats = 0
+        if isinstance(env, RepeatAction):
+            inner, repeats = env.env, int(env.num_repeats)
+        base = _bare_env(inner, "StickyAction")
+        if base._step_wrappers != (repeats, 0.0, 0):
+            raise error.Error("this env already runs StickyAction (RepeatAction goes UNDER StickyAction, never over it): switch them off first "
+                              "(env.set_step_wrappers())")
+        super().__init__(env)
+        base.set_step_wrappers(repeats, float(repeat_action_probability), int(rng[0]))
+        _close_fusion(env)
+        self.repeat_action_probability = repeat_action_probability
+        self.repeat_action_duration_range = rng
+
+
 class NumpyToTorch(VectorWrapper):
     """gymnasium.wrappers.vector.NumpyToTorch (wrappers/vector/numpy_to_torch.py:16-53) without the conversion: the wrapped HipVectorEnv is
     switched to ``output="torch"``, so observations, rewards and flags ARE torch tensors the engine wrote in HBM (zero copy; the reference

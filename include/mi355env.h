@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-/* Entry points that were only ADDED since (mi_action_sample_masked and its three companions) leave the number where it is: nothing an ABI 10
+/* Entry points that were only ADDED since (mi_action_sample_masked and its three companions, mi_set_step_wrappers) leave the number where it is: nothing an ABI 10
  * caller uses changed, and a caller that needs them finds out by looking the symbol up. */
 #define MI355ENV_ABI_VERSION 10
 
@@ -436,6 +436,32 @@ enum {
 };
 int mi_set_env_attr(mi_vecenv *env, int attr, const double *values, int on_device);
 int mi_get_env_attr(mi_vecenv *env, int attr, double *host_out);
+
+/*
+ * The per-sub-environment action wrappers (added to ABI 10, which it leaves as it is): gymnasium.wrappers.RepeatAction and StickyAction
+ * (wrappers/stateful_action.py:16-220) around every scalar env, outside its TimeLimit -- what
+ * make_vec(id, n, "sync", wrappers=(lambda e: StickyAction(RepeatAction(e, k), p, d),)) builds -- for the five classic-control kinds (not with
+ * MI_CFG_SHARED_RNG or MI_CFG_FAST_MATH, not with a step epilogue attached).  They live below the vector level, so the engine steps each lane
+ * differently; mi_step, mi_rollout and mi_rollout_infos all follow, in one launch as before.
+ *   num_repeats >= 1: RepeatAction(env, num_repeats).  A step runs up to num_repeats inner steps with the same action and stops after the first that
+ *     terminates or truncates; reward = 0.0 + r_1 + r_2 ... in that order; obs (and final_obs under SAME_STEP) is the last inner step's; TimeLimit
+ *     counts INNER steps.  The NEXT_STEP autoreset step repeats nothing.  episode_return / episode_length and mi_stats count what the vector level
+ *     sees: one step per call (utils/performance.py:88-90) and the sum of the summed rewards.  0: no such wrapper.
+ *   sticky_duration >= 1: StickyAction(env, sticky_probability, sticky_duration) OUTSIDE the RepeatAction: one decision per call.  A lane that has a
+ *     last action and is not inside a series takes ONE float64 draw u from its own generator (the one its resets consume; mi_get_rng shows it
+ *     moved) BEFORE the step and any draw of the step itself (ACROBOT's torque noise), and starts a series if u < sticky_probability; inside a
+ *     series nothing is drawn.  The effective action -- the last one while a series lasts -- becomes the last action.  Every reset of a row (mi_reset
+ *     with or without mask, the NEXT_STEP autoreset step, the SAME_STEP reset) clears its state, so the first step after a reset draws nothing.  A
+ *     (low, high) duration range is not offered: Generator.integers takes PCG64's buffered 32-bit half, which these lanes do not carry.  0: no such
+ *     wrapper (sticky_probability is then ignored; 0.0 with a duration still draws).
+ *   (0, any, 0) switches both off; num_repeats 1 without StickyAction differs from that only in `0.0 + reward` (a reward of -0.0 becomes 0.0).
+ * Every call (re)constructs the wrappers: the sticky state of all rows is cleared.  The first call that switches one on moves the env to the
+ * per-lane kernels for good (as mi_set_env_attr does); the state lives in device memory, allocated by that call: mi_step stays capturable.
+ * mi_get_state / mi_set_state do not carry it.  Actions are validated as given (stricter than the reference, which never sees an action that a
+ * sticky one replaces); mi_rollout's actions_out are the policy's actions, not the effective ones.  With StickyAction on, the element type of the
+ * action rows (mi_step_io.actions_dtype) must not change from call to call: MI_ERR_UNSUPPORTED.
+ */
+int mi_set_step_wrappers(mi_vecenv *env, int num_repeats, double sticky_probability, int sticky_duration);
 
 /*
  * Stateful vector wrappers as device epilogues of the step path.  All array arguments are DEVICE
