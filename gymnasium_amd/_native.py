@@ -61,6 +61,8 @@ TRANSFORM_CLIP, TRANSFORM_AFFINE_INVERSE, TRANSFORM_MAX_ACT_DIM = 0, 1, 32  # MI
 WRAPPER_SYMBOLS += ["transform_observations", "one_hot"]
 MI_F16, MI_I32, MI_U8 = 4, 5, 6  # mi_dtype: targets of transform_observations(OBS_CAST) only
 OBS_AFFINE, OBS_CAST, OBS_MAX_DIM, ONE_HOT_MAX_PARTS = 0, 1, 1024, 4  # MI_OBS_*, MI_ONE_HOT_MAX_PARTS
+# NormalizeObservation / NormalizeReward around every scalar env: per-sub-environment statistics (csrc/per_env_normalize.hip; added to ABI 10 as well).
+WRAPPER_SYMBOLS += ["per_env_normalize_step", "per_env_normalize_steps"]
 
 
 class MiConfig(C.Structure):
@@ -103,6 +105,14 @@ class MiStepEpilogue(C.Structure):
                 ("return_rms", C.c_void_p), ("accumulated", C.c_void_p), ("prev_done", C.c_void_p), ("gamma", C.c_double),
                 ("reward_epsilon", C.c_double), ("clip_pre", C.c_int32), ("clip_post", C.c_int32), ("clip_pre_min", C.c_double),
                 ("clip_pre_max", C.c_double), ("clip_post_min", C.c_double), ("clip_post_max", C.c_double)]
+
+
+class MiPerEnvState(C.Structure):
+    """mi_per_env_state: the device arrays and settings of wrappers.per_env.NormalizeObservation / NormalizeReward (include/mi355env.h)."""
+    _fields_ = [("obs_mean", C.c_void_p), ("obs_var", C.c_void_p), ("obs_count", C.c_void_p), ("obs_first", C.c_void_p), ("obs_phase", C.c_int32),
+                ("obs_dtype", C.c_int32), ("obs_dim", C.c_int32), ("obs_update", C.c_int32), ("obs_epsilon", C.c_double), ("acc", C.c_void_p),
+                ("ret_mean", C.c_void_p), ("ret_var", C.c_void_p), ("ret_count", C.c_void_p), ("was_done", C.c_void_p), ("gamma", C.c_double),
+                ("reward_epsilon", C.c_double), ("reward_update", C.c_int32), ("autoreset_mode", C.c_int32)]
 
 
 class MiStats(C.Structure):
@@ -173,6 +183,8 @@ class NativeLib:
             self.transform_actions = f("transform_actions", [i32, vp, vp, i32, vp, i32, C.c_int64, i32, i32, vp, vp], i32)
             self.transform_observations = f("transform_observations", [i32, vp, vp, i32, vp, i32, C.c_int64, i32, i32, vp, vp], i32)
             self.one_hot = f("one_hot", [i32, vp, C.POINTER(vp), i32, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int64, vp], i32)
+            self.per_env_normalize_step = f("per_env_normalize_step", [i32, vp, C.POINTER(MiPerEnvState), i32] + [vp] * 11, i32)
+            self.per_env_normalize_steps = f("per_env_normalize_steps", [i32, vp, C.POINTER(MiPerEnvState), i32, i32] + [vp] * 6, i32)
             self.step_async = f("step_async", [vp, C.POINTER(MiStepIO)], i32)
             self.step_wait = f("step_wait", [vp], i32)
             self.host_buffers = f("host_buffers", [vp, C.POINTER(MiStepIO)], i32)

@@ -27,6 +27,9 @@ SOURCES = {  # translation unit -> the headers it depends on
     "action_wrappers.hip": [os.path.join("..", "..", "include", "mi355env.h")],
     # RescaleObservation / DtypeObservation / FlattenObservation over an observation block in HBM (mi_transform_observations, mi_one_hot): default flag set
     "observation_wrappers.hip": [os.path.join("..", "..", "include", "mi355env.h")],
+    # NormalizeObservation / NormalizeReward around every scalar env (mi_per_env_normalize_step / _steps): per-lane recurrences, default flag set --
+    # bit parity rests on -ffp-contract=off and on hipcc's default correctly rounded float32 division and sqrtf
+    "per_env_normalize.hip": ["per_env_normalize_internal.h", os.path.join("..", "..", "include", "mi355env.h")],
 }
 OUT = os.path.join(HERE, "libmi355env.so")
 ARCH = "gfx950"

@@ -565,6 +565,57 @@ int mi_transform_observations(int device, void *hip_stream, const void *in, int 
 int mi_one_hot(int device, void *hip_stream, const int64_t *const *parts, int num_parts, const int64_t *start, const int32_t *width, int64_t rows,
                int64_t *out);
 
+/*
+ * gymnasium.wrappers.NormalizeObservation / NormalizeReward around EVERY SCALAR env (wrappers/stateful_observation.py:464-561,
+ * stateful_reward.py:20-142, wrappers/utils.py:33-71) -- what SyncVectorEnv over wrapped scalar envs computes: one set of running statistics per
+ * sub-environment, each updated from a batch of one (csrc/per_env_normalize.hip, arithmetic in csrc/per_env_normalize_internal.h; added to ABI 10,
+ * which they leave as it is).  Bit for bit the reference's NumPy arithmetic; no reduction over the batch.  Both calls only enqueue ONE kernel on
+ * hip_stream: no allocation, no synchronisation.  All state lives in device arrays the caller owns, described by mi_per_env_state (N = num_envs,
+ * D = obs_dim); either half may be absent (obs_mean == NULL / ret_mean == NULL).
+ *
+ * Observation half.  obs_mean / obs_var: [N][D] of obs_dtype -- MI_F32 for float32 observations, MI_F64 for float64 ones --, initially 0 and 1.
+ * obs_count: float64, initially 1e-4; obs_first: 1 while a row has not been updated since construction (MI_F64 only: the reference's arrays are
+ * float32 until the first update, which makes that update's var * count a float32 product).  A row's count and flag are read by the D threads of
+ * the row, so they are DOUBLE-BUFFERED: [2][N], a call reads half `obs_phase` and writes the other half for every row; the caller flips
+ * obs_phase after every call that had an observation block.
+ * Reward half, all float64 [N]: acc (the discounted return, initially 0; only `terminated` of a step clears it, never a reset or a truncation),
+ * ret_mean / ret_var / ret_count (0, 1, 1e-4), and was_done [N] uint8: the rows that finished in the previous step.  Under
+ * MI_AUTORESET_NEXT_STEP such a row is in its autoreset step: reward_out is 0.0 and nothing of the row changes; under SAME_STEP and DISABLED every
+ * row takes the step.  was_done is rewritten as terminated | truncated by every call; the caller clears the rows it resets.
+ *
+ * mi_per_env_normalize_step, what one reset() or step() returns:
+ *   obs / obs_out: [N][D] obs_dtype / float32 (NULL: no observation block).  row_mask ([N] uint8, or NULL = every row): rows outside it are left
+ *     alone -- statistics untouched, obs_out[row] = prev_out[row] (the batch returned last; prev_out NULL: obs_out[row] is not written).
+ *   final_obs / final_out / final_mask (SAME_STEP, or all NULL): for the rows in final_mask the final observation updates the statistics and is
+ *     normalised FIRST, then the row's `obs`: two updates in one call.  Rows outside final_mask: final_out is 0.
+ *   reward / terminated / truncated / reward_out: [N] (NULL reward: no reward block).
+ * mi_per_env_normalize_steps, the T consecutive step() calls of a rollout: obs [T][N][D], obs_out [T][N][D] float32 (may alias obs for MI_F32),
+ *   reward / terminated / truncated / reward_out [T][N] (reward_out may alias reward).  Every thread keeps its statistics in registers over the T
+ *   steps and stores them once; the result and the state left behind equal T calls of mi_per_env_normalize_step.  NEXT_STEP and DISABLED only
+ *   (SAME_STEP needs the final observations: MI_ERR_UNSUPPORTED).
+ * N * D must stay below 2^31; T * N * D is indexed in 64 bits.
+ */
+typedef struct mi_per_env_state {
+    void *obs_mean, *obs_var;   /* [N][D] of obs_dtype, or NULL: no NormalizeObservation */
+    double *obs_count;          /* [2][N] */
+    uint8_t *obs_first;         /* [2][N] */
+    int32_t obs_phase;          /* 0 / 1: the half of obs_count / obs_first that is current */
+    int32_t obs_dtype;          /* MI_F32 / MI_F64 */
+    int32_t obs_dim;
+    int32_t obs_update;         /* update_running_mean of NormalizeObservation */
+    double obs_epsilon;
+    double *acc, *ret_mean, *ret_var, *ret_count; /* [N], or ret_mean == NULL: no NormalizeReward */
+    uint8_t *was_done;          /* [N] */
+    double gamma, reward_epsilon;
+    int32_t reward_update;      /* update_running_mean of NormalizeReward */
+    int32_t autoreset_mode;     /* mi_autoreset_mode */
+} mi_per_env_state;
+int mi_per_env_normalize_step(int device, void *hip_stream, const mi_per_env_state *state, int num_envs, const void *obs, void *obs_out,
+                              const uint8_t *row_mask, const void *prev_out, const void *final_obs, void *final_out, const uint8_t *final_mask,
+                              const double *reward, const uint8_t *terminated, const uint8_t *truncated, double *reward_out);
+int mi_per_env_normalize_steps(int device, void *hip_stream, const mi_per_env_state *state, int T, int num_envs, const void *obs, void *obs_out,
+                               const double *reward, const uint8_t *terminated, const uint8_t *truncated, double *reward_out);
+
 /* The same three wrappers as the OUTPUT STAGE of the step kernel (classic-control kinds): mi_step / mi_step_async then return the wrapped
  * observations and rewards in place of the raw ones -- one extra launch per step (the normalisations need the statistics of the WHOLE batch,
  * stateful_observation.py:146-152) instead of the ten of the stand-alone passes, and no staging for host callers: the values are rewritten
