@@ -51,6 +51,10 @@ HOST_SYMBOLS += ["action_sample_masked", "action_sample_weighted", "action_get_b
 # RepeatAction / StickyAction of the sub-environments inside the step (mi_set_step_wrappers; added to ABI 10, which it leaves as it is): product library
 # only -- HipVectorEnv.set_step_wrappers tells the backends apart by whether the entry point is bound.
 HOST_SYMBOLS += ["set_step_wrappers"]
+# Per-sub-environment model fields of the MuJoCo kinds (mi_set_model_field; added to ABI 10, which it leaves as it is): product library only -- the oracle
+# takes a model as data for ALL its envs (orc_mj_register_model), and HipVectorEnv.set_attr tells the backends apart by whether the entry point is bound.
+HOST_SYMBOLS += ["model_field_width", "set_model_field", "get_model_field"]
+MODEL_GRAVITY, MODEL_ACTUATOR_GEAR, MODEL_DOF_DAMPING, MODEL_PAIR_FRICTION = 0, 1, 2, 3  # MI_MODEL_*
 WRAPPER_SYMBOLS = ["rms_create", "rms_destroy", "rms_get", "rms_set", "normalize_observation", "normalize_reward", "clip_reward", "set_step_epilogue"]
 # The normalisations over a whole trajectory (ABI 9): what the wrappers' rollout() runs over the output of mi_rollout.
 WRAPPER_SYMBOLS += ["wrapper_steps_workspace", "normalize_observation_steps", "normalize_reward_steps"]
@@ -198,6 +202,12 @@ class NativeLib:
             try:
                 self.set_step_wrappers = f("set_step_wrappers", [vp, i32, dbl, i32], i32)
             except ImportError:  # an ABI 10 build from before the entry point (MI355ENV_LIBRARY, A/B runs): HipVectorEnv.set_step_wrappers refuses
+                pass
+            try:
+                self.model_field_width = f("model_field_width", [vp, i32], i32)
+                self.set_model_field = f("set_model_field", [vp, i32, vp, i32], i32)
+                self.get_model_field = f("get_model_field", [vp, i32, vp], i32)
+            except ImportError:  # (likewise: set_attr on a MuJoCo env refuses)
                 pass
 
     def _fn(self, name, argtypes, restype):
@@ -492,6 +502,22 @@ class Engine:
             values = np.ascontiguousarray(values, dtype=np.float64)
             assert values.shape == (self.num_envs,)
         self.lib.check(self.lib.set_env_attr(self.handle, int(attr), _ptr(values), 1 if on_device else 0))
+
+    def model_field_width(self, field: int) -> int:
+        return int(self.lib.model_field_width(self.handle, int(field)))
+
+    def set_model_field(self, field: int, values, on_device: bool = False):
+        """mi_set_model_field: ``values`` = [num_envs, width] float64 (a C-contiguous host array, or with ``on_device`` a device address), or None
+        for the compiled-in values."""
+        if values is not None and not on_device:
+            values = np.ascontiguousarray(values, dtype=np.float64)
+            assert values.shape == (self.num_envs, self.model_field_width(field)), values.shape
+        self.lib.check(self.lib.set_model_field(self.handle, int(field), _ptr(values), 1 if on_device else 0))
+
+    def get_model_field(self, field: int) -> np.ndarray:
+        out = np.empty((self.num_envs, self.model_field_width(field)), dtype=np.float64)
+        self.lib.check(self.lib.get_model_field(self.handle, int(field), _ptr(out)))
+        return out
 
     def get_env_attr(self, attr: int) -> np.ndarray:
         out = np.empty(self.num_envs, dtype=np.float64)

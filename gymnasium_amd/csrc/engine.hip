@@ -67,6 +67,11 @@ struct TabTable {
     const int32_t *env_table;  // [N] table of each sub-environment when there are several (mi_tabular_table.num_tables > 1), else nullptr
 };
 
+// Per-sub-environment model fields of a MuJoCo env (mi_set_model_field), as they ride in DevEnv.
+struct MjModelDev {
+    int tab_ints[3];     // tab.nS, tab.nA, tab.K of the union below: always 0 here
+    const double *rows;  // [mjx::LaneFields::WIDTH][N], read by the mjx::LaneModel instantiations only; NULL until the first mi_set_model_field
+};
 // Device view of one vector environment (passed by value as a kernel argument).
 struct DevEnv {
     double *state;       // [S][N]   physics state, component-major
@@ -82,8 +87,15 @@ struct DevEnv {
     int solver_newton;   // MI_CFG_SOLVER_NEWTON (one-lane MuJoCo kernels; the cooperative kernel is chosen at launch)
     int tab_fickle_rows; // MI_ENV_TABULAR with params[2] != 0 (Taxi's fickle passenger): the state has a third row (TabLane::aux)
     EnvParams P;
-    TabTable tab;
+    // By kind; the size and layout of DevEnv are the table's, as before the union.  Kernels of EVERY kind read tab.nS (seed_words_kernel /
+    // seed_sequence_kernel: < 0 is the Blackjack marker), so the pointer of the MuJoCo kinds lies behind the table's three integers, which stay 0 for
+    // them: it shares its bytes with tab.csprob, which only the tabular kernels read.
+    union {
+        TabTable tab;  // the tabular kinds
+        MjModelDev mj; // the MuJoCo kinds
+    };
 };
+static_assert(offsetof(MjModelDev, rows) == offsetof(TabTable, csprob) && sizeof(MjModelDev) <= sizeof(TabTable), "mj.rows must alias a pointer of the table, not nS / nA / K");
 // Per-sub-environment attributes (mi_set_env_attr; the *AttrT types of envs_classic.h): attribute a of sub-environment i is rows[a * N + i] if bit
 // a of `mask` is set, else its construction value.  An extra argument of step_kernel / rollout_kernel, which the other types do not read.
 struct AttrDev {
@@ -1045,6 +1057,18 @@ int shared_step(mi_vecenv *v, const mi_internal::StepPtrs &p);
 int shared_rollout(mi_vecenv *v, const mi_internal::RolloutPtrs &p, const mi_internal::ActionStream &as, int T, bool sample, const mi_internal::RolloutExtra *ex = nullptr);
 int shared_recount(mi_vecenv *v);
 }  // namespace mi_classic
+// The one-lane MuJoCo kernels of an env with per-sub-environment model fields (mi_set_model_field) -- mj_step_kernel and mj_rollout_kernel over
+// mjx::LaneModel env types -- behind plain launch functions: they are instantiated in a translation unit of their own (mjx_model.hip: this file with
+// MI_MJ_MODEL_TU), which compiles side by side with the others.  `mj_step_ptrs` is an MjStepPtrs -- a type of the unnamed namespace, whose name is
+// part of the stock kernels' symbols and therefore stays where it is; both units compile the one definition.  d.mj.rows are the env's rows.
+// false: a kind the unit does not hold.
+namespace mi_mjmodel {
+bool step(int kind, int autoreset_mode, int grid, hipStream_t stream, const mi_internal::DevEnv &d, const void *mj_step_ptrs);
+// load the unit's code object on the current device now (kernels load on first use, which a stream capture must not trigger)
+bool preload(int kind);
+bool rollout(int kind, int autoreset_mode, bool sample, int grid, hipStream_t stream, const mi_internal::DevEnv &d, const mi_internal::RolloutPtrs &p,
+             const mi_internal::ActionStream &as, int T, int obs_dim, int in_f64, const mi_internal::RolloutExtra &ex);
+}  // namespace mi_mjmodel
 namespace {
 
 // FULL: every trajectory output is materialised -- the per-store null checks (five taken branches per step for a
@@ -1964,6 +1988,23 @@ struct MjLane {
     double ep_ret;
     int32_t ep_len;
 };
+// The sub-environment's own model fields of an env type over a mjx::LaneModel (void, and nothing to load, for the stock models): loaded once per launch
+template <class E>
+using MjLaneFields = typename mjx::ModelView<typename E::Model>::Fields;
+template <class E>
+struct MjLaneHolder {
+    static constexpr bool HAS = !std::is_void<MjLaneFields<E>>::value;
+    typename std::conditional<HAS, MjLaneFields<E>, char>::type fields;  // (a byte nobody touches for the stock models)
+    MI_DEV void load(const DevEnv &d, int i) {
+        if constexpr (HAS) fields.load(d.mj.rows, (size_t)d.N, (size_t)i);
+    }
+    MI_DEV const MjLaneFields<E> *get() const {
+        if constexpr (HAS)
+            return &fields;
+        else
+            return nullptr;
+    }
+};
 template <class E>
 MI_DEV void mj_load(const DevEnv &d, int i, MjLane<E> &L) {
     for (int k = 0; k < E::S; k++) L.s[k] = d.state[(size_t)k * d.N + i];
@@ -1991,7 +2032,7 @@ MI_DEV void mj_autoreset(const DevEnv &d, int i, MjLane<E> &L, double *obs) {
 template <class E, int MODE, bool COOP = false>
 MI_DEV void mj_lane_step(const DevEnv &d, int i, MjLane<E> &L, const mjx::ActRow action, double *obs, double *final_obs, double *info,
                          double &reward, bool &te, bool &tr, double &out_ret, int32_t &out_len, LaneStats &st,
-                         const double *extras = nullptr, double *final_info = nullptr) {
+                         const double *extras = nullptr, double *final_info = nullptr, const MjLaneFields<E> *lane = nullptr) {
     te = tr = false, reward = 0.0;
     if (MODE == MI_AUTORESET_NEXT_STEP && (L.flags & kNeedsReset)) {
         mj_autoreset<E>(d, i, L, obs);
@@ -2015,7 +2056,7 @@ MI_DEV void mj_lane_step(const DevEnv &d, int i, MjLane<E> &L, const mjx::ActRow
             const double before[2] = {L.s[E::NQ + 2 * E::NV], L.s[E::NQ + 2 * E::NV + 1]};
             E::finish(L.s, before, x, action, d.P, obs, reward, te, info);
         } else {
-            E::step(L.s, action, d.P, obs, reward, te, info, d.solver_newton != 0);
+            E::step(L.s, action, d.P, obs, reward, te, info, d.solver_newton != 0, lane);
         }
         L.elapsed += 1;
         tr = d.max_steps > 0 && (int)L.elapsed >= d.max_steps;
@@ -2050,11 +2091,23 @@ __global__ __launch_bounds__(kBlock) void mj_step_kernel(DevEnv d, MjStepPtrs io
         int32_t out_len;
         bool te, tr;
         const mjx::ActRow a = {static_cast<const char *>(io.actions) + (size_t)i * E::NU * (io.act_f64 ? 8 : 4), io.act_f64 != 0};
-        mj_lane_step<E, MODE, COOP>(d, i, L, a, io.obs + (size_t)i * io.obs_dim,
-                              io.final_obs ? io.final_obs + (size_t)i * io.obs_dim : nullptr,
-                              io.info ? io.info + (size_t)i * E::INFO : nullptr, reward, te, tr, out_ret, out_len, st,
-                              COOP ? io.extras + (size_t)i * mjx::coop::Sim<typename E::Model, E::COOP_G>::EX_TOTAL : nullptr,
-                              io.final_info ? io.final_info + (size_t)i * E::INFO : nullptr);
+        // Two spellings of one call, on purpose: with a holder object in the stock instantiations -- even an empty one, as in mj_rollout_kernel -- the
+        // DISABLED-mode kernels of the stock robots come out with two instructions in another order (scripts/kernel_stream_diff.py), and the stock
+        // kernels are to stay what they were instruction for instruction.
+        if constexpr (MjLaneHolder<E>::HAS) {
+            MjLaneHolder<E> lane;
+            lane.load(d, i);
+            mj_lane_step<E, MODE, false>(d, i, L, a, io.obs + (size_t)i * io.obs_dim,
+                                         io.final_obs ? io.final_obs + (size_t)i * io.obs_dim : nullptr,
+                                         io.info ? io.info + (size_t)i * E::INFO : nullptr, reward, te, tr, out_ret, out_len, st, nullptr,
+                                         io.final_info ? io.final_info + (size_t)i * E::INFO : nullptr, lane.get());
+        } else {
+            mj_lane_step<E, MODE, COOP>(d, i, L, a, io.obs + (size_t)i * io.obs_dim,
+                                        io.final_obs ? io.final_obs + (size_t)i * io.obs_dim : nullptr,
+                                        io.info ? io.info + (size_t)i * E::INFO : nullptr, reward, te, tr, out_ret, out_len, st,
+                                        COOP ? io.extras + (size_t)i * mjx::coop::Sim<typename E::Model, E::COOP_G>::EX_TOTAL : nullptr,
+                                        io.final_info ? io.final_info + (size_t)i * E::INFO : nullptr);
+        }
         mj_store<E>(d, i, L);
         if (io.reward) io.reward[i] = reward;
         if (io.terminated) io.terminated[i] = te;
@@ -2087,6 +2140,8 @@ __global__ __launch_bounds__(kBlock) void mj_rollout_kernel(DevEnv d, RolloutPtr
     if (i < d.N) {
         MjLane<E> L;
         mj_load<E>(d, i, L);
+        MjLaneHolder<E> lane;
+        lane.load(d, i);
         u128 astate = 0;
         const u128 ainc = make_u128(as.inc_hi, as.inc_lo);
         if (SAMPLE) {
@@ -2123,7 +2178,7 @@ __global__ __launch_bounds__(kBlock) void mj_rollout_kernel(DevEnv d, RolloutPtr
             double *finfo = ex.final_info ? ex.final_info + (t * N + i) * E::INFO : nullptr;
             // (the finishing step's info reaches final_info through the info row: without a caller's array a private row serves)
             double *info = ex.info ? ex.info + (t * N + i) * E::INFO : (finfo ? scratch_info : nullptr);
-            mj_lane_step<E, MODE>(d, i, L, row, obs, fobs, info, reward, te, tr, out_ret, out_len, st, nullptr, finfo);
+            mj_lane_step<E, MODE>(d, i, L, row, obs, fobs, info, reward, te, tr, out_ret, out_len, st, nullptr, finfo, lane.get());
             if (io.reward) io.reward[t * N + i] = reward;
             if (io.terminated) io.terminated[t * N + i] = te;
             if (io.truncated) io.truncated[t * N + i] = tr;
@@ -2141,6 +2196,7 @@ __global__ __launch_bounds__(kBlock) void mj_rollout_kernel(DevEnv d, RolloutPtr
     block_accumulate(d, st);
 }
 
+#ifndef MI_MJ_MODEL_TU
 // ---- cooperative physics (mjx_coop.h): G lanes per sub-environment, 64 / G sub-environments per wavefront --------------
 // mj_physics_kernel lives in mjx_physics.h and is instantiated in physics16.hip / physics32.hip (their own compiler settings); here it
 // is only launched: mi_phys::launch16 / launch32.
@@ -2942,6 +2998,14 @@ __global__ __launch_bounds__(kBlock) void act_sample_kernel(ActSpec sp, ActionSt
     act_lane[i] = (uint64_t)(s >> 64), act_lane[(size_t)N + i] = (uint64_t)s;
 }
 
+// mi_set_model_field with device values: the caller's [N][width] rows into `width` component-major rows of the env's block
+__global__ __launch_bounds__(kBlock) void model_transpose_kernel(const double *src, double *dst, int N, int width) {
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= N) return;
+    for (int c = 0; c < width; c++) dst[(size_t)c * N + i] = src[(size_t)i * width + c];
+}
+
+#endif  // !MI_MJ_MODEL_TU
 #endif  // !MI_CLASSIC_TU
 
 // ---------------------------------------------------------------------------------------------------------
@@ -2949,6 +3013,65 @@ __global__ __launch_bounds__(kBlock) void act_sample_kernel(ActSpec sp, ActionSt
 // ---------------------------------------------------------------------------------------------------------
 
 }  // namespace
+#ifdef MI_MJ_MODEL_TU
+namespace mi_mjmodel {
+template <class M0, int KIND>
+using Env = mjx::MjEnv<mjx::LaneModel<M0>, KIND>;
+template <class F>
+static bool dispatch(int kind, F &&f) {
+    switch (kind) {
+    case MI_ENV_HALF_CHEETAH: f(Env<mjx::HalfCheetahModel, mjx::kHalfCheetah>()); return true;
+    case MI_ENV_ANT: f(Env<mjx::AntModel, mjx::kAnt>()); return true;
+    case MI_ENV_HUMANOID: f(Env<mjx::HumanoidModel, mjx::kHumanoid>()); return true;
+    case MI_ENV_HOPPER: f(Env<mjx::HopperModel, mjx::kHopper>()); return true;
+    case MI_ENV_WALKER2D: f(Env<mjx::Walker2dModel, mjx::kWalker2d>()); return true;
+    case MI_ENV_INVERTED_PENDULUM: f(Env<mjx::InvertedPendulumModel, mjx::kInvertedPendulum>()); return true;
+    case MI_ENV_INVERTED_DOUBLE_PENDULUM: f(Env<mjx::InvertedDoublePendulumModel, mjx::kInvertedDoublePendulum>()); return true;
+    case MI_ENV_REACHER: f(Env<mjx::ReacherModel, mjx::kReacher>()); return true;
+    case MI_ENV_HUMANOID_STANDUP: f(Env<mjx::HumanoidStandupModel, mjx::kHumanoidStandup>()); return true;
+    case MI_ENV_SWIMMER: f(Env<mjx::SwimmerModel, mjx::kSwimmer>()); return true;
+    case MI_ENV_PUSHER: f(Env<mjx::PusherModel, mjx::kPusher>()); return true;
+    }
+    return false;
+}
+bool preload(int kind) {
+    hipError_t err = hipSuccess;
+    const bool held = dispatch(kind, [&](auto env) {
+        hipFuncAttributes attr;
+        err = hipFuncGetAttributes(&attr, reinterpret_cast<const void *>(&mj_step_kernel<decltype(env), MI_AUTORESET_NEXT_STEP, false>));
+    });
+    return held && err == hipSuccess;
+}
+bool step(int kind, int mode, int grid, hipStream_t stream, const DevEnv &d, const void *mj_step_ptrs) {
+    const MjStepPtrs mp = *static_cast<const MjStepPtrs *>(mj_step_ptrs);
+    const dim3 g(grid), b(kBlock);
+    return dispatch(kind, [&](auto env) {
+        using E = decltype(env);
+        switch (mode) {
+        case MI_AUTORESET_NEXT_STEP: hipLaunchKernelGGL((mj_step_kernel<E, MI_AUTORESET_NEXT_STEP, false>), g, b, 0, stream, d, mp); break;
+        case MI_AUTORESET_SAME_STEP: hipLaunchKernelGGL((mj_step_kernel<E, MI_AUTORESET_SAME_STEP, false>), g, b, 0, stream, d, mp); break;
+        default: hipLaunchKernelGGL((mj_step_kernel<E, MI_AUTORESET_DISABLED, false>), g, b, 0, stream, d, mp); break;
+        }
+    });
+}
+bool rollout(int kind, int mode, bool sample, int grid, hipStream_t stream, const DevEnv &d, const RolloutPtrs &p, const ActionStream &as, int T, int obs_dim,
+             int in_f64, const RolloutExtra &ex) {
+    const dim3 g(grid), b(kBlock);
+    return dispatch(kind, [&](auto env) {
+        using E = decltype(env);
+        const bool next = mode == MI_AUTORESET_NEXT_STEP;  // (mi_rollout refuses a DISABLED env)
+        if (next && sample)
+            hipLaunchKernelGGL((mj_rollout_kernel<E, MI_AUTORESET_NEXT_STEP, true>), g, b, 0, stream, d, p, as, T, obs_dim, in_f64, ex);
+        else if (next)
+            hipLaunchKernelGGL((mj_rollout_kernel<E, MI_AUTORESET_NEXT_STEP, false>), g, b, 0, stream, d, p, as, T, obs_dim, in_f64, ex);
+        else if (sample)
+            hipLaunchKernelGGL((mj_rollout_kernel<E, MI_AUTORESET_SAME_STEP, true>), g, b, 0, stream, d, p, as, T, obs_dim, in_f64, ex);
+        else
+            hipLaunchKernelGGL((mj_rollout_kernel<E, MI_AUTORESET_SAME_STEP, false>), g, b, 0, stream, d, p, as, T, obs_dim, in_f64, ex);
+    });
+}
+}  // namespace mi_mjmodel
+#else  // every other translation unit: the rest of the file
 // shared with the other translation units of the library (hidden visibility): sets mi_last_error(), returns `code`
 namespace mi_internal {
 #ifndef MI_CLASSIC_TU
@@ -3050,6 +3173,11 @@ struct mi_vecenv {
     // come from them.  attr_mask != 0 ("per-lane mode"): step and rollout run the *AttrT kernels (envs_classic.h); a bit, once set, stays set
     double *d_attr;
     uint32_t attr_mask;
+    // mi_set_model_field (MuJoCo kinds): [LaneFields::WIDTH][N] float64 rows of gravity, actuator_gear, dof_damping, pair_friction -- allocated by the first
+    // call, all fields at once, holding the compiled-in values -- and the set of fields a call has written (mi_get_model_field answers for the others without a copy).  d_model != NULL: step and rollout run the
+    // one-lane kernels over the mjx::LaneModel env types (mjx_model.hip) for good; mj_coop is cleared with it.
+    double *d_model;
+    uint32_t model_mask;
     // mi_set_step_wrappers: RepeatAction / StickyAction of the sub-environments inside the step.  wrap_on: the *_wrapped_kernel entry points run, with
     // `wrap` as their last argument (its two arrays are allocated by the first call that switches StickyAction on).  per_lane: some call has switched
     // them on -- from then on the env stays on the per-lane types (envs_classic.h *AttrT) and their one-role kernels, as after mi_set_env_attr.
@@ -3433,6 +3561,11 @@ int launch_mj_step(mi_vecenv *v, MjStepPtrs mp) {
     const dim3 g(v->grid), b(kBlock);
     const int mode = v->cfg.autoreset_mode;
     mp.extras = nullptr;
+    if (v->d_model) {  // per-sub-environment model fields: the one-lane simulator with the lane's view
+        if (!mi_mjmodel::step(v->cfg.kind, mode, v->grid, v->stream, v->d, &mp)) return fail(MI_ERR_UNSUPPORTED, "no per-lane-model kernel for this env kind");
+        HIP_TRY(hipGetLastError());
+        return MI_OK;
+    }
     if constexpr (!E::HAS_COOP) {
         switch (mode) {
         case MI_AUTORESET_NEXT_STEP: hipLaunchKernelGGL((mj_step_kernel<E, MI_AUTORESET_NEXT_STEP, false>), g, b, 0, v->stream, v->d, mp); break;
@@ -3703,7 +3836,7 @@ void mi_destroy(mi_vecenv *v) {
     (void)hipStreamSynchronize(v->stream);
     void *ptrs[] = {v->d.state, v->d.meta, v->d.rng, v->d.ep_ret, v->d.ep_len, v->d.blk_count, v->d.blk_ret, v->d_out,
                     v->d_pow2, v->d_act_lane, v->d_act_stage, v->d_actions, v->d_mask, v->d_words, v->d_extras, v->d_act_scratch, v->d_obs_scratch,
-                    v->shared.words, v->d_shared_pow2, v->shared.blk_done, v->shared.blk_prefix, v->d_attr, v->wrap.last_action, v->wrap.sticky_word,
+                    v->shared.words, v->d_shared_pow2, v->shared.blk_done, v->shared.blk_prefix, v->d_attr, v->d_model, v->wrap.last_action, v->wrap.sticky_word,
                     v->d_act_ctl, v->d_act_partial, v->d_act_slot, v->d_arg_stage};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
@@ -3792,6 +3925,106 @@ int mi_get_env_attr(mi_vecenv *v, int attr, double *host_out) {
     }
     HIP_TRY(hipMemcpyAsync(host_out, v->d_attr + (size_t)attr * N, sizeof(double) * N, hipMemcpyDeviceToHost, v->stream));
     HIP_TRY(hipStreamSynchronize(v->stream));
+    return MI_OK;
+}
+
+// Per-sub-environment model fields of the MuJoCo kinds (include/mi355env.h MI_MODEL_*; device side: mjx::LaneModel).  As everywhere on this path the
+// parity with `mujoco` is UNPINNED; the CPU oracle, which takes the same fields as data, is the reference.
+struct ModelFieldInfo {
+    int width[MI_MODEL_FIELD_COUNT], offset[MI_MODEL_FIELD_COUNT], total;
+    const double *defaults[MI_MODEL_FIELD_COUNT];
+};
+static bool model_field_info(const mi_vecenv *v, ModelFieldInfo &out) {
+    if (!v || !is_mj(v->cfg.kind)) return false;
+    return dispatch_mj(v->cfg.kind, [&](auto env) -> int {
+               typedef typename decltype(env)::Model M;
+               typedef mjx::LaneFields<M> V;
+               const ModelFieldInfo f = {{3, M::NU, M::NV, M::NPAIR}, {V::OFF_GRAVITY, V::OFF_GEAR, V::OFF_DAMPING, V::OFF_FRICTION}, V::WIDTH,
+                                         {M::gravity, M::actuator_gear, M::dof_damping, M::pair_friction}};
+               out = f;
+               return (int)MI_OK;
+           }) == MI_OK;
+}
+static int model_field_check(mi_vecenv *v, int field, ModelFieldInfo &f) {
+    if (!v) return fail(MI_ERR_INVALID_ARGUMENT, "null env");
+    if (!model_field_info(v, f)) return fail(MI_ERR_UNSUPPORTED, "per-sub-environment model fields: the MuJoCo kinds only");
+    if (field < 0 || field >= MI_MODEL_FIELD_COUNT) return fail(MI_ERR_INVALID_ARGUMENT, "model field id out of range");
+    if (v->has_pending) return fail(MI_ERR_STATE, "an asynchronous step is pending (mi_step_wait)");
+    return MI_OK;
+}
+
+int mi_model_field_width(mi_vecenv *v, int field) {
+    ModelFieldInfo f;
+    if (!model_field_info(v, f) || field < 0 || field >= MI_MODEL_FIELD_COUNT) return -1;
+    return f.width[field];
+}
+
+int mi_set_model_field(mi_vecenv *v, int field, const double *values, int on_device) {
+    ModelFieldInfo f;
+    if (const int rc = model_field_check(v, field, f)) return rc;
+    const size_t N = (size_t)v->cfg.num_envs;
+    const int w = f.width[field];
+    if (values && !on_device)
+        for (size_t k = 0; k < N * (size_t)w; k++) {
+            const double x = values[k];
+            if (!(x - x == 0.0)) return fail(MI_ERR_INVALID_ARGUMENT, "mi_set_model_field: non-finite value");
+            if (field == MI_MODEL_DOF_DAMPING && x < 0.0) return fail(MI_ERR_INVALID_ARGUMENT, "mi_set_model_field: dof_damping must be >= 0");
+            if (field == MI_MODEL_PAIR_FRICTION && x < 1e-5) return fail(MI_ERR_INVALID_ARGUMENT, "mi_set_model_field: pair_friction must be >= 1e-5 (MuJoCo's minimum)");
+        }
+    if (set_device(v)) return MI_ERR_HIP;
+    if (!v->d_model) {  // every field at once, at the compiled-in values: a later field needs no allocation (mi_step stays capturable)
+        if (!mi_mjmodel::preload(v->cfg.kind)) {  // ... and the per-lane kernels loaded now: a capture may follow this call at once
+            (void)hipGetLastError();
+            return fail(MI_ERR_HIP, "mi_set_model_field: could not load the per-lane-model kernels");
+        }
+        double *rows = nullptr;
+        HIP_TRY(hipMalloc(&rows, sizeof(double) * (size_t)f.total * N));
+        std::vector<double> host((size_t)f.total * N);
+        for (int a = 0; a < MI_MODEL_FIELD_COUNT; a++)
+            for (int c = 0; c < f.width[a]; c++)
+                for (size_t i = 0; i < N; i++) host[(size_t)(f.offset[a] + c) * N + i] = f.defaults[a][c];
+        if (hipMemcpyAsync(rows, host.data(), sizeof(double) * host.size(), hipMemcpyHostToDevice, v->stream) != hipSuccess ||
+            hipStreamSynchronize(v->stream) != hipSuccess) {
+            (void)hipFree(rows);
+            return fail(MI_ERR_HIP, "mi_set_model_field: could not initialise the model rows");
+        }
+        v->d_model = rows, v->d.mj.rows = rows;
+        v->mj_coop = false;  // for good: the cooperative kernels read the compiled-in model
+    }
+    v->model_mask |= 1u << field;
+    if (w == 0) return MI_OK;  // (a robot without contact pairs)
+    double *dst = v->d_model + (size_t)f.offset[field] * N;
+    if (values && on_device) {
+        hipLaunchKernelGGL(model_transpose_kernel, dim3(v->grid), dim3(kBlock), 0, v->stream, values, dst, (int)N, w);
+        HIP_TRY(hipGetLastError());
+    } else {  // staged: the caller may reuse its array as soon as this returns
+        std::vector<double> host((size_t)w * N);
+        for (int c = 0; c < w; c++)
+            for (size_t i = 0; i < N; i++) host[(size_t)c * N + i] = values ? values[i * (size_t)w + c] : f.defaults[field][c];
+        HIP_TRY(hipMemcpyAsync(dst, host.data(), sizeof(double) * host.size(), hipMemcpyHostToDevice, v->stream));
+        HIP_TRY(hipStreamSynchronize(v->stream));
+    }
+    return MI_OK;
+}
+
+int mi_get_model_field(mi_vecenv *v, int field, double *host_out) {
+    ModelFieldInfo f;
+    if (const int rc = model_field_check(v, field, f)) return rc;
+    if (!host_out) return fail(MI_ERR_INVALID_ARGUMENT, "null argument");
+    const size_t N = (size_t)v->cfg.num_envs;
+    const int w = f.width[field];
+    if (!(v->model_mask & (1u << field))) {  // never written: the compiled-in values, no synchronisation
+        for (size_t i = 0; i < N; i++)
+            for (int c = 0; c < w; c++) host_out[i * (size_t)w + c] = f.defaults[field][c];
+        return MI_OK;
+    }
+    if (w == 0) return MI_OK;
+    if (set_device(v)) return MI_ERR_HIP;
+    std::vector<double> host((size_t)w * N);
+    HIP_TRY(hipMemcpyAsync(host.data(), v->d_model + (size_t)f.offset[field] * N, sizeof(double) * host.size(), hipMemcpyDeviceToHost, v->stream));
+    HIP_TRY(hipStreamSynchronize(v->stream));
+    for (size_t i = 0; i < N; i++)
+        for (int c = 0; c < w; c++) host_out[i * (size_t)w + c] = host[(size_t)c * N + i];
     return MI_OK;
 }
 
@@ -4474,6 +4707,12 @@ static int rollout_impl(mi_vecenv *v, int T, const mi_rollout_io *io, const Roll
         rc = dispatch_mj(v->cfg.kind, [&](auto env) -> int {
             using E = decltype(env);
             const RolloutExtra e = ex ? *ex : RolloutExtra{};
+            if (v->d_model) {
+                if (!mi_mjmodel::rollout(v->cfg.kind, v->cfg.autoreset_mode, sample, v->grid, v->stream, v->d, p, as, T, v->lay.obs_dim, in_f64, e))
+                    return fail(MI_ERR_UNSUPPORTED, "no per-lane-model kernel for this env kind");
+                HIP_TRY(hipGetLastError());
+                return (int)MI_OK;
+            }
             if (v->mj_coop) return launch_mj_rollout_coop<E>(v, p, as, T, sample, in_f64, e);
             const dim3 g(v->grid), b(kBlock);
             const bool next = v->cfg.autoreset_mode == MI_AUTORESET_NEXT_STEP;
@@ -4701,3 +4940,4 @@ int mi_set_state(mi_vecenv *v, const double *state, const int32_t *elapsed, cons
 }  // extern "C"
 #pragma GCC visibility pop
 #endif  // MI_CLASSIC_TU
+#endif  // !MI_MJ_MODEL_TU

@@ -166,9 +166,52 @@ struct Contact {
     int pair;
 };
 
+// ---- model view -------------------------------------------------------------------------------------------------------
+// The four model fields a sub-environment may have values of its own for (mi_set_model_field): opt.gravity, actuator_gear[:, 0],
+// dof_damping and the sliding friction of the contact pairs.  No compiled-model quantity is derived from any of them
+// (tests/test_model_attrs_host.py), so they can be replaced without recompiling the model.  The simulator reads them through the view
+// that its Data inherits.  For a generated model the view is empty and folds to the model's constants: the code of every stock
+// instantiation is what it was before the view existed.  LaneModel<M0> is M0 with a view that refers to one sub-environment's values
+// (LaneFields, loaded once per launch): the simulator instantiated for it is the per-lane one.  Like the rest of this pipeline their
+// parity with `mujoco` is UNPINNED; the CPU oracle, which takes the same fields as data, is the reference.
+template <class M0>
+struct LaneModel : M0 {};
+template <class M>
+struct LaneFields {
+    // rows of the engine's [WIDTH][N] float64 block (component-major, like the state rows)
+    static constexpr int OFF_GRAVITY = 0, OFF_GEAR = 3, OFF_DAMPING = 3 + M::NU, OFF_FRICTION = 3 + M::NU + M::NV, WIDTH = 3 + M::NU + M::NV + M::NPAIR;
+    double gravity[3], gear[M::NU], damping[M::NV], friction[M::NPAIR > 0 ? M::NPAIR : 1];
+    // sub-environment i of N: one coalesced load per row
+    MJX_DEV void load(const double *rows, size_t N, size_t i) {
+        for (int k = 0; k < 3; k++) gravity[k] = rows[(size_t)(OFF_GRAVITY + k) * N + i];
+        for (int k = 0; k < M::NU; k++) gear[k] = rows[(size_t)(OFF_GEAR + k) * N + i];
+        for (int k = 0; k < M::NV; k++) damping[k] = rows[(size_t)(OFF_DAMPING + k) * N + i];
+        for (int k = 0; k < M::NPAIR; k++) friction[k] = rows[(size_t)(OFF_FRICTION + k) * N + i];
+    }
+};
+template <class M>
+struct ModelView {
+    typedef void Fields;  // nothing to bind
+    MJX_DEV void bind(const Fields *) {}
+    static MJX_DEV double gravity(int k) { return M::gravity[k]; }
+    static MJX_DEV double gear(int u) { return M::actuator_gear[u]; }
+    static MJX_DEV double damping(int i) { return M::dof_damping[i]; }
+    static MJX_DEV double friction(int p) { return M::pair_friction[p]; }
+};
+template <class M0>
+struct ModelView<LaneModel<M0>> {
+    typedef LaneFields<M0> Fields;
+    const Fields *lane;
+    MJX_DEV void bind(const Fields *f) { lane = f; }
+    MJX_DEV double gravity(int k) const { return lane->gravity[k]; }
+    MJX_DEV double gear(int u) const { return lane->gear[u]; }
+    MJX_DEV double damping(int i) const { return lane->damping[i]; }
+    MJX_DEV double friction(int p) const { return lane->friction[p]; }
+};
+
 // per-lane simulation state of one forward evaluation
 template <class M>
-struct Data {
+struct Data : ModelView<M> {
     static constexpr int NQ = M::NQ, NV = M::NV, NB = M::NBODY, NJ = M::NJNT, NU = M::NU, NTRI = M::NV * (M::NV + 1) / 2;
     static constexpr int MAXCON = Limits<M>::MAXCON;
     double qpos[NQ], qvel[NV], ctrl[NU];
@@ -316,7 +359,7 @@ MJX_DEV void com_vel_and_bias(Data<M> &d, double *qfrc_bias) {
     double cacc[M::NBODY][6], cfrc[M::NBODY][6];
 #pragma unroll
     for (int k = 0; k < 6; k++) d.cvel[0][k] = 0, cacc[0][k] = 0, cfrc[0][k] = 0;
-    cacc[0][3] = -M::gravity[0], cacc[0][4] = -M::gravity[1], cacc[0][5] = -M::gravity[2];
+    cacc[0][3] = -d.gravity(0), cacc[0][4] = -d.gravity(1), cacc[0][5] = -d.gravity(2);
 #pragma unroll
     for (int b = 1; b < M::NBODY; b++) {
         const int p = M::body_parentid[b];
@@ -727,7 +770,7 @@ MJX_DEV void make_constraint(Data<M> &d) {
         const Contact<M> &con = d.con[c];
         const int p = con.pair;
         const int b1 = M::geom_bodyid[M::pair_geom1[p]], b2 = M::geom_bodyid[M::pair_geom2[p]];
-        const double tran = M::body_invweight0[b1][0] + M::body_invweight0[b2][0], mu = M::pair_friction[p];
+        const double tran = M::body_invweight0[b1][0] + M::body_invweight0[b2][0], mu = d.friction(p);
         double k, b, imp, R;
         const bool pyramid = M::pair_condim[p] > 1;
         row_params<M>(M::pair_solref[p], M::pair_solimp[p], con.dist, M::pair_margin[p], pyramid ? tran + mu * mu * tran : tran, k, b, imp, R);
@@ -765,7 +808,7 @@ struct RowView {  // all rows, regenerated on the fly
                 f(row, d.con_D[c], edge_aref[row], Jc[0]);
                 row++;
             } else {
-                const double mu = M::pair_friction[p];
+                const double mu = d.friction(p);
                 for (int e = 0; e < 4; e++) {
                     const double sg = (e & 1) ? -mu : mu;
                     const int t = 1 + e / 2;
@@ -1061,7 +1104,7 @@ MJX_DEVN void forward(Data<M> &d) {
     for (int u = 0; u < M::NU; u++) {
         double c = d.ctrl[u];
         c = c < M::actuator_ctrlrange[u][0] ? M::actuator_ctrlrange[u][0] : (c > M::actuator_ctrlrange[u][1] ? M::actuator_ctrlrange[u][1] : c);
-        d.qfrc_actuator[M::actuator_dofadr[u]] += M::actuator_gear[u] * c;
+        d.qfrc_actuator[M::actuator_dofadr[u]] += d.gear(u) * c;
     }
     double fl[NV];
 #pragma unroll
@@ -1069,7 +1112,7 @@ MJX_DEVN void forward(Data<M> &d) {
     if constexpr (M::DENSITY > 0 || M::VISCOSITY > 0) fluid<M>(d, fl);
 #pragma unroll
     for (int i = 0; i < NV; i++) {
-        double passive = fl[i] - M::dof_damping[i] * d.qvel[i];
+        double passive = fl[i] - d.damping(i) * d.qvel[i];
         const int j = M::dof_jntid[i];
         if (M::jnt_type[j] == HINGE || M::jnt_type[j] == SLIDE)
             passive -= M::jnt_stiffness[j] * (d.qpos[M::jnt_qposadr[j]] - M::qpos0[M::jnt_qposadr[j]]);
@@ -1122,12 +1165,12 @@ MJX_DEV void step(Data<M> &d) {
         double qacc[NV];
         bool damped = false;
 #pragma unroll
-        for (int i = 0; i < NV; i++) damped |= M::dof_damping[i] > 0;
+        for (int i = 0; i < NV; i++) damped |= d.damping(i) > 0;  // (a lane's own values decide, as the oracle's loop does)
         if (damped) {
             double A[Data<M>::NTRI], L[Data<M>::NTRI];
             for (int k = 0; k < Data<M>::NTRI; k++) A[k] = d.qM[k];
 #pragma unroll
-            for (int i = 0; i < NV; i++) A[tri(i, i)] += h * M::dof_damping[i], qacc[i] = d.qfrc_smooth[i] + d.qfrc_constraint[i];
+            for (int i = 0; i < NV; i++) A[tri(i, i)] += h * d.damping(i), qacc[i] = d.qfrc_smooth[i] + d.qfrc_constraint[i];
             chol_factor<NV>(A, L);
             chol_solve<NV>(L, qacc);
         } else {
@@ -1187,7 +1230,7 @@ MJX_DEV void contact_forces(const Data<M> &d, double cfrc_ext[M::NBODY][6]) {
         const double *f = d.con_force[c];
         double lf[3] = {f[0], 0, 0};
         if (M::pair_condim[p] > 1) {
-            const double mu = M::pair_friction[p];
+            const double mu = d.friction(p);
             lf[0] = f[0] + f[1] + f[2] + f[3], lf[1] = (f[0] - f[1]) * mu, lf[2] = (f[2] - f[3]) * mu;
         }
         double F[3], r[3] = {con.pos[0] - d.com[0], con.pos[1] - d.com[1], con.pos[2] - d.com[2]}, tq[3];

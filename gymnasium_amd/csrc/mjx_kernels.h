@@ -294,9 +294,12 @@ struct MjEnv {
     }
 
     // One env.step() with the one-lane simulator (mjx_core.h): physics, then finish().
+    // `lane`: the sub-environment's own model fields when M is a LaneModel (mi_set_model_field); the view is all that differs -- reset() and finish()
+    // read none of the four fields (the reset observation's cinert / cvel do not depend on gravity)
     static MJX_DEV void step(double *s, const ActRow action, const mi::EnvParams &P, double *obs, double &reward, bool &terminated,
-                             double *info, bool newton = false) {
+                             double *info, bool newton = false, const typename ModelView<M>::Fields *lane = nullptr) {
         Data<M> d;
+        d.bind(lane);
         for (int k = 0; k < NQ; k++) d.qpos[k] = s[k];
         for (int k = 0; k < NV; k++) d.qvel[k] = s[NQ + k];
         for (int u = 0; u < NU; u++) d.ctrl[u] = action[u];

@@ -200,6 +200,7 @@ def compile_model(desc, faithful_solver: bool = True) -> CompiledModel:
     m.geom_pos = np.array([g["pos"] for g in geoms], dtype=np.float64)
     m.geom_quat = np.array([g["quat"] for g in geoms], dtype=np.float64)
     m.geom_mat = np.array([quat_to_mat(g["quat"]) for g in geoms])
+    m.geom_friction = np.array([g["friction"] for g in geoms], dtype=np.float64).reshape(-1, 3)  # (sliding, torsional, rolling): mixed into pair_friction below
 
     # ---- body inertial properties from geoms (inertiafromgeom) --------------------------------------------------
     m.body_mass = np.zeros(nbody)

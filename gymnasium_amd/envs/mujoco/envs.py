@@ -17,7 +17,8 @@ from __future__ import annotations
 import numpy as np
 
 from ...gym_api import error, logger, spaces
-from ...vector.hip_vector_env import HipVectorEnv
+from ... import _native
+from ...vector.hip_vector_env import HipVectorEnv, UnknownEnvAttributeError
 from . import models as _models
 
 _WARNED_UNPINNED = False
@@ -75,6 +76,128 @@ class _MujocoVectorEnv(HipVectorEnv):
     def dt(self) -> float:
         """MujocoEnv.dt (mujoco_env.py:189-191): model.opt.timestep * frame_skip."""
         return _models.MODELS[self.KIND]()["option"]["timestep"] * self.frame_skip
+
+    # -- per-sub-environment model fields: set_attr / get_attr ---------------------------------------------------------------------------------
+    # This engine's spelling of writing env.unwrapped.model.opt.gravity, .actuator_gear[:, 0], .dof_damping and .geom_friction[:, 0] of every
+    # sub-environment of a SyncVectorEnv.  An EXTENSION: the reference's scalar envs have no such attributes (there one writes to the mjModel).  Like
+    # all MuJoCo physics here their parity with `mujoco` is UNPINNED; the CPU oracle, which takes the same fields as data, is the reference.  No
+    # compiled-model quantity is derived from any of the four (tests/test_model_attrs_host.py), so the engine replaces them without recompiling.
+    # (name, engine field id, minimum value or None): geom_friction is mixed into the engine's contact-pair rows on the host.
+    MODEL_FIELDS = (("gravity", _native.MODEL_GRAVITY, None), ("actuator_gear", _native.MODEL_ACTUATOR_GEAR, None),
+                    ("dof_damping", _native.MODEL_DOF_DAMPING, 0.0), ("geom_friction", _native.MODEL_PAIR_FRICTION, 1e-5))  # 1e-5: MuJoCo's documented minimum
+    _COMPILED: dict = {}
+
+    def _compiled_model(self):
+        if self.KIND not in self._COMPILED:
+            from . import compiler
+
+            self._COMPILED[self.KIND] = compiler.compile_model(self.KIND)
+        return self._COMPILED[self.KIND]
+
+    def _env_attr_refusal(self):
+        return None  # (the names are checked by _model_field)
+
+    def _model_field(self, name: str):
+        """(field id, minimum, stock value [width]) of a model field; UnknownEnvAttributeError for any other name."""
+        for field, fid, lo in self.MODEL_FIELDS:
+            if field == name:
+                m = self._compiled_model()
+                stock = {"gravity": m.gravity, "actuator_gear": m.actuator_gear, "dof_damping": m.dof_damping, "geom_friction": m.geom_friction[:, 0]}[name]
+                return fid, lo, np.array(stock, dtype=np.float64)
+        raise UnknownEnvAttributeError(f"{type(self).__name__} has no per-sub-environment attribute {name!r}; the supported names are "
+                                       f"{', '.join(f[0] for f in self.MODEL_FIELDS)} (model fields of the compiled robot: set_attr does not create new ones)")
+
+    def get_attr(self, name: str) -> tuple:
+        """The model field of every sub-environment: a tuple of num_envs float64 arrays; before any set_attr the compiled model's values."""
+        self._check_open()
+        self._check_not_pending("get_attr")
+        fid, _, stock = self._model_field(name)
+        if not (self._env_attr_mask >> fid) & 1:
+            return tuple(stock.copy() for _ in range(self.num_envs))
+        if name == "geom_friction":  # the engine holds the pair rows: the geoms' values are kept as they were given
+            held = self._model_geom_friction
+            rows = held if isinstance(held, np.ndarray) else held.cpu().numpy()
+        else:
+            rows = self._engine.get_model_field(fid)
+        return tuple(np.array(r, dtype=np.float64) for r in rows)
+
+    def set_attr(self, name: str, values) -> None:
+        """Set a model field of the sub-environments, by SyncVectorEnv.set_attr's rule: a list or tuple gives one array per sub-environment,
+        anything else that is not a tensor the same array for all; a float64 tensor of shape (num_envs, width) on the env's device is taken without
+        a host round trip.  Widths: gravity 3, actuator_gear nu, dof_damping nv, geom_friction ngeom (the sliding coefficient; a contact pair
+        takes the larger of its two geoms' values, as the model compiler mixes them).  Takes effect from the next step(); reset() does not undo
+        it.  The first call moves the env to the one-lane simulator for good (slower than the cooperative kernel for the large robots:
+        docs/results_log.md) and loads those kernels, so capture_steps() may follow it without an eager step in between; a graph captured BEFORE it
+        refuses to replay.  None restores the compiled model's values."""
+        self._check_open()
+        self._check_not_pending("set_attr")
+        fid, lo, stock = self._model_field(name)
+        N, W = self.num_envs, stock.shape[0]
+        dev = None
+        if values is None:
+            rows = np.tile(stock, (N, 1))
+        elif type(values).__module__.split(".")[0] == "torch" and hasattr(values, "dim"):
+            if str(values.dtype) != "torch.float64":
+                raise TypeError(f"set_attr({name!r}): a tensor must be float64, got {values.dtype}")
+            if tuple(values.shape) != (N, W):
+                raise ValueError(f"set_attr({name!r}): a tensor must have shape ({N}, {W}) = (num_envs, width of {name}), got {tuple(values.shape)}")
+            if values.device.type != "cuda" or values.device.index != self._device_index:
+                raise ValueError(f"set_attr({name!r}): a tensor must live on the env's device (cuda:{self._device_index}), got {values.device}; "
+                                 "pass host values as a list or an array")
+            dev = values
+        else:
+            if isinstance(values, (list, tuple)):
+                if len(values) != N:
+                    raise ValueError("Values must be a list or tuple with length equal to the number of environments. "
+                                     f"Got `{len(values)}` values for {N} environments.")
+                per_env = list(values)
+            else:
+                per_env = [values] * N
+            rows = np.empty((N, W), dtype=np.float64)
+            for i, v in enumerate(per_env):
+                if isinstance(v, (str, bytes)) or v is None:
+                    raise TypeError(f"set_attr({name!r}) takes arrays of {W} numbers, got {type(v).__name__}")
+                try:
+                    a = np.asarray(v, dtype=np.float64)
+                except (TypeError, ValueError):
+                    raise TypeError(f"set_attr({name!r}) takes arrays of {W} numbers, got {type(v).__name__}") from None
+                if a.shape != (W,):
+                    raise ValueError(f"set_attr({name!r}): the value of a sub-environment must have shape ({W},) = the width of {name}, got {a.shape}")
+                rows[i] = a
+        what = dev if dev is not None else rows
+        finite = bool(np.isfinite(rows).all()) if dev is None else bool(self._torch_module().isfinite(dev).all())
+        if not finite:
+            raise ValueError(f"set_attr({name!r}): values must be finite")
+        if lo is not None and bool((what < lo).any()):
+            raise ValueError(f"set_attr({name!r}): values must be >= {lo}" + (" (MuJoCo's minimum friction)" if name == "geom_friction" else ""))
+        if not hasattr(self._engine.lib, "set_model_field"):
+            raise error.Error(f"set_attr({name!r}): the engine behind this env has no per-sub-environment model fields (mi_set_model_field)")
+        if name == "geom_friction":  # the compiler's rule (compiler.py: element-wise maximum of the two geoms), over the compiled pairs
+            m = self._compiled_model()
+            if dev is None:
+                send = np.maximum(rows[:, m.pair_geom1], rows[:, m.pair_geom2]).reshape(N, len(m.pair_geom1))
+            else:
+                t = self._torch_module()
+                g1, g2 = (t.as_tensor(np.asarray(g, dtype=np.int64), device=dev.device) for g in (m.pair_geom1, m.pair_geom2))
+                send = t.maximum(dev[:, g1], dev[:, g2]).reshape(N, len(m.pair_geom1))
+        else:
+            send = what
+        if dev is None:
+            self._engine.set_model_field(fid, np.ascontiguousarray(send))
+        else:
+            d = send.contiguous()
+            if self.output == "torch":
+                self._bind_stream()  # the transposition is ordered after what produced the tensor on torch's stream
+            else:
+                self._torch_module().cuda.current_stream(d.device).synchronize()
+            self._engine.set_model_field(fid, d.data_ptr(), on_device=True)
+            self._engine.synchronize()  # (the engine's stream is not the allocator's: keep `d` alive until the kernel ran)
+        if name == "geom_friction":
+            self._model_geom_friction = rows.copy() if dev is None else dev.clone()
+        self._env_attr_mask = self._env_attr_mask | (1 << fid)
+
+    def _torch_module(self):
+        return self._torch if "_torch" in self.__dict__ else __import__("torch")
 
     def _tendon_values(self, qpos, qvel):
         """data.ten_length / data.ten_velocity of mj_forward at (qpos, qvel): fixed tendons are linear in both."""

@@ -982,7 +982,8 @@ class HipVectorEnv(VectorEnv):
     def _env_attr_refusal(self) -> str | None:
         if self.ENV_ATTRS is None:
             return (f"{type(self).__name__}: per-sub-environment attributes (get_attr / set_attr) exist for CartPole-v1, Pendulum-v1, Acrobot-v1, "
-                    "MountainCar-v0 and MountainCarContinuous-v0 only")
+                    "MountainCar-v0 and MountainCarContinuous-v0 only (the MuJoCo v5 classes have model fields of their own: gravity, actuator_gear, "
+                    "dof_damping, geom_friction)")
         return None
 
     def _env_attr_id(self, name: str) -> int:

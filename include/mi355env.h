@@ -438,6 +438,29 @@ int mi_set_env_attr(mi_vecenv *env, int attr, const double *values, int on_devic
 int mi_get_env_attr(mi_vecenv *env, int attr, double *host_out);
 
 /*
+ * Per-sub-environment model fields of the MuJoCo kinds (added to ABI 10, which it leaves as it is): this engine's spelling of writing
+ * env.unwrapped.model.opt.gravity, .actuator_gear[:, 0], .dof_damping and the sliding friction of the compiled contact pairs (the element-wise
+ * maximum of the two geoms' geom_friction[:, 0]) in every sub-environment of a SyncVectorEnv.  An extension: the reference's scalar envs have no
+ * such attributes.  Like all MuJoCo physics here the parity with `mujoco` is UNPINNED (no `mujoco` build to take fixtures from); the CPU oracle,
+ * which takes the same fields as data, is the reference for these fields.  No compiled-model quantity is derived from any of them.
+ * mi_model_field_width: 3 / nu / nv / number of contact pairs (0 for a robot without any); < 0: not a MuJoCo kind, or no such field.
+ * mi_set_model_field: `values` = [num_envs][width] row-major float64, host (on_device = 0: checked and staged before the call returns) or device
+ * memory (on_device = 1: transposed into the env's rows by a small kernel on the env's stream; the caller has checked the values); NULL restores
+ * the compiled-in values.  Takes effect from the next mi_step / mi_rollout; resets do not undo it and mi_get_state does not include it.  The
+ * first call allocates the rows of all four fields at the compiled-in values and moves the env to the one-lane simulator for good (a robot whose
+ * default is the cooperative kernel gets slower: docs/results_log.md; MI355ENV_MJ_COOP=1 does not bring it back); the values live in device
+ * memory updated in place, so mi_step stays capturable and a HIP graph captured after the switch sees later calls.  That first call also loads
+ * the per-lane kernels' code object (kernels otherwise load on first use, which a stream capture must not trigger): a capture may follow it at once.
+ * Refused: a kind that is not a MuJoCo one (MI_ERR_UNSUPPORTED); a non-finite value, a negative damping, a friction below 1e-5 -- MuJoCo's
+ * documented minimum (MI_ERR_INVALID_ARGUMENT).
+ * mi_get_model_field: the current values into `host_out` ([num_envs][width] float64); synchronises.
+ */
+enum { MI_MODEL_GRAVITY = 0, MI_MODEL_ACTUATOR_GEAR = 1, MI_MODEL_DOF_DAMPING = 2, MI_MODEL_PAIR_FRICTION = 3, MI_MODEL_FIELD_COUNT = 4 };
+int mi_model_field_width(mi_vecenv *env, int field);
+int mi_set_model_field(mi_vecenv *env, int field, const double *values, int on_device);
+int mi_get_model_field(mi_vecenv *env, int field, double *host_out);
+
+/*
  * The per-sub-environment action wrappers (added to ABI 10, which it leaves as it is): gymnasium.wrappers.RepeatAction and StickyAction
  * (wrappers/stateful_action.py:16-220) around every scalar env, outside its TimeLimit -- what
  * make_vec(id, n, "sync", wrappers=(lambda e: StickyAction(RepeatAction(e, k), p, d),)) builds -- for the five classic-control kinds (not with

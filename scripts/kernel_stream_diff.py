@@ -1,7 +1,9 @@
 """Compare the gfx950 instruction streams of two builds of the library, kernel by kernel (device functions included): every symbol of the first
 file must exist in the second with the same sequence of (opcode, operands) -- but for the literal of a pc-relative address (s_getpc_b64 followed by
 s_add_u32 / s_addc_u32), which is the distance to a constant table and moves when code elsewhere grows.  Symbols only the second file has are
-listed as new.
+listed as new.  A function that several translation units emit (a non-template kernel or out-of-line device function of a shared header, each unit
+with its own flags) has several copies under one name: every copy of the first file must be among the second file's, in whatever order the units
+were linked.
 usage: python scripts/kernel_stream_diff.py OLD.so NEW.so      (exit status 1 if a common symbol differs or one is missing)"""
 import hashlib
 import os
@@ -17,8 +19,8 @@ OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
 
 
 def streams(path):
-    """{mangled symbol: (instruction count, sha256 of its "opcode operands" lines)} over every gfx950 code object of the file"""
-    out = {}
+    """{mangled symbol: set of (instruction count, sha256 of its "opcode operands" lines), one per distinct copy} over every gfx950 code object of the file"""
+    out, copies = {}, {}
     for co in extract_all(path):
         with tempfile.NamedTemporaryFile(suffix=".co") as f:
             f.write(co), f.flush()
@@ -29,6 +31,7 @@ def streams(path):
             if m:
                 cur = m.group(1)
                 out[cur] = [0, hashlib.sha256()]
+                copies.setdefault(cur, []).append(out[cur])
                 continue
             m = re.match(r"^\s+(\S+)\s*(.*?)\s*// [0-9A-F]+:", line)
             if m and cur:
@@ -42,16 +45,16 @@ def streams(path):
                     pcrel = 0
                 out[cur][0] += 1
                 out[cur][1].update(f"{op} {args}\n".encode())
-    return {k: (n, h.hexdigest()) for k, (n, h) in out.items()}
+    return {k: {(n, h.hexdigest()) for n, h in v} for k, v in copies.items()}
 
 
 def main():
     old, new = streams(sys.argv[1]), streams(sys.argv[2])
     missing = sorted(set(old) - set(new))
-    differ = sorted(k for k in old if k in new and old[k] != new[k])
+    differ = sorted(k for k in old if k in new and not old[k] <= new[k])
     added = sorted(set(new) - set(old))
     print(f"{len(old)} symbols in {sys.argv[1]}, {len(new)} in {sys.argv[2]}: {len(old) - len(missing) - len(differ)} identical, "
-          f"{len(differ)} differ, {len(missing)} missing, {len(added)} new ({sum(new[k][0] for k in added)} instructions)")
+          f"{len(differ)} differ, {len(missing)} missing, {len(added)} new ({sum(max(n for n, _ in new[k]) for k in added)} instructions)")
     names = subprocess.run(["c++filt"], input="\n".join(differ + missing + added), capture_output=True, text=True).stdout.splitlines()
     for tag, group in (("DIFFERS", differ), ("MISSING", missing), ("new", added)):
         for k in group:
