@@ -13,10 +13,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SOURCES = {  # translation unit -> the headers it depends on
     "engine.hip": ["envs_classic.h", "sincos_exact.h", "sincos_table.h", "pow_exact.h", "pow_tables.h", "wrappers_internal.h", "mjx_physics.h", "pcg64_dev.h",
                    "action_mask_internal.h",
-                   "mjx_core.h", "mjx_coop.h", "mjx_kernels.h", "ziggurat_tables.h",
+                   "mjx_core.h", "mjx_coop.h", "mjx_kernels.h", "log1p_exact.h", "ziggurat_tables.h",
                    os.path.join("generated", "mjx_models.h"), os.path.join("..", "..", "include", "mi355env.h")],
-    "physics16.hip": ["mjx_physics.h", "envs_classic.h", "sincos_exact.h", "pow_exact.h", "pcg64_dev.h", "mjx_core.h", "mjx_coop.h", "mjx_kernels.h", os.path.join("generated", "mjx_models.h")],
-    "physics32.hip": ["mjx_physics.h", "envs_classic.h", "sincos_exact.h", "pow_exact.h", "pcg64_dev.h", "mjx_core.h", "mjx_coop.h", "mjx_kernels.h", os.path.join("generated", "mjx_models.h")],
+    "physics16.hip": ["mjx_physics.h", "envs_classic.h", "sincos_exact.h", "pow_exact.h", "pcg64_dev.h", "mjx_core.h", "mjx_coop.h", "mjx_kernels.h", "log1p_exact.h", os.path.join("generated", "mjx_models.h")],
+    "physics32.hip": ["mjx_physics.h", "envs_classic.h", "sincos_exact.h", "pow_exact.h", "pcg64_dev.h", "mjx_core.h", "mjx_coop.h", "mjx_kernels.h", "log1p_exact.h", os.path.join("generated", "mjx_models.h")],
     "wrappers.hip": ["wrappers_internal.h", os.path.join("..", "..", "include", "mi355env.h")],
     # engine.hip once more with MI_CLASSIC_TU: only the classic-control kernels and their launchers (namespace mi_classic)
     "classic.hip": ["engine.hip", "envs_classic.h", "sincos_exact.h", "sincos_table.h", "pow_exact.h", "pow_tables.h", "wrappers_internal.h", "pcg64_dev.h",
@@ -24,7 +24,7 @@ SOURCES = {  # translation unit -> the headers it depends on
     # engine.hip once more with MI_MJ_MODEL_TU: only the one-lane MuJoCo kernels over the per-sub-environment model fields and their launchers
     # (namespace mi_mjmodel); a unit of its own so that its 77 kernels compile beside engine.o instead of after it
     "mjx_model.hip": ["engine.hip", "envs_classic.h", "sincos_exact.h", "sincos_table.h", "pow_exact.h", "pow_tables.h", "wrappers_internal.h", "pcg64_dev.h", "action_mask_internal.h",
-                      "mjx_physics.h", "mjx_core.h", "mjx_coop.h", "mjx_kernels.h", "ziggurat_tables.h",
+                      "mjx_physics.h", "mjx_core.h", "mjx_coop.h", "mjx_kernels.h", "log1p_exact.h", "ziggurat_tables.h",
                       os.path.join("generated", "mjx_models.h"), os.path.join("..", "..", "include", "mi355env.h")],
     # sample(mask=...) / sample(probability=...) on the action stream: kernels of their own behind action_mask_internal.h
     "action_mask.hip": ["action_mask_internal.h", "pcg64_dev.h"],

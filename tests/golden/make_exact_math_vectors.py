@@ -144,10 +144,14 @@ def npz_bytes(arrays):
 
 
 def write_flat(vec, path):
-    """what exact_math_check --vectors reads: 64-bit words; "EXMATHV1", then per function {id, n, n arguments, n results (sin, then cos)}"""
+    """what exact_math_check --vectors reads: 64-bit words; "EXMATHV1", then per function {id, n, n arguments, n results (sin, then cos)}.  `vec` may hold
+    a fifth function, "log1p": the (arguments, results) columns of tests/golden/normal_sampler.npz, which the caller adds"""
     with open(path, "wb") as f:
         f.write(b"EXMATHV1")
-        for ident, key in ((1, "trig"), (2, "fmod"), (3, "pow"), (4, "powf")):
+        for ident, key in ((1, "trig"), (2, "fmod"), (3, "pow"), (4, "powf"), (5, "log1p")):
+            if key not in vec:
+                assert key == "log1p"
+                continue
             cols = [np.ascontiguousarray(c).astype(np.uint64) for c in vec[key]]
             f.write(np.array([ident, cols[0].size], dtype="<u8").tobytes())
             for c in cols:

@@ -4,9 +4,10 @@
 // float64 division.  tests/test_sincos_exact.py and tests/test_pow_exact.py check them as HOST code; this program checks what the kernels execute:
 // every member of mi::ExactMathT<true> (constant Horner steps as inline-asm v_fma_f64) and mi::ExactMathT<false> (the builtin), called from
 // 256-thread workgroups with the tables and the fill_hot constants in LDS (init<true, true>(), default MI_HOT_TRIG), plus
-// SharedDivisor(b).under(a) behind the call sites' range tests and div_unscaled.
+// SharedDivisor(b).under(a) behind the call sites' range tests and div_unscaled; and log1p_exact.h's log1p_neg_unit (glibc's log1p on (-1, 0], the tail
+// of mjx::standard_normal), which has one form only.
 //
-// Reference: the running C library on the host side of this program (sin, cos, fmod, pow, powf looked up with dlsym, so that the compiler cannot fold
+// Reference: the running C library on the host side of this program (sin, cos, fmod, pow, powf, log1p looked up with dlsym, so that the compiler cannot fold
 // pow(x, 2.0) into x * x), and the host's a / b for the divisions.  Bit patterns are compared; NaN matches NaN; the sign of a zero counts.
 // With --vectors FILE the same kernels also run on recorded arguments and results (tests/golden/exact_math_vectors.npz written out flat by
 // tests/test_gpu_exact_math.py), which pins the device to the reference's libm whatever this machine's is.
@@ -33,13 +34,14 @@
 #include <vector>
 
 #include "envs_classic.h"
+#include "log1p_exact.h"
 
 typedef unsigned long long u64;
 
 // ---------------------------------------------------------------------------------------------------------------------------------------
 // device side
 // ---------------------------------------------------------------------------------------------------------------------------------------
-enum Op { SIN, COS, SINCOS, SPREAD, SIN_B, COS_B, SINCOS_B, COS_BL, MAIN_UNCHECKED, FMOD, SQ, SQ2, SQ3, SQ_PLAIN, SQF, SQF_PLAIN, DIV_SHARED, DIV_UNSCALED, N_OPS };
+enum Op { SIN, COS, SINCOS, SPREAD, SIN_B, COS_B, SINCOS_B, COS_BL, MAIN_UNCHECKED, FMOD, SQ, SQ2, SQ3, SQ_PLAIN, SQF, SQF_PLAIN, DIV_SHARED, DIV_UNSCALED, LOG1P, N_OPS };
 enum Dom { D_ALL, D_LIBM, D_BOUNDED, D_MAIN, D_FLAG };
 
 __device__ __host__ static inline bool libm_range(u64 xb) {  // where the unbounded forms are glibc's algorithm (or return NaN): not the ocml hand-over
@@ -130,6 +132,8 @@ __global__ __launch_bounds__(256) void member(const void *xv, const void *yv, vo
         o0[i] = q;
     } else if constexpr (OP == DIV_UNSCALED) {
         o0[i] = mi::div_unscaled(x[i], y[i]);
+    } else if constexpr (OP == LOG1P) {  // mjx::standard_normal's tail (mjx_kernels.h); not a member of the math policies: M only loads its tables
+        o0[i] = mi_log1p::log1p_neg_unit(x[i]);
     }
 }
 
@@ -186,7 +190,7 @@ __global__ __launch_bounds__(256) void identical(const u64 *a, const u64 *b, lon
 typedef double (*fn1_t)(double);
 typedef double (*fn2_t)(double, double);
 typedef float (*fn2f_t)(float, float);
-static fn1_t volatile ref_sin, ref_cos;
+static fn1_t volatile ref_sin, ref_cos, ref_log1p;
 static fn2_t volatile ref_fmod, ref_pow;
 static fn2f_t volatile ref_powf;
 static const double kTwoPi = 6.283185307179586;
@@ -456,7 +460,7 @@ static kern_t pick(int op) {
 #define PICK(o) \
     case o: return member<M, o>;
         PICK(SIN) PICK(COS) PICK(SINCOS) PICK(SPREAD) PICK(SIN_B) PICK(COS_B) PICK(SINCOS_B) PICK(COS_BL) PICK(MAIN_UNCHECKED) PICK(FMOD) PICK(SQ) PICK(SQ2) PICK(SQ3)
-        PICK(SQ_PLAIN) PICK(SQF) PICK(SQF_PLAIN) PICK(DIV_SHARED) PICK(DIV_UNSCALED)
+        PICK(SQ_PLAIN) PICK(SQF) PICK(SQF_PLAIN) PICK(DIV_SHARED) PICK(DIV_UNSCALED) PICK(LOG1P)
 #undef PICK
     }
     return nullptr;
@@ -641,6 +645,69 @@ static void check_div(const char *name, int op, const std::vector<double> &A, co
     h_y = nullptr;
 }
 
+// ---- log1p(-u), u in [0, 1): log1p_exact.h, the tail of mjx::standard_normal ------------------------------------------------------------------
+// Per binade [2^-(b+1), 2^-b) of u, b = 0 .. 52: u = m 2^-53 as Pcg64::next_double gives it (the low b significand bits zero), u with every significand bit
+// random, and the 2^15 doubles upwards of the binade's lower end; then the neighbourhoods of the routine's branch points.
+static const long kLog1pGrid = 1L << 17, kLog1pEdge = 1L << 15;
+static void log1p_inputs(std::vector<double> &X) {
+    for (int b = 0; b < 53; b++) {
+        for (long k = 0; k < 2 * kLog1pGrid; k++) {
+            u64 m = (rnd(900 + b, (u64)k) >> 12) | (1ull << 52);
+            if (k < kLog1pGrid) m &= ~((1ull << b) - 1);
+            X.push_back(-std::ldexp((double)m * 0x1p-53, -b));
+        }
+        const u64 lo = as_bits(std::ldexp(0.5, -b));
+        for (long k = 0; k < kLog1pEdge; k++) X.push_back(-as_double(lo + (u64)k));
+    }
+    // branch points: 2^-29 and 2^-54 (the short forms), 1 - sqrt(2)/2 (k = 0 from there down) and u = 1 - 2^-j (1 + x crosses a power of two), the ends
+    const double edges[] = {0x1p-29, 0x1p-54, 0.2928932188134524, 0.5, 0.75, 0.875, 0.9375, 1.0 - 0x1p-20, 1.0 - 0x1p-40};
+    for (double e : edges)
+        for (long d = -4096; d <= 4096; d++) X.push_back(-as_double(as_bits(e) + (u64)d));
+    for (long d = 0; d < 4096; d++) X.push_back(-as_double(as_bits(1.0) - 1 - (u64)d));  // the largest u
+    X.push_back(-0.0), X.push_back(-0x1p-53), X.push_back(-0x1p-52);
+}
+static void describe_log1p(const std::vector<double> &X) {
+    long binade[53] = {0}, grid = 0, short_form = 0, direct = 0, reduced = 0, zero = 0;
+    for (double x : X) {
+        const double u = -x;
+        if (u == 0.0) {
+            zero++;
+            continue;
+        }
+        int e;
+        std::frexp(u, &e);  // u in [2^(e-1), 2^e)
+        if (-e >= 0 && -e < 53) binade[-e]++;
+        grid += std::ldexp(u, 53) == std::floor(std::ldexp(u, 53));
+        const uint32_t ax = (uint32_t)(as_bits(x) >> 32) & 0x7fffffffu;
+        if (ax < 0x3e200000u) short_form++;
+        else if (ax <= 0x3fd2bec3u) direct++;
+        else reduced++;
+    }
+    std::printf("describe log1p_neg_unit arguments=%zu zero=%ld generator_grid=%ld below_2^-29=%ld direct=%ld reduced=%ld", X.size(), zero, grid, short_form, direct, reduced);
+    for (int b = 0; b < 53; b++) std::printf(" u_2^-%d=%ld", b + 1, binade[b]);
+    std::printf("\n");
+}
+static void check_log1p(const double *x, const u64 *ref, long total, const std::string &tag) {
+    for (long off = 0; off < total; off += kChunk) {
+        const long n = std::min<long>(kChunk, total - off);
+        upload((const u64 *)x + off, nullptr, ref + off, nullptr, n);
+        const kern_t k = pick<mi::ExactMathT<true>>(LOG1P);
+        Case &c = get_case("log1p_neg_unit." + tag), &again = get_case("relaunch.log1p_neg_unit." + tag);
+        for (int launch = 0; launch < 2; launch++) {
+            hipLaunchKernelGGL(k, grid(n), dim3(256), 0, 0, d_x, d_y, launch ? d_b0 : d_a0, launch ? d_b1 : d_a1, n, 0);
+            CHECK(hipGetLastError());
+        }
+        CHECK(hipMemset(d_res, 0, sizeof(Result)));
+        hipLaunchKernelGGL(compare64, grid(n), dim3(256), 0, 0, (const u64 *)d_a0, (const u64 *)d_r0, (const u64 *)d_x, (const u64 *)d_a1, n, (int)D_ALL, d_res);
+        CHECK(hipGetLastError());
+        report(c, fetch(), h_r0, P_F64);
+        CHECK(hipMemset(d_res, 0, sizeof(Result)));
+        hipLaunchKernelGGL(identical, grid(n), dim3(256), 0, 0, (const u64 *)d_a0, (const u64 *)d_b0, n, d_res);
+        CHECK(hipGetLastError());
+        report(again, fetch(), nullptr, P_F64);
+    }
+}
+
 // the float32 scan: all 2^32 patterns, `step` at a time; with_gpu = false: only count (--describe)
 static void sqf_scan(bool with_gpu, bool with_libm) {
     const long step = 2 * kChunk;
@@ -668,8 +735,9 @@ static void sqf_scan(bool with_gpu, bool with_libm) {
     std::printf("describe sqf patterns=%llu powf_ne_product=%llu\n", patterns, differ);
 }
 
-// ---- the recorded vectors (--vectors): u64 words; "EXMATHV1", then sections {id, n, payload}: 1 trig x sin cos, 2 fmod x r, 3 pow x r, 4 powf x r (32-bit values widened)
-static bool read_vectors(const char *path, std::vector<std::vector<u64>> sec[5]) {
+// ---- the recorded vectors (--vectors): u64 words; "EXMATHV1", then sections {id, n, payload}: 1 trig x sin cos, 2 fmod x r, 3 pow x r, 4 powf x r (32-bit values widened),
+// 5 log1p x r (tests/golden/normal_sampler.npz: the calls of its tail lanes)
+static bool read_vectors(const char *path, std::vector<std::vector<u64>> sec[6]) {
     FILE *f = std::fopen(path, "rb");
     if (!f) return false;
     std::vector<u64> w;
@@ -682,15 +750,15 @@ static bool read_vectors(const char *path, std::vector<std::vector<u64>> sec[5])
     while (at + 2 <= w.size()) {
         const u64 id = w[at], n = w[at + 1];
         const int arrays = id == 1 ? 3 : 2;
-        if (id < 1 || id > 4 || at + 2 + arrays * n > w.size()) return false;
+        if (id < 1 || id > 5 || at + 2 + arrays * n > w.size()) return false;
         for (int a = 0; a < arrays; a++) sec[id].emplace_back(w.begin() + at + 2 + a * n, w.begin() + at + 2 + (a + 1) * n);
         at += 2 + arrays * n;
     }
     return at == w.size();
 }
 static int vectors_leg(const char *path) {
-    std::vector<std::vector<u64>> sec[5];
-    if (!read_vectors(path, sec) || sec[1].size() != 3 || sec[2].size() != 2 || sec[3].size() != 2 || sec[4].size() != 2) {
+    std::vector<std::vector<u64>> sec[6];
+    if (!read_vectors(path, sec) || sec[1].size() != 3 || sec[2].size() != 2 || sec[3].size() != 2 || sec[4].size() != 2 || sec[5].size() != 2) {
         std::printf("vectors: cannot read %s\n", path);
         return 2;
     }
@@ -706,7 +774,8 @@ static int vectors_leg(const char *path) {
     std::vector<uint32_t> x32(nf), r32(nf);
     for (long k = 0; k < nf; k++) x32[k] = (uint32_t)sec[4][0][k], r32[k] = (uint32_t)sec[4][1][k];
     check_sqf(x32.data(), r32.data(), nf, 0, "vectors");
-    std::printf("vectors: %zu sin / cos, %zu fmod, %zu pow, %ld powf rows\n", sec[1][0].size(), fx.size(), sec[3][0].size(), nf);
+    check_log1p((const double *)sec[5][0].data(), sec[5][1].data(), (long)sec[5][0].size(), "vectors");
+    std::printf("vectors: %zu sin / cos, %zu fmod, %zu pow, %ld powf, %zu log1p rows\n", sec[1][0].size(), fx.size(), sec[3][0].size(), nf, sec[5][0].size());
     return 0;
 }
 
@@ -726,9 +795,9 @@ int main(int argc, char **argv) {
     void *libm = dlopen("libm.so.6", RTLD_NOW);
     if (!libm) libm = RTLD_DEFAULT;
     ref_sin = (fn1_t)dlsym(libm, "sin"), ref_cos = (fn1_t)dlsym(libm, "cos"), ref_fmod = (fn2_t)dlsym(libm, "fmod"), ref_pow = (fn2_t)dlsym(libm, "pow");
-    ref_powf = (fn2f_t)dlsym(libm, "powf");
-    if (!ref_sin || !ref_cos || !ref_fmod || !ref_pow || !ref_powf) {
-        std::printf("libm: sin / cos / fmod / pow / powf not found\n");
+    ref_powf = (fn2f_t)dlsym(libm, "powf"), ref_log1p = (fn1_t)dlsym(libm, "log1p");
+    if (!ref_sin || !ref_cos || !ref_fmod || !ref_pow || !ref_powf || !ref_log1p) {
+        std::printf("libm: sin / cos / fmod / pow / powf / log1p not found\n");
         return 2;
     }
     // known answers of glibc's FMA build (the tests/test_sincos_exact.py and tests/test_pow_exact.py guards)
@@ -815,6 +884,18 @@ int main(int argc, char **argv) {
             std::printf("describe sq arguments=%zu pow_ne_product=%ld\n", X.size(), (long)dx);
             std::printf("describe sq_groups arguments=%zu pow_ne_product=%ld all_hard_groups_sq2=%ld all_hard_groups_sq3=%ld\n", F.size(), df, all_hard[2], all_hard[3]);
             if (!describe) check_sq(X, rx, "libm"), check_groups(F, rf, "libm");
+        }
+        {
+            std::vector<double> X;
+            log1p_inputs(X);
+            describe_log1p(X);
+            if (!describe) {
+                std::vector<u64> ref(X.size());
+                parallel_for((long)X.size(), [&](long lo, long hi, int) {
+                    for (long k = lo; k < hi; k++) ref[k] = as_bits(ref_log1p(X[k]));
+                });
+                check_log1p(X.data(), ref.data(), (long)X.size(), "libm");
+            }
         }
         sqf_scan(!describe, expected);
     }

@@ -3,7 +3,7 @@
   * the program cross-compiles for gfx950 with the library's flags;
   * its --describe mode (no GPU, no HIP call) shows that the inputs contain what the check claims to cover: every branch range of s_sin.c in both the
     sorted and the shuffled sin / cos set, enough arguments with pow(x, 2) != x * x, all 2^32 float32 patterns, numerators on both sides of
-    SharedDivisor::ordinary(), every binade of fmod's quotient up to 2^52;
+    SharedDivisor::ordinary(), every binade of fmod's quotient up to 2^52, every binade of log1p's u = -x down to the generator's 2^-53;
   * the recorded vectors (tests/golden/exact_math_vectors.npz) are what tests/golden/make_exact_math_vectors.py writes, byte for byte, and the running
     libm and the host builds of the headers (tests/sincos_host, tests/pow_host) reproduce every row.
 """
@@ -27,6 +27,12 @@ def vectors_module():
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
     return mod
+
+
+def with_log1p(vectors):
+    """the recorded vectors plus the log1p calls of tests/golden/normal_sampler.npz's tail lanes (arguments -u, glibc's results), as write_flat takes them"""
+    with np.load(os.path.join(HERE, "golden", "normal_sampler.npz"), allow_pickle=False) as z:
+        return dict(vectors, log1p=(z["log1p_x"], z["log1p_r"]))
 
 
 def compile_check(exe, contract="off"):
@@ -101,6 +107,16 @@ def test_fmod_inputs_populate_every_quotient_binade_up_to_2_52(described):
     for b in range(20, 52):  # the quotient in [2^b, 2^(b+1)): up to 2^52, the routine's advertised limit
         assert f[f"quotient_2^{b}"] >= 2 ** 16, b
     assert f["quotient_below_2^20"] >= 3_000_000
+
+
+def test_log1p_inputs_cover_every_binade_of_u_and_every_branch(described):
+    d = described["log1p_neg_unit"]
+    for b in range(1, 54):  # u in [2^-b, 2^-(b-1)): the generator's u = m 2^-53 reaches down to 2^-53
+        assert d[f"u_2^-{b}"] >= 2 * 2 ** 17 + 2 ** 15, b
+    assert d["arguments"] >= 53 * (2 * 2 ** 17 + 2 ** 15) and d["zero"] >= 1
+    assert d["generator_grid"] >= 53 * 2 ** 17
+    # the routine's three forms: x - x^2 / 2 below 2^-29 (25 binades), f = x down to 1 - sqrt(2)/2, the reduction 1 + x = 2^k (1 + f) beyond
+    assert d["below_2^-29"] >= 24 * 2 ** 18 and d["direct"] >= 27 * 2 ** 18 and d["reduced"] >= 2 ** 18
 
 
 # ---- the recorded vectors ------------------------------------------------------------------------------------------------------------------
@@ -178,3 +194,10 @@ def test_flat_vector_file_round_trips(tmp_path):
             assert np.array_equal(w[at + 2 + k * n: at + 2 + (k + 1) * n], col.astype(np.uint64))
         at += 2 + len(v[key]) * n
     assert at == w.size
+    # ... and with the fifth section, as tests/test_gpu_exact_math.py writes it: the four above unchanged, then the log1p rows
+    v5 = with_log1p(v)
+    mk.write_flat(v5, path)
+    w5 = np.fromfile(path, dtype="<u8")
+    n = v5["log1p"][0].size
+    assert n >= 3000 and np.array_equal(w5[:at], w) and w5[at] == 5 and w5[at + 1] == n and w5.size == at + 2 + 2 * n
+    assert np.array_equal(w5[at + 2: at + 2 + n], v5["log1p"][0]) and np.array_equal(w5[at + 2 + n:], v5["log1p"][1])

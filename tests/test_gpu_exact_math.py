@@ -1,5 +1,6 @@
 """-m gpu: the DEVICE build of sincos_exact.h, pow_exact.h and the division helpers of envs_classic.h, member by member, bit for bit
-(tests/hip/exact_math_check.hip, compiled here with the library's flags):
+(tests/hip/exact_math_check.hip, compiled here with the library's flags), and of log1p_exact.h (log1p on (-1, 0], the tail of the MuJoCo resets' normal
+sampler: against the log1p calls recorded in tests/golden/normal_sampler.npz and against the running libm over every binade of u):
 
   * every member of mi::ExactMathT<true> and mi::ExactMathT<false> against the recorded vectors of tests/golden/exact_math_vectors.npz (the reference's
     libm, whatever this machine's is), SharedDivisor behind its call sites' range tests and div_unscaled against the host's IEEE division;
@@ -16,7 +17,7 @@ import subprocess
 
 import pytest
 
-from test_exact_math_check import HIPCC, compile_check, vectors_module
+from test_exact_math_check import HIPCC, compile_check, vectors_module, with_log1p
 
 pytestmark = pytest.mark.gpu
 
@@ -48,9 +49,10 @@ def expected_cases(trig_sets, other_set, sqf_set):
     return names
 
 
-VECTOR_CASES = expected_cases(["vectors"], "vectors", "vectors")
+# log1p_exact.h's log1p_neg_unit (the tail of mjx::standard_normal) has one form: no policy in its case names
+VECTOR_CASES = expected_cases(["vectors"], "vectors", "vectors") + ["log1p_neg_unit.vectors", "relaunch.log1p_neg_unit.vectors"]
 DIVISION_CASES = ["shared_divisor.ieee", "relaunch.shared_divisor.ieee", "div_unscaled.ieee", "relaunch.div_unscaled.ieee"]
-LIBM_CASES = expected_cases(["sorted", "shuffled"], "libm", "all")
+LIBM_CASES = expected_cases(["sorted", "shuffled"], "libm", "all") + ["log1p_neg_unit.libm", "relaunch.log1p_neg_unit.libm"]
 
 
 @pytest.fixture(scope="module")
@@ -61,7 +63,7 @@ def run(tmp_path_factory):
     exe = compile_check(str(d / "exact_math_check"))
     mk = vectors_module()
     flat = str(d / "vectors.bin")
-    mk.write_flat(mk.load(), flat)
+    mk.write_flat(with_log1p(mk.load()), flat)
     try:
         p = subprocess.run([exe, "--vectors", flat], capture_output=True, text=True, timeout=RUN_TIMEOUT)
     except subprocess.TimeoutExpired as e:
@@ -125,6 +127,8 @@ def test_device_build_equals_the_running_libm(run):
             return 20_000_000 if "sincos_main_unchecked" in name and not name.startswith("relaunch") else 90_000_000
         if name.startswith("sq_is_plain"):
             return 9_000_000
+        if "log1p_neg_unit" in name:
+            return 53 * (2 * 2 ** 17 + 2 ** 15)  # per binade of u: the generator's grid, full significands, the binade's lower end
         return 2_000_000
 
     assert_clean(run, LIBM_CASES, floor)

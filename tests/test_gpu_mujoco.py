@@ -232,6 +232,55 @@ def test_cooperative_kernel_equals_one_lane_simulator(name, monkeypatch):
     ser.close(), coop.close()
 
 
+@pytest.mark.parametrize("name,n,offset", [("ant", 1, 0), ("ant", 3, 1), ("ant", 7, 0), ("humanoid", 1, 0), ("humanoid", 3, 1)])
+def test_cooperative_kernel_at_ragged_batch_sizes(name, n, offset, oracle_factory):
+    """mj_physics_kernel retires the groups of a wavefront that lie past the end of the batch (mjx_physics.h: `env < d.N ? env : 0`); every other
+    test of Ant and Humanoid uses a multiple of 64 sub-environments.  Here the last (only) wavefront is partial: 1, 3 and 7 of Ant's four 16-lane
+    groups per wavefront, 1 and 3 of Humanoid's two 32-lane groups; env_index_offset = 1 at N = 3, so that the partial wavefront does not start at
+    seed index 0.  The cooperative default against the ORACLE in the regime of test_reset_bit_exact_and_windowed_parity (atol 1e-8 over
+    re-synchronised windows; flags and generator words exact), 10 steps; then rollout(4) against four step() calls, bit for bit."""
+    import torch
+
+    T, window = 10, (10 if name == "ant" else 5)
+    kw = dict(num_envs=n, env_index_offset=offset)
+    gpu = gymnasium_amd.make_vec(IDS[name], **kw)
+    cpu = gymnasium_amd.make_vec(IDS[name], _engine_factory=oracle_factory, **kw)
+    og, _ = gpu.reset(seed=11)
+    oc, _ = cpu.reset(seed=11)
+    nstate = NSTATE[name]
+    assert og.shape[0] == n and np.array_equal(og[:, :nstate], oc[:, :nstate]), "reset state must be bit-exact"
+    np.testing.assert_allclose(og[:, nstate:], oc[:, nstate:], rtol=1e-9, atol=1e-9)
+    assert np.array_equal(gpu.get_rng_state(), cpu.get_rng_state())
+    gpu.action_space.seed(2)
+    worst = 0.0
+    for t in range(T):
+        a = gpu.action_space.sample()
+        og, rg, teg, trg, _ = gpu.step(a)
+        oc, rc, tec, trc, _ = cpu.step(a)
+        assert np.array_equal(teg, tec) and np.array_equal(trg, trc), f"{name} flags t={t}"
+        worst = max(worst, float(np.abs(og - oc).max()))
+        np.testing.assert_allclose(og, oc, rtol=0, atol=1e-8, err_msg=f"{name} obs t={t}")
+        np.testing.assert_allclose(rg, rc, rtol=0, atol=1e-8, err_msg=f"{name} reward t={t}")
+        if (t + 1) % window == 0:
+            gpu.set_state(*cpu.get_state())
+    assert np.array_equal(gpu.get_rng_state(), cpu.get_rng_state())
+    sg, sc = gpu.statistics(), cpu.statistics()
+    assert all(sg[k] == sc[k] for k in ("env_steps", "reset_steps", "episodes", "length_sum"))
+    print(f"{name} x {n} (offset {offset}): max |obs diff| {worst:.3e} over {T} steps (resync every {window})")
+    gpu.close(), cpu.close()
+    a, b = (gymnasium_amd.make_vec(IDS[name], output="torch", **kw) for _ in range(2))
+    a.reset(seed=3), b.reset(seed=3)
+    a.action_space.seed(7), b.action_space.seed(7)
+    out = a.rollout(4)
+    for t in range(4):
+        act = b.action_space.sample()
+        o, r, te, tr, _ = b.step(torch.from_numpy(act).cuda())
+        assert np.array_equal(out["actions"][t].cpu().numpy(), act), f"sampled actions t={t}"
+        assert torch.equal(out["obs"][t], o) and torch.equal(out["rewards"][t], r) and torch.equal(out["terminations"][t], te) and torch.equal(out["truncations"][t], tr)
+    assert np.array_equal(a.get_rng_state(), b.get_rng_state()) and np.array_equal(a.get_state()[0], b.get_state()[0])
+    a.close(), b.close()
+
+
 @pytest.mark.parametrize("name,kw", [("ant", {}), ("humanoid", {}), ("humanoid", {"terminate_when_unhealthy": False})], ids=["ant", "humanoid", "humanoid-on-the-ground"])
 def test_full_batch_cooperative_equals_one_lane_at_the_benchmark_shape(name, kw, monkeypatch):
     """the WHOLE batch of BASELINE configs[3] / [4]'s per-GPU shape -- 32 768 robots -- stepped by the cooperative kernel and by the one-lane
