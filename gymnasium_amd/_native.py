@@ -67,6 +67,9 @@ MI_F16, MI_I32, MI_U8 = 4, 5, 6  # mi_dtype: targets of transform_observations(O
 OBS_AFFINE, OBS_CAST, OBS_MAX_DIM, ONE_HOT_MAX_PARTS = 0, 1, 1024, 4  # MI_OBS_*, MI_ONE_HOT_MAX_PARTS
 # NormalizeObservation / NormalizeReward around every scalar env: per-sub-environment statistics (csrc/per_env_normalize.hip; added to ABI 10 as well).
 WRAPPER_SYMBOLS += ["per_env_normalize_step", "per_env_normalize_steps"]
+# FrameStackObservation / DelayObservation / TimeAwareObservation around every scalar env (csrc/stateful_observation.hip; added to ABI 10 as well).
+WRAPPER_SYMBOLS += ["stateful_observation_step", "stateful_observation_steps"]
+SO_FRAME_STACK, SO_DELAY, SO_TIME_AWARE = 0, 1, 2  # MI_SO_*
 
 
 class MiConfig(C.Structure):
@@ -117,6 +120,15 @@ class MiPerEnvState(C.Structure):
                 ("obs_dtype", C.c_int32), ("obs_dim", C.c_int32), ("obs_update", C.c_int32), ("obs_epsilon", C.c_double), ("acc", C.c_void_p),
                 ("ret_mean", C.c_void_p), ("ret_var", C.c_void_p), ("ret_count", C.c_void_p), ("was_done", C.c_void_p), ("gamma", C.c_double),
                 ("reward_epsilon", C.c_double), ("reward_update", C.c_int32), ("autoreset_mode", C.c_int32)]
+
+
+class MiStatefulObservationState(C.Structure):
+    """mi_stateful_observation_state: the settings and device arrays of one wrappers.per_env.FrameStackObservation / DelayObservation /
+    TimeAwareObservation (include/mi355env.h)."""
+    _fields_ = [("kind", C.c_int32), ("in_dtype", C.c_int32), ("out_dtype", C.c_int32), ("dim", C.c_int32), ("depth", C.c_int32), ("padding", C.c_int32),
+                ("normalize_time", C.c_int32), ("max_timesteps", C.c_int32), ("autoreset_mode", C.c_int32), ("reserved", C.c_int32),
+                ("padding_value", C.c_void_p), ("carried_in", C.c_void_p), ("carried_out", C.c_void_p), ("count_in", C.c_void_p),
+                ("count_out", C.c_void_p), ("pending_in", C.c_void_p), ("pending_out", C.c_void_p)]
 
 
 class MiStats(C.Structure):
@@ -199,6 +211,11 @@ class NativeLib:
             self.action_sample_weighted = f("action_sample_weighted", [vp, vp, vp, i32], i32)
             self.action_get_buffered = f("action_get_buffered", [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)], i32)
             self.action_set_buffered = f("action_set_buffered", [vp, C.c_uint32, C.c_uint32], i32)
+            try:
+                self.stateful_observation_step = f("stateful_observation_step", [i32, vp, C.POINTER(MiStatefulObservationState), i32, i32] + [vp] * 9, i32)
+                self.stateful_observation_steps = f("stateful_observation_steps", [i32, vp, C.POINTER(MiStatefulObservationState), i32, i32] + [vp] * 4, i32)
+            except ImportError:  # (likewise: the per_env stateful observation wrappers refuse at their first call)
+                pass
             try:
                 self.set_step_wrappers = f("set_step_wrappers", [vp, i32, dbl, i32], i32)
             except ImportError:  # an ABI 10 build from before the entry point (MI355ENV_LIBRARY, A/B runs): HipVectorEnv.set_step_wrappers refuses

@@ -35,6 +35,9 @@ SOURCES = {  # translation unit -> the headers it depends on
     # NormalizeObservation / NormalizeReward around every scalar env (mi_per_env_normalize_step / _steps): per-lane recurrences, default flag set --
     # bit parity rests on -ffp-contract=off and on hipcc's default correctly rounded float32 division and sqrtf
     "per_env_normalize.hip": ["per_env_normalize_internal.h", os.path.join("..", "..", "include", "mi355env.h")],
+    # FrameStackObservation / DelayObservation / TimeAwareObservation around every scalar env (mi_stateful_observation_step / _steps): data movement
+    # decided in stateful_observation_internal.h, default flag set
+    "stateful_observation.hip": ["stateful_observation_internal.h", os.path.join("..", "..", "include", "mi355env.h")],
 }
 OUT = os.path.join(HERE, "libmi355env.so")
 ARCH = "gfx950"

@@ -302,8 +302,62 @@ class Tuple(Space):
         return isinstance(other, Tuple) and self.spaces == other.spaces
 
 
+class Dict(Space):
+    """A dictionary of spaces (spaces/dict.py:17-250), as far as TimeAwareObservation(flatten=False) needs it: samples are dicts, a plain ``dict``
+    of spaces is ordered by its sorted keys, keyword spaces follow."""
+
+    def __init__(self, spaces=None, seed=None, **spaces_kwargs):
+        spaces = {} if spaces is None else dict(spaces)
+        try:
+            spaces = dict(sorted(spaces.items()))
+        except TypeError:  # (keys that do not compare: the insertion order stays)
+            pass
+        for key, sp in spaces_kwargs.items():
+            if key in spaces:
+                raise ValueError(f"Dict space keyword '{key}' already exists in the spaces dictionary.")
+            spaces[key] = sp
+        self.spaces = spaces
+        for key, sp in self.spaces.items():
+            assert isinstance(sp, Space), f"Dict space element is not an instance of Space: key='{key}', space={sp}"
+        super().__init__(None, None, None)
+        if seed is not None:
+            self.seed(seed)
+
+    def seed(self, seed=None):
+        if seed is None:
+            return {key: sp.seed(None) for key, sp in self.spaces.items()}
+        if isinstance(seed, (int, np.integer)):
+            super().seed(int(seed))
+            subseeds = self.np_random.integers(np.iinfo(np.int32).max, size=len(self.spaces))
+            return {key: sp.seed(int(ss)) for (key, sp), ss in zip(self.spaces.items(), subseeds)}
+        return {key: self.spaces[key].seed(seed[key]) for key in self.spaces}
+
+    def sample(self, mask=None, probability=None):
+        return {key: sp.sample() for key, sp in self.spaces.items()}
+
+    def contains(self, x) -> bool:
+        return isinstance(x, dict) and x.keys() == self.spaces.keys() and all(x[key] in sp for key, sp in self.spaces.items())
+
+    def keys(self):
+        return self.spaces.keys()
+
+    def __getitem__(self, key):
+        return self.spaces[key]
+
+    def __len__(self):
+        return len(self.spaces)
+
+    def __repr__(self):
+        return "Dict(" + ", ".join(f"{key!r}: {sp}" for key, sp in self.spaces.items()) + ")"
+
+    def __eq__(self, other):
+        return isinstance(other, Dict) and self.spaces == other.spaces
+
+
 def batch_space(space, n=1):
-    """n independent copies of ``space`` as one batched space (space_utils.py:51-100; Box, Discrete and Tuple only)."""
+    """n independent copies of ``space`` as one batched space (space_utils.py:51-100; Box, Discrete, Tuple and Dict only)."""
+    if isinstance(space, Dict):
+        return Dict({key: batch_space(sp, n) for key, sp in space.spaces.items()}, seed=deepcopy(space._np_random))
     if isinstance(space, Tuple):
         return Tuple(tuple(batch_space(sp, n) for sp in space.spaces), seed=deepcopy(space._np_random))
     if isinstance(space, Box):

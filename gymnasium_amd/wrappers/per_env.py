@@ -38,6 +38,11 @@ state for all rows.  Normalising float64 observations with ``update_running_mean
 (the reference: in float32) -- outside the tested domain.
 
 There is no CPU implementation: over a backend without the device engine the constructors validate their arguments and then raise ``error.Error``.
+
+``FrameStackObservation``, ``DelayObservation`` and ``TimeAwareObservation`` (stateful_observation.py:304-461, 35-103, 106-301) are the same kind of
+wrapper -- scalar, around every sub-environment, state in HBM (csrc/stateful_observation.hip) -- as layers of their own that go over the env, the
+action wrappers, the two normalisers above and one another: see ``_StatefulObservation`` below.  They build their spaces on any backend and ask for
+the device engine at the first call.
 """
 from __future__ import annotations
 
@@ -419,3 +424,349 @@ class NormalizeReward(_PerEnvWrapper):
     def pending_autoreset(self, value):
         self._allocate()
         self._write(self._was_done, np.asarray(value, dtype=np.bool_), np.uint8)
+
+
+# -- FrameStackObservation / DelayObservation / TimeAwareObservation around every sub-environment ------------------------------------------------------
+_PADDING = {"reset": 0, "zero": 1, "_custom": 2}
+
+
+class _StatefulObservation(VectorWrapper):
+    """What the three stateful observation wrappers of gymnasium/wrappers/stateful_observation.py:35-461 share: placement below the vector level,
+    device state per sub-environment, and reset / step / rollout as ONE launch each behind the wrapped env's own (csrc/stateful_observation.hip).
+
+    Each wrapper is its own layer: it goes over a ``HipVectorEnv`` with float32 / float64 Box observations, ``RepeatAction`` / ``StickyAction``,
+    ``per_env.NormalizeObservation`` / ``NormalizeReward`` or another wrapper of this family, in any order; every vector wrapper goes above.  The
+    ``per_env`` normalisers do NOT go over this family (their placement check refuses it).  It keeps its own record of the rows that finished in the
+    last step (under NEXT_STEP their next step is the autoreset step: the scalar wrapper's ``reset()``).
+
+      * ``reset``: rows outside ``options["reset_mask"]`` keep their state and return what they returned last (the wrapper keeps a reference to the
+        last batch it handed out: do not modify a returned tensor in place if masked resets follow).
+      * ``step``: NEXT_STEP, SAME_STEP (``infos["final_obs"]`` is the wrapper's output for the final observation, the returned observation its output
+        for the reset observation) and DISABLED.
+      * ``rollout``: NEXT_STEP and DISABLED, equal to T x ``step()`` in values and in the state left behind, with the state carried in from before
+        (frames of the running episode, a part-filled queue, a running counter, a pending autoreset); refused under SAME_STEP.  Directly over a
+        DISABLED env the trajectory is collected from T ``step()`` calls, as the normalisers do.
+      * ``capture_steps``: refused.
+
+    There is no CPU implementation: over a backend without the device engine the constructors validate their arguments and build their spaces --
+    which can be inspected --, and the first ``reset`` / ``step`` / ``rollout`` raises ``error.Error``.
+    Out of scope: ``MaxAndSkipObservation`` (an inner-step wrapper: it belongs in the step kernel next to ``RepeatAction``), fusing these passes into
+    the step / rollout kernels, rollouts under SAME_STEP, ToyText observations, the normalisers above these wrappers."""
+
+    _what = "observations"
+    _kind = None
+
+    def __init__(self, env):
+        name = type(self).__name__
+        e = env
+        while isinstance(e, (_StatefulObservation, _PerEnvWrapper, RepeatAction, StickyAction)):
+            e = e.env
+        if isinstance(e, VectorWrapper) or not hasattr(e, "_engine"):
+            raise error.Error(f"per_env.{name} wraps every SUB-environment, below the vector level: it goes over a HipVectorEnv (gymnasium_amd.make_vec(...)), "
+                              f"RepeatAction / StickyAction or other per_env wrappers, and the vector wrappers go above it; got {type(e).__name__}")
+        space = env.single_observation_space
+        if not isinstance(space, spaces.Box) or np.dtype(space.dtype) not in (np.float32, np.float64):
+            raise error.Error(f"per_env.{name} takes float32 / float64 Box observations, the sub-environments have {space}")
+        super().__init__(env)
+        self._base, self._inner = e, env
+        self._np_dtype = np.dtype(space.dtype)
+        self._in_shape = tuple(space.shape)
+        self._dim = int(np.prod(space.shape)) if space.shape else 1
+        self._code = _native.MI_F32 if self._np_dtype == np.float32 else _native.MI_F64
+        self._struct, self._allocated, self._last = None, False, None
+        _close_fusion(env)
+
+    # -- device state ---------------------------------------------------------------------------------------------------------------------
+    def _dev(self):
+        return getattr(self._base, "_device_index", 0)
+
+    def _device(self):
+        return _torch().device("cuda", self._dev())
+
+    @staticmethod
+    def _tdtype_of(np_dtype):
+        torch = _torch()
+        return {np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float64, np.dtype(np.int32): torch.int32}[np.dtype(np_dtype)]
+
+    def _require(self):
+        base = self._base
+        if getattr(base, "_engine_factory", None) is not None or not hasattr(getattr(base._engine, "lib", None), "stateful_observation_step"):
+            raise error.Error(f"per_env.{type(self).__name__} needs the device engine (mi_stateful_observation_step): its state lives in HBM and there is "
+                              "no CPU implementation")
+
+    def _allocate(self):
+        """The state arrays, twice each: a launch reads one set and writes the other."""
+        if self._allocated:
+            return
+        self._require()
+        torch, dev, n = _torch(), self._device(), self.num_envs
+        self._pending = [torch.zeros((n,), dtype=torch.uint8, device=dev) for _ in range(2)]
+        self._count = [torch.zeros((n,), dtype=torch.int32, device=dev) for _ in range(2)]
+        self._carried = self._carried_arrays(torch, dev, n)
+        self._last = torch.zeros((n,) + self._out_row, dtype=self._tdtype_of(self._out_np_dtype), device=dev)
+        s = self._struct = _native.MiStatefulObservationState()
+        s.kind, s.in_dtype, s.dim, s.autoreset_mode = self._kind, self._code, self._dim, _MODES[self._base.autoreset_mode]
+        s.out_dtype = {np.dtype(np.float32): _native.MI_F32, np.dtype(np.float64): _native.MI_F64, np.dtype(np.int32): _native.MI_I32}[self._out_np_dtype]
+        self._configure(s)
+        self._allocated = True
+
+    def _carried_arrays(self, torch, dev, n):
+        return None
+
+    def _configure(self, s):
+        pass
+
+    def _state(self):
+        self._allocate()
+        s = self._struct
+        s.pending_in, s.pending_out = self._pending[0].data_ptr(), self._pending[1].data_ptr()
+        s.count_in, s.count_out = self._count[0].data_ptr(), self._count[1].data_ptr()
+        if self._carried is not None:
+            s.carried_in, s.carried_out = self._carried[0].data_ptr(), self._carried[1].data_ptr()
+        return s
+
+    def _launched(self, last):
+        """After a launch: what was written is the state now."""
+        self._pending.reverse(), self._count.reverse()
+        if self._carried is not None:
+            self._carried.reverse()
+        self._last = last
+
+    @property
+    def pending_autoreset(self):
+        """The rows that finished in the last step (``[N]`` bool): under NEXT_STEP their next step resets them."""
+        self._allocate()
+        return self._pending[0].cpu().numpy().astype(np.bool_)
+
+    # -- staging ----------------------------------------------------------------------------------------------------------------------------
+    def _stage(self, obs, steps=None):
+        x, was_tensor = self._to_device(obs)
+        lead = self.num_envs if steps is None else steps * self.num_envs
+        if x.dtype != self._tdtype_of(self._np_dtype) or x.numel() != lead * self._dim:
+            raise ValueError(f"per_env.{type(self).__name__}: expected {self._np_dtype} observations of {lead} x {self._dim} elements, got {x.dtype} "
+                             f"{tuple(x.shape)}")
+        if x.device != self._device():
+            x = x.to(self._device())
+        return x, was_tensor
+
+    def _new_out(self, steps=None):
+        lead = (self.num_envs,) if steps is None else (steps, self.num_envs)
+        return _torch().empty(lead + self._out_row, dtype=self._tdtype_of(self._out_np_dtype), device=self._device())
+
+    def _launch_step(self, is_reset, x, out, row_mask=None, fin=None, fin_out=None, fin_mask=None, te=None, tr=None):
+        torch = _torch()
+        dev = self._device()
+        lib = _native.load_library()
+        state = self._state()
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        lib.check(lib.stateful_observation_step(dev.index, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), C.byref(state), self.num_envs,
+                                                int(is_reset), p(x), p(out), p(row_mask), p(self._last) if row_mask is not None else None, p(fin), p(fin_out),
+                                                p(fin_mask), p(te), p(tr)))
+        self._launched(out)
+
+    # what the wrapper hands out for an input batch and its own output (TimeAwareObservation(flatten=False) returns a dict)
+    def _wrap(self, given, out, was_tensor):
+        return self._back(out, was_tensor)
+
+    def _wrap_row(self, given_row, out_row):
+        return out_row
+
+    # -- API --------------------------------------------------------------------------------------------------------------------------------
+    def reset(self, *, seed=None, options=None):
+        torch = _torch()
+        self._require()
+        mask = options.get("reset_mask") if options is not None else None
+        mask = None if mask is None else np.ascontiguousarray(mask).view(np.uint8).copy()
+        obs, infos = self.env.reset(seed=seed, options=options)
+        mask_t = None if mask is None else torch.from_numpy(mask).to(self._device())
+        x, was_tensor = self._stage(obs)
+        out = self._new_out()
+        self._launch_step(True, x, out, row_mask=mask_t)
+        return self._wrap(obs, out, was_tensor), infos
+
+    def step(self, actions):
+        torch = _torch()
+        self._require()
+        obs, reward, terminated, truncated, infos = self.env.step(actions)
+        x, was_tensor = self._stage(obs)
+        out = self._new_out()
+        dev = self._device()
+        kw = {}
+        same = self._base.autoreset_mode == AutoresetMode.SAME_STEP
+        if same and "final_obs" in infos:
+            fmask = infos["_final_obs"]
+            if was_tensor:
+                fin, fm = infos["final_obs"].contiguous(), _PerEnvWrapper._u8(fmask.contiguous())
+            else:  # the NumPy infos hold an object array of the finished rows' observations
+                rows = np.zeros((self.num_envs, self._dim), dtype=self._np_dtype)
+                for i in np.flatnonzero(fmask):
+                    rows[i] = np.asarray(infos["final_obs"][i]).reshape(-1)
+                fin, fm = self._to_device(rows)[0], self._to_device(np.asarray(fmask).view(np.uint8))[0]
+            kw.update(fin=fin.to(dev), fin_mask=fm.to(dev), fin_out=self._new_out())
+        if not same:
+            te, tr = (_PerEnvWrapper._u8(self._to_device(f)[0]) for f in (terminated, truncated))
+            kw.update(te=te.to(dev), tr=tr.to(dev))
+        self._launch_step(False, x, out, **kw)
+        if "fin_out" in kw:
+            infos = dict(infos)
+            if was_tensor:
+                infos["final_obs"] = self._wrap(infos["final_obs"], kw["fin_out"], True)
+            else:
+                host, arr = kw["fin_out"].cpu().numpy(), np.full(self.num_envs, None, dtype=object)
+                for i in np.flatnonzero(infos["_final_obs"]):
+                    arr[i] = self._wrap_row(infos["final_obs"][i], host[i].copy())
+                infos["final_obs"] = arr
+        return self._wrap(obs, out, was_tensor), reward, terminated, truncated, infos
+
+    def rollout(self, num_steps, actions=None, **kwargs):
+        """T x ``step()`` through the wrapper: the wrapped ``rollout``, then ONE launch over the whole trajectory (mi_stateful_observation_steps)."""
+        torch = _torch()
+        self._require()
+        if self._base.autoreset_mode == AutoresetMode.SAME_STEP:
+            raise error.Error(f"rollout() through per_env.{type(self).__name__} under SAME_STEP is not supported: a row that ends returns its final and its "
+                              "reset observation in one step; use step(), or NEXT_STEP / DISABLED")
+        if self._base.autoreset_mode == AutoresetMode.DISABLED and not isinstance(self.env, (_StatefulObservation, _PerEnvWrapper)):
+            out = _PerEnvWrapper._rollout_by_steps(self, int(num_steps), actions, **kwargs)
+        else:
+            out = dict(self.env.rollout(num_steps, actions, **kwargs))
+        steps = int(out["rewards"].shape[0])
+        if steps < 1:
+            return out
+        x, _ = self._stage(out["obs"], steps)
+        res = self._new_out(steps)
+        dev = self._device()
+        te, tr = (_PerEnvWrapper._u8(out[k].contiguous()) for k in ("terminations", "truncations"))
+        lib = _native.load_library()
+        lib.check(lib.stateful_observation_steps(dev.index, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), C.byref(self._state()), steps,
+                                                 self.num_envs, C.c_void_p(x.data_ptr()), C.c_void_p(res.data_ptr()), C.c_void_p(te.data_ptr()),
+                                                 C.c_void_p(tr.data_ptr())))
+        self._launched(res[-1].clone())  # (not a view: it would keep the whole trajectory alive)
+        out["obs"] = self._wrap(out["obs"], res, True)
+        return out
+
+    def capture_steps(self, *args, **kwargs):
+        _refuse_capture(self, self._what)
+
+
+class FrameStackObservation(_StatefulObservation):
+    """``SyncVectorEnv`` over scalar envs each wrapped in ``gymnasium.wrappers.FrameStackObservation(env, stack_size, padding_type=...)``
+    (stateful_observation.py:304-461): observations ``[N, stack_size, ...]`` in the observations' dtype, the newest frame last.  Every reset of a row
+    (``reset()``, a masked reset, the NEXT_STEP autoreset step, the SAME_STEP reset) fills ``stack_size - 1`` slots with the padding -- the reset
+    observation itself (``"reset"``), zeros (``"zero"``) or a custom observation -- and the last slot with the reset observation."""
+
+    _kind = _native.SO_FRAME_STACK
+
+    def __init__(self, env, stack_size: int, *, padding_type="reset"):
+        if not np.issubdtype(type(stack_size), np.integer):
+            raise TypeError(f"The stack_size is expected to be an integer, actual type: {type(stack_size)}")
+        if not 0 < stack_size:
+            raise ValueError(f"The stack_size needs to be greater than zero, actual value: {stack_size}")
+        super().__init__(env)
+        space = env.single_observation_space
+        self._padding_value = None
+        if isinstance(padding_type, str) and (padding_type == "reset" or padding_type == "zero"):
+            pass
+        elif padding_type in space:
+            self._padding_value = np.ascontiguousarray(np.asarray(padding_type, dtype=self._np_dtype).reshape(-1))
+            padding_type = "_custom"
+        elif isinstance(padding_type, str):
+            raise ValueError(f"Unexpected `padding_type`, expected 'reset', 'zero' or a custom observation space, actual value: {padding_type!r}")
+        else:
+            raise ValueError(f"Unexpected `padding_type`, expected 'reset', 'zero' or a custom observation space, actual value: {padding_type!r} not an "
+                             f"instance of env observation ({space})")
+        self.stack_size, self.padding_type = int(stack_size), padding_type
+        self._out_np_dtype, self._out_row = self._np_dtype, (self.stack_size,) + self._in_shape
+        self.single_observation_space = batch_space(space, self.stack_size)
+        self.observation_space = batch_space(self.single_observation_space, self.env.num_envs)
+
+    def _configure(self, s):
+        s.depth, s.padding = self.stack_size, _PADDING[self.padding_type]
+        if self._padding_value is not None:
+            self._padding_t = _torch().from_numpy(self._padding_value.copy()).to(self._device())
+            s.padding_value = self._padding_t.data_ptr()
+
+    def _state(self):
+        s = super()._state()
+        s.carried_in = self._last.data_ptr()  # the stack returned last IS the state
+        return s
+
+
+class DelayObservation(_StatefulObservation):
+    """``SyncVectorEnv`` over scalar envs each wrapped in ``gymnasium.wrappers.DelayObservation(env, delay)`` (stateful_observation.py:35-103): a row's
+    queue empties at every reset of the row; until it holds more than ``delay`` observations the row returns zeros, then the observation from
+    ``delay`` steps earlier.  ``delay = 0`` passes the observations through."""
+
+    _kind = _native.SO_DELAY
+
+    def __init__(self, env, delay: int):
+        if not np.issubdtype(type(delay), np.integer):
+            raise TypeError(f"The delay is expected to be an integer, actual type: {type(delay)}")
+        if not 0 <= delay:
+            raise ValueError(f"The delay needs to be greater than zero, actual value: {delay}")
+        super().__init__(env)
+        self.delay = int(delay)
+        self._out_np_dtype, self._out_row = self._np_dtype, self._in_shape
+        self.single_observation_space = env.single_observation_space
+        self.observation_space = env.observation_space
+
+    def _carried_arrays(self, torch, dev, n):
+        if self.delay == 0:
+            return None
+        return [torch.zeros((n, self.delay, self._dim), dtype=self._tdtype_of(self._np_dtype), device=dev) for _ in range(2)]
+
+    def _configure(self, s):
+        s.depth = self.delay
+
+
+class TimeAwareObservation(_StatefulObservation):
+    """``SyncVectorEnv`` over scalar envs each wrapped in ``gymnasium.wrappers.TimeAwareObservation(env, flatten, normalize_time)``
+    (stateful_observation.py:106-301): every row keeps a counter that every reset of the row zeroes and every ``step()`` of the wrapper increments
+    (over ``RepeatAction``: outer steps); ``max_timesteps`` is the TimeLimit the engine runs with.  ``flatten=True``: ``[N, D + 1]`` with the time in
+    the last column -- int32 time makes the flattened Box float64 (exact), the normalised time ``float32(t / max_timesteps)`` keeps the observations'
+    dtype.  ``flatten=False``: ``{"obs": [N, ...], "time": [N, 1]}`` in a ``Dict`` space.  ``dict_time_key`` is accepted for signature parity (no
+    environment here has a Dict observation)."""
+
+    _kind = _native.SO_TIME_AWARE
+
+    def __init__(self, env, flatten: bool = True, normalize_time: bool = False, *, dict_time_key: str = "time"):
+        super().__init__(env)
+        self.flatten, self.normalize_time = flatten, normalize_time
+        limit = getattr(self._base, "max_episode_steps", None)
+        if not limit:
+            raise ValueError("The environment must be wrapped by a TimeLimit wrapper or the spec specify a `max_episode_steps`.")
+        self.max_timesteps = int(limit)
+        space = env.single_observation_space
+        time_space = spaces.Box(0.0, 1.0) if normalize_time else spaces.Box(0, self.max_timesteps, dtype=np.int32)
+        if flatten:  # spaces/utils.py flatten_space of Dict(obs=..., time=...): the flattened bounds side by side in the common dtype
+            self._out_np_dtype = np.dtype(np.result_type(space.dtype, time_space.dtype))
+            self._out_row = (self._dim + 1,)
+            self.single_observation_space = spaces.Box(low=np.concatenate([space.low.flatten(), time_space.low.flatten()]),
+                                                       high=np.concatenate([space.high.flatten(), time_space.high.flatten()]), dtype=self._out_np_dtype)
+        else:
+            self._out_np_dtype, self._out_row = np.dtype(time_space.dtype), (1,)
+            self.single_observation_space = spaces.Dict(obs=space, time=time_space)
+        self.observation_space = batch_space(self.single_observation_space, self.env.num_envs)
+
+    def _configure(self, s):
+        s.normalize_time, s.max_timesteps = int(bool(self.normalize_time)), self.max_timesteps
+        if not self.flatten:  # the launch writes the time column alone; the observations pass through untouched
+            s.dim, s.in_dtype = 0, _native.MI_F32
+
+    def _launch_step(self, is_reset, x, out, fin=None, **kw):
+        if not self.flatten:
+            x, fin = None, None
+        super()._launch_step(is_reset, x, out, fin=fin, **kw)
+
+    def _wrap(self, given, out, was_tensor):
+        if self.flatten:
+            return self._back(out, was_tensor)
+        return {"obs": given, "time": self._back(out, was_tensor)}
+
+    def _wrap_row(self, given_row, out_row):
+        return out_row if self.flatten else {"obs": given_row, "time": out_row}
+
+    @property
+    def timesteps(self):
+        """Every sub-environment's ``timesteps`` (stateful_observation.py:216), ``[N]`` int32."""
+        self._allocate()
+        return self._count[0].cpu().numpy()

@@ -639,6 +639,62 @@ int mi_per_env_normalize_step(int device, void *hip_stream, const mi_per_env_sta
 int mi_per_env_normalize_steps(int device, void *hip_stream, const mi_per_env_state *state, int T, int num_envs, const void *obs, void *obs_out,
                                const double *reward, const uint8_t *terminated, const uint8_t *truncated, double *reward_out);
 
+/*
+ * gymnasium.wrappers.FrameStackObservation / DelayObservation / TimeAwareObservation around EVERY SCALAR env
+ * (wrappers/stateful_observation.py:304-461, 35-103, 106-301 under vector/sync_vector_env.py:207-337) -- what SyncVectorEnv over wrapped scalar
+ * envs returns (csrc/stateful_observation.hip, index arithmetic in csrc/stateful_observation_internal.h; added to ABI 10, which they leave as it
+ * is).  The wrappers move data; the only arithmetic is the normalised time, float32(t / max_timesteps) with the quotient taken in float64, and
+ * the exact widenings to float64.  Both calls only enqueue ONE kernel on hip_stream: no allocation, no synchronisation.  One state struct per
+ * wrapper; all state lives in device arrays the caller owns (N = num_envs, D = dim, the flat size of one input observation).  A call READS the
+ * `_in` arrays and WRITES every entry of the `_out` arrays (never the same memory); the caller swaps them after the call.
+ *
+ *   MI_SO_FRAME_STACK  depth = stack_size k >= 1.  out [N][k][D] of in_dtype.  carried_in: the stack returned last, [N][k][D] (the caller
+ *                      keeps the output; carried_out is not used).  padding: 0 the reset observation, 1 zeros, 2 padding_value ([D] in_dtype).
+ *   MI_SO_DELAY        depth = delay >= 0.  out [N][D] of in_dtype.  carried_in / carried_out: the last `delay` raw observations [N][delay][D],
+ *                      oldest first; count_in / count_out [N] int32: how many of them (the last ones) the row's queue holds.
+ *   MI_SO_TIME_AWARE   out [N][D + 1] of out_dtype: the observation widened, then the time -- int32 counter (normalize_time = 0) or
+ *                      float32(t / max_timesteps) -- converted to out_dtype: MI_F64 (float64 observations; float32 ones with the integer
+ *                      time), MI_F32 (float32 observations with the normalised time).  dim = 0 gives the time column alone, [N][1] MI_I32 or
+ *                      MI_F32 (flatten=False).  count_in / count_out [N] int32: the counters.
+ *   pending_in / pending_out [N] uint8, all kinds: the rows that finished in the previous step (under NEXT_STEP their next step is the reset).
+ *
+ * mi_stateful_observation_step, what one reset() (is_reset = 1) or step() returns.  A reset: rows in row_mask ([N] uint8, NULL = all) reset,
+ *   the others keep their state and get prev_out[row] (the batch returned last; NULL: zeros).  A step: under NEXT_STEP the rows of pending_in
+ *   reset, the others step; under SAME_STEP (final_obs / final_out / final_mask, or all NULL when no row finished) a row of final_mask first
+ *   takes final_obs as a step -- final_out, laid out like out; zeros outside the mask -- and then resets with obs.  terminated / truncated [N]:
+ *   the step's flags (pending_out; not read by a reset or under SAME_STEP).
+ * mi_stateful_observation_steps, the T consecutive step() calls of a rollout: obs [T][N][D], out [T][N][...], terminated / truncated [T][N].
+ *   FrameStack and Delay are one write stream over all T * N outputs (each looks back at most k - 1 / delay steps through the flags), TimeAware
+ *   walks the T steps per row.  Values and the state left behind equal T calls of mi_stateful_observation_step, except that FrameStack's new
+ *   carried state is out[T - 1], which the caller keeps.  NEXT_STEP and DISABLED only (MI_ERR_UNSUPPORTED under SAME_STEP).
+ * The elements of one step (N * k * D) must stay below 2^31; the trajectory is indexed in 64 bits.
+ */
+enum { MI_SO_FRAME_STACK = 0, MI_SO_DELAY = 1, MI_SO_TIME_AWARE = 2 };
+typedef struct mi_stateful_observation_state {
+    int32_t kind;             /* MI_SO_* */
+    int32_t in_dtype;         /* MI_F32 / MI_F64 */
+    int32_t out_dtype;        /* FrameStack / Delay: in_dtype; TimeAware: see above */
+    int32_t dim;              /* D */
+    int32_t depth;            /* stack_size / delay */
+    int32_t padding;          /* FrameStack: 0 reset / 1 zero / 2 custom */
+    int32_t normalize_time;   /* TimeAware */
+    int32_t max_timesteps;    /* TimeAware with normalize_time */
+    int32_t autoreset_mode;   /* mi_autoreset_mode */
+    int32_t reserved;
+    const void *padding_value;
+    const void *carried_in;
+    void *carried_out;
+    const int32_t *count_in;
+    int32_t *count_out;
+    const uint8_t *pending_in;
+    uint8_t *pending_out;
+} mi_stateful_observation_state;
+int mi_stateful_observation_step(int device, void *hip_stream, const mi_stateful_observation_state *state, int num_envs, int is_reset, const void *obs,
+                                 void *out, const uint8_t *row_mask, const void *prev_out, const void *final_obs, void *final_out,
+                                 const uint8_t *final_mask, const uint8_t *terminated, const uint8_t *truncated);
+int mi_stateful_observation_steps(int device, void *hip_stream, const mi_stateful_observation_state *state, int T, int num_envs, const void *obs,
+                                  void *out, const uint8_t *terminated, const uint8_t *truncated);
+
 /* The same three wrappers as the OUTPUT STAGE of the step kernel (classic-control kinds): mi_step / mi_step_async then return the wrapped
  * observations and rewards in place of the raw ones -- one extra launch per step (the normalisations need the statistics of the WHOLE batch,
  * stateful_observation.py:146-152) instead of the ten of the stand-alone passes, and no staging for host callers: the values are rewritten
