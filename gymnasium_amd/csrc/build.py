@@ -6,39 +6,15 @@ Flags that matter for parity: -ffp-contract=off (hipcc's device default is `fast
 the CPU reference does not perform) and no -ffast-math.
 """
 import os
+import re
 import subprocess
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SOURCES = {  # translation unit -> the headers it depends on
-    "engine.hip": ["envs_classic.h", "sincos_exact.h", "sincos_table.h", "pow_exact.h", "pow_tables.h", "wrappers_internal.h", "mjx_physics.h", "pcg64_dev.h",
-                   "action_mask_internal.h",
-                   "mjx_core.h", "mjx_coop.h", "mjx_kernels.h", "log1p_exact.h", "ziggurat_tables.h",
-                   os.path.join("generated", "mjx_models.h"), os.path.join("..", "..", "include", "mi355env.h")],
-    "physics16.hip": ["mjx_physics.h", "envs_classic.h", "sincos_exact.h", "pow_exact.h", "pcg64_dev.h", "mjx_core.h", "mjx_coop.h", "mjx_kernels.h", "log1p_exact.h", os.path.join("generated", "mjx_models.h")],
-    "physics32.hip": ["mjx_physics.h", "envs_classic.h", "sincos_exact.h", "pow_exact.h", "pcg64_dev.h", "mjx_core.h", "mjx_coop.h", "mjx_kernels.h", "log1p_exact.h", os.path.join("generated", "mjx_models.h")],
-    "wrappers.hip": ["wrappers_internal.h", os.path.join("..", "..", "include", "mi355env.h")],
-    # engine.hip once more with MI_CLASSIC_TU: only the classic-control kernels and their launchers (namespace mi_classic)
-    "classic.hip": ["engine.hip", "envs_classic.h", "sincos_exact.h", "sincos_table.h", "pow_exact.h", "pow_tables.h", "wrappers_internal.h", "pcg64_dev.h",
-                    "action_mask_internal.h", os.path.join("..", "..", "include", "mi355env.h")],
-    # engine.hip once more with MI_MJ_MODEL_TU: only the one-lane MuJoCo kernels over the per-sub-environment model fields and their launchers
-    # (namespace mi_mjmodel); a unit of its own so that its 77 kernels compile beside engine.o instead of after it
-    "mjx_model.hip": ["engine.hip", "envs_classic.h", "sincos_exact.h", "sincos_table.h", "pow_exact.h", "pow_tables.h", "wrappers_internal.h", "pcg64_dev.h", "action_mask_internal.h",
-                      "mjx_physics.h", "mjx_core.h", "mjx_coop.h", "mjx_kernels.h", "log1p_exact.h", "ziggurat_tables.h",
-                      os.path.join("generated", "mjx_models.h"), os.path.join("..", "..", "include", "mi355env.h")],
-    # sample(mask=...) / sample(probability=...) on the action stream: kernels of their own behind action_mask_internal.h
-    "action_mask.hip": ["action_mask_internal.h", "pcg64_dev.h"],
-    # ClipAction / RescaleAction over an action block in HBM (mi_transform_actions): one elementwise kernel, default flag set
-    "action_wrappers.hip": [os.path.join("..", "..", "include", "mi355env.h")],
-    # RescaleObservation / DtypeObservation / FlattenObservation over an observation block in HBM (mi_transform_observations, mi_one_hot): default flag set
-    "observation_wrappers.hip": [os.path.join("..", "..", "include", "mi355env.h")],
-    # NormalizeObservation / NormalizeReward around every scalar env (mi_per_env_normalize_step / _steps): per-lane recurrences, default flag set --
-    # bit parity rests on -ffp-contract=off and on hipcc's default correctly rounded float32 division and sqrtf
-    "per_env_normalize.hip": ["per_env_normalize_internal.h", os.path.join("..", "..", "include", "mi355env.h")],
-    # FrameStackObservation / DelayObservation / TimeAwareObservation around every scalar env (mi_stateful_observation_step / _steps): data movement
-    # decided in stateful_observation_internal.h, default flag set
-    "stateful_observation.hip": ["stateful_observation_internal.h", os.path.join("..", "..", "include", "mi355env.h")],
-}
+# The translation units, each compiled on its own and linked into one library; what a unit is and why it is one stands at its head.  A unit's
+# dependencies are the quoted includes it reaches (includes()), so there is no header list to keep.
+SOURCES = ["engine.hip", "physics16.hip", "physics32.hip", "wrappers.hip", "classic.hip", "mjx_model.hip", "action_mask.hip", "action_wrappers.hip",
+           "observation_wrappers.hip", "per_env_normalize.hip", "stateful_observation.hip"]
 OUT = os.path.join(HERE, "libmi355env.so")
 ARCH = "gfx950"
 # Per translation unit, on top of FLAGS: LLVM's iterative GCN scheduler for the cooperative physics kernels.  With ONE wavefront per SIMD it
@@ -68,6 +44,7 @@ NO_MLICM = ["-mllvm", "-disable-machine-licm"]
 # classic parity test is array_equal) and the two-build comparison of tests/test_gpu_scheduler_guard.py covers this unit as well.
 # (`iterative-ilp` crashes clang-22 on engine.hip, `iterative-maxocc` stops with "Illegal instruction detected: Operand has incorrect register class".)
 MAXILP = ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]
+# Every unit not named here builds with FLAGS alone (the default flag set its head refers to).
 TU_FLAGS = {"physics16.hip": ITERATIVE + SINK, "physics32.hip": ITERATIVE + SINK, "classic.hip": MAXILP}
 FLAGS = ["-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-fvisibility=hidden", "-Wall", "-Wno-unused-function", "-Wno-missing-braces"]
 
@@ -82,11 +59,27 @@ def generate_models() -> None:
     codegen.generate()
 
 
-def _stale(target: str, deps) -> bool:
+def includes(path: str, seen=None) -> set:
+    """Every file `path` reaches through `#include "..."` lines, resolved relative to the including file (conditional includes count too: too many
+    dependencies only rebuild more)."""
+    seen = set() if seen is None else seen
+    with open(path) as f:
+        names = re.findall(r'^\s*#\s*include\s*"([^"]+)"', f.read(), re.M)
+    for name in names:
+        dep = os.path.normpath(os.path.join(os.path.dirname(path), name))
+        if dep not in seen:
+            seen.add(dep)
+            includes(dep, seen)
+    return seen
+
+
+def _stale(target: str, src: str) -> bool:
+    """`target` is older than the unit `src`, a file it includes or this script (call after generate_models(): the closure reads generated/)."""
     if not os.path.exists(target):
         return True
     t = os.path.getmtime(target)
-    return any(os.path.getmtime(os.path.join(HERE, f)) > t for f in deps)
+    unit = os.path.join(HERE, src)
+    return any(os.path.getmtime(f) > t for f in {unit, os.path.join(HERE, "build.py")} | includes(unit))
 
 
 OUT_REF = os.path.join(HERE, "libmi355env_ref.so")
@@ -103,13 +96,13 @@ def build(force: bool = False, verbose: bool = True, reference_scheduler: bool =
     out = OUT_REF if reference_scheduler else OUT
     objs, relink = [], force or not os.path.exists(out)
     jobs = []
-    for src, headers in SOURCES.items():
+    for src in SOURCES:
         tu_flags = [] if reference_scheduler else TU_FLAGS.get(src, [])
         # translation units whose flags do not differ between the two builds share one object file
         suffix = "_ref.o" if (reference_scheduler and TU_FLAGS.get(src)) else ".o"
         obj = os.path.join(HERE, os.path.splitext(src)[0] + suffix)
         objs.append(obj)
-        if force or _stale(obj, [src, "build.py"] + headers):
+        if force or _stale(obj, src):
             cmd = [hipcc, f"--offload-arch={ARCH}", *FLAGS, *tu_flags, *os.environ.get("MI355ENV_HIPCC_FLAGS", "").split(), "-c", "-o", obj,
                    os.path.join(HERE, src)]
             if verbose:
@@ -133,11 +126,11 @@ def build_both(verbose: bool = True):
     generate_models()
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     jobs = []
-    for src, headers in SOURCES.items():
+    for src in SOURCES:
         if not TU_FLAGS.get(src):
             continue
         obj = os.path.join(HERE, os.path.splitext(src)[0] + "_ref.o")
-        if _stale(obj, [src, "build.py"] + headers):
+        if _stale(obj, src):
             cmd = [hipcc, f"--offload-arch={ARCH}", *FLAGS, *os.environ.get("MI355ENV_HIPCC_FLAGS", "").split(), "-c", "-o", obj, os.path.join(HERE, src)]
             if verbose:
                 print(" ".join(cmd), flush=True)

@@ -1,5 +1,7 @@
 // engine.hip -- libmi355env.so: lockstep vector-environment kernels for MI355X (gfx950) and the C ABI of
-// include/mi355env.h.
+// include/mi355env.h.  The classic-control and ToyText kernels and the host side are here; what the units of the library share is in
+// engine_types.h (structs, mi_vecenv, cross-unit launch functions) and lane_common.h (device helpers), the per-lane MuJoCo kernels in
+// mj_glue_kernels.h, which this file instantiates over the stock models and mjx_model.hip over the per-sub-environment model fields.
 //
 // Execution model: one sub-environment per lane, 256-thread workgroups (4 wavefronts of 64, one per SIMD of a CU);
 // at num_envs = 65536 the grid is 256 workgroups = one per CU.  Sub-environment state is struct-of-arrays in HBM
@@ -35,92 +37,15 @@
 // measured +6.4 % (CartPole), +5.8 % (Pendulum), +2.7 % (MountainCarContinuous) against the default max-occupancy scheduler, with every result bit
 // unchanged (scheduling reorders, it does not re-associate; tests/test_gpu_parity.py compares array_equal) -- and -1 ... -2 % on the ToyText and
 // one-lane MuJoCo kernels, which therefore stay in engine.o on the default scheduler (profiles/r04_maxilp_classic.txt).
-#include "../../include/mi355env.h"
-#include "envs_classic.h"
+#include "engine_types.h"
+#include "lane_common.h"
 #include "wrappers_internal.h"
-#include "pcg64_dev.h"
-#include "action_mask_internal.h"
 #ifndef MI_CLASSIC_TU
-#include "mjx_kernels.h"
-#include "mjx_coop.h"
+#include "mj_glue_kernels.h"
 #include "mjx_physics.h"
 #endif
 
-using namespace mi;
-
 namespace {
-
-constexpr int kBlock = 256;  // 4 wavefronts: one per SIMD of a CU
-constexpr int kErrInvalidAction = 1, kErrDisabledStepped = 2;
-constexpr uint32_t kFlagShift = 30, kElapsedMask = (1u << kFlagShift) - 1u;
-
-}  // namespace
-// Plain types that cross the boundary between the two translation units (launcher arguments, members of mi_vecenv): a named namespace, so that
-// mi_classic's functions have external linkage.
-namespace mi_internal {
-// Transition table of a tabular (ToyText) environment, device pointers (mi_tabular_load).
-struct TabTable {
-    int nS, nA, K;
-    const double *csprob, *prob, *reward, *isd;
-    const int32_t *next, *count;
-    const uint8_t *term;
-    const int32_t *env_table;  // [N] table of each sub-environment when there are several (mi_tabular_table.num_tables > 1), else nullptr
-};
-
-// Per-sub-environment model fields of a MuJoCo env (mi_set_model_field), as they ride in DevEnv.
-struct MjModelDev {
-    int tab_ints[3];     // tab.nS, tab.nA, tab.K of the union below: always 0 here
-    const double *rows;  // [mjx::LaneFields::WIDTH][N], read by the mjx::LaneModel instantiations only; NULL until the first mi_set_model_field
-};
-// Device view of one vector environment (passed by value as a kernel argument).
-struct DevEnv {
-    double *state;       // [S][N]   physics state, component-major
-    uint32_t *meta;      // [N]      TimeLimit elapsed steps (bits 0..29) | flags (bits 30..31)
-    uint64_t *rng;       // [4][N]   PCG64 {state_hi, state_lo, inc_hi, inc_lo}
-    double *ep_ret;      // [N]      running episode return
-    int32_t *ep_len;     // [N]      running episode length
-    uint64_t *blk_count; // [grid][4] per-workgroup totals: env_steps, reset_steps, episodes, length_sum
-    double *blk_ret;     // [grid]    per-workgroup sum of finished-episode returns
-    int *error;          // sticky device error word
-    int N;
-    int max_steps;
-    int solver_newton;   // MI_CFG_SOLVER_NEWTON (one-lane MuJoCo kernels; the cooperative kernel is chosen at launch)
-    int tab_fickle_rows; // MI_ENV_TABULAR with params[2] != 0 (Taxi's fickle passenger): the state has a third row (TabLane::aux)
-    EnvParams P;
-    // By kind; the size and layout of DevEnv are the table's, as before the union.  Kernels of EVERY kind read tab.nS (seed_words_kernel /
-    // seed_sequence_kernel: < 0 is the Blackjack marker), so the pointer of the MuJoCo kinds lies behind the table's three integers, which stay 0 for
-    // them: it shares its bytes with tab.csprob, which only the tabular kernels read.
-    union {
-        TabTable tab;  // the tabular kinds
-        MjModelDev mj; // the MuJoCo kinds
-    };
-};
-static_assert(offsetof(MjModelDev, rows) == offsetof(TabTable, csprob) && sizeof(MjModelDev) <= sizeof(TabTable), "mj.rows must alias a pointer of the table, not nS / nA / K");
-// Per-sub-environment attributes (mi_set_env_attr; the *AttrT types of envs_classic.h): attribute a of sub-environment i is rows[a * N + i] if bit
-// a of `mask` is set, else its construction value.  An extra argument of step_kernel / rollout_kernel, which the other types do not read.
-struct AttrDev {
-    const double *rows;  // [A][N] component-major, like DevEnv::state
-    uint32_t mask;       // wave-uniform
-};
-// The per-sub-environment action wrappers of the reference (wrappers/stateful_action.py) folded into the step (mi_set_step_wrappers): the last
-// argument of step_wrapped_kernel / rollout_wrapped_kernel, which the env runs instead of step_kernel / rollout_kernel / rollout_infos_kernel then.
-// Everything but the two arrays is wave-uniform.
-struct WrapDev {
-    int repeats;            // RepeatAction(env, repeats): inner steps per step(); 0: no such wrapper
-    int sticky_duration;    // StickyAction(env, p, duration); 0: no such wrapper
-    double sticky_p;
-    uint64_t *last_action;  // [N] StickyAction.last_action: the bits of the lane's last effective action (E::Act)
-    uint32_t *sticky_word;  // [N] bit 31: last_action is not None; bits 0..30: repeats_taken (is_sticky_actions <=> > 0; num_repeats is then the duration)
-};
-}  // namespace mi_internal
-using namespace mi_internal;
-namespace {
-
-struct LaneStats {
-    uint32_t env_steps, reset_steps, episodes;
-    uint64_t length_sum;
-    double return_sum;
-};
 
 template <class E>
 struct Lane {
@@ -139,14 +64,6 @@ MI_DEV void load_lane(const DevEnv &d, int i, Lane<E> &L) {
     L.elapsed = m & kElapsedMask, L.flags = m >> kFlagShift;
     L.ep_ret = d.ep_ret[i], L.ep_len = d.ep_len[i];
     trig_invalidate(L.trig);
-}
-// step_kernel's form of load_lane + load_rng: the raw words are REQUESTED here and looked at only after the math tables are staged (arrive()),
-// held opaque in between -- the compiler otherwise starts on them at once (the first 128-bit multiply of the generator is speculated out of
-// the reset branch), i.e. waits for this trip to memory before it requests the tables: two trips in a row where one does.
-template <class T>
-MI_DEV void hold_opaque(T &x) {
-    static_assert(sizeof(T) == 4 || sizeof(T) == 8, "one or two VGPRs");
-    asm volatile("" : "+v"(x));
 }
 // E has per-lane attributes (envs_classic.h *AttrT: N_ATTR, attr_default, attrs_arrive)
 template <class E, class = void>
@@ -219,15 +136,6 @@ MI_DEV void store_lane(const DevEnv &d, int i, const Lane<E> &L) {
     for (int k = 0; k < E::S; k++) d.state[(size_t)k * d.N + i] = L.s[k];
     d.meta[i] = (L.elapsed & kElapsedMask) | (L.flags << kFlagShift);
     d.ep_ret[i] = L.ep_ret, d.ep_len[i] = L.ep_len;
-}
-MI_DEV Pcg64 load_rng(const DevEnv &d, int i) {
-    Pcg64 r;
-    r.state = make_u128(d.rng[i], d.rng[(size_t)d.N + i]);
-    r.inc = make_u128(d.rng[(size_t)2 * d.N + i], d.rng[(size_t)3 * d.N + i]);
-    return r;
-}
-MI_DEV void store_rng_state(const DevEnv &d, int i, const Pcg64 &r) {
-    d.rng[i] = (uint64_t)(r.state >> 64), d.rng[(size_t)d.N + i] = (uint64_t)r.state;
 }
 
 // The next E::NDRAWS values of the lane's own stream, drawn AHEAD of the reset that will consume them.
@@ -590,67 +498,6 @@ MI_DEV void load_row(const float *src, float *dst) {
     for (int k = 0; k < W; k++) dst[k] = src[k];
 }
 
-MI_DEV double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-MI_DEV uint32_t wave_sum(uint32_t v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor((int)v, off, 64);
-    return v;
-}
-MI_DEV uint64_t wave_sum(uint64_t v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += (uint64_t)__shfl_xor((long long)v, off, 64);
-    return v;
-}
-
-// Per-workgroup totals: wavefront butterflies, 4 partials through LDS, one plain read-modify-write of the
-// workgroup's own slot (no atomics: 1024 same-address atomics would cost more than the whole step).
-// The workgroup's previous totals as step_kernel loads them AHEAD (with the lane's state): the read-modify-write at the end of the kernel is
-// then a plain store, not one more dependent trip to memory in a kernel whose whole run time is a handful of such trips.
-struct BlockTotals {
-    uint64_t count;  // threads 0..3: blk_count[block][thread]
-    double ret;      // thread 64: blk_ret[block]
-    bool loaded;
-};
-MI_DEV BlockTotals block_totals_load(const DevEnv &d) {
-    BlockTotals t = {0ull, 0.0, true};
-    if (threadIdx.x < 4) t.count = d.blk_count[(size_t)blockIdx.x * 4 + threadIdx.x];
-    if (threadIdx.x == 64) {
-        uint32_t zero = 0;  // (an offset the compiler cannot see through: a VECTOR load that stays in flight -- the uniform address would make it an s_load, which the wavefront waits for on the spot)
-        hold_opaque(zero);
-        t.ret = d.blk_ret[(size_t)blockIdx.x + zero];
-    }
-    return t;
-}
-MI_DEV void block_accumulate(const DevEnv &d, const LaneStats &st, const BlockTotals &before = BlockTotals{0ull, 0.0, false}) {
-    __shared__ uint64_t sh_c[4][kBlock / 64];
-    __shared__ double sh_r[kBlock / 64];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const uint32_t c0 = wave_sum(st.env_steps), c1 = wave_sum(st.reset_steps), c2 = wave_sum(st.episodes);
-    // c2 is wavefront-uniform: the two wide reductions are skipped by wavefronts in which no episode finished
-    const uint64_t c3 = c2 ? wave_sum(st.length_sum) : 0;
-    const double r = c2 ? wave_sum(st.return_sum) : 0.0;
-    if (lane == 0) sh_c[0][wave] = c0, sh_c[1][wave] = c1, sh_c[2][wave] = c2, sh_c[3][wave] = c3, sh_r[wave] = r;
-    __syncthreads();
-    if (threadIdx.x < 4) {
-        uint64_t t = 0;
-#pragma unroll
-        for (int w = 0; w < kBlock / 64; w++) t += sh_c[threadIdx.x][w];
-        if (t) {
-            uint64_t *slot = &d.blk_count[(size_t)blockIdx.x * 4 + threadIdx.x];
-            *slot = (before.loaded ? before.count : *slot) + t;
-        }
-    } else if (threadIdx.x == 64) {
-        double t = 0.0;
-#pragma unroll
-        for (int w = 0; w < kBlock / 64; w++) t += sh_r[w];
-        if (t != 0.0) d.blk_ret[blockIdx.x] = (before.loaded ? before.ret : d.blk_ret[blockIdx.x]) + t;
-    }
-}
-
 // ---------------------------------------------------------------------------------------------------------
 // kernels
 // ---------------------------------------------------------------------------------------------------------
@@ -671,22 +518,6 @@ MI_DEV void block_accumulate(const DevEnv &d, const LaneStats &st, const BlockTo
 //     Beyond kEpiFoldMax step workgroups the fold is a one-workgroup launch of its own (epilogue_combine) and phase 2 reads its result.
 // Together: 2 launches per wrapped step (3 beyond 262144 sub-environments) instead of 1 + 4 + 5 + 1 with the stand-alone passes.
 // ---------------------------------------------------------------------------------------------------------
-constexpr int kEpiObsMax = 6, kEpiCols = 2 * kEpiObsMax + 3, kEpiFoldMax = 1024;
-}  // namespace
-namespace mi_internal {
-struct EpiDev {
-    int obs_on, obs_update, ret_on, ret_update, same_step, clip_pre, clip_post, fold_in_finish;  // clip_*: bit 0 = has min, bit 1 = has max
-    int step_blocks;
-    float gamma;
-    double obs_eps, ret_eps, pre_lo, pre_hi, post_lo, post_hi;
-    double *obs_mean, *obs_var, *obs_count, *ret_mean, *ret_var, *ret_count;              // the statistics before this step (read only)
-    double *obs_mean2, *obs_var2, *obs_count2, *ret_mean2, *ret_var2, *ret_count2;        // where the updated ones go
-    float *acc;
-    uint8_t *prev_done;
-    double *partial;   // [step_blocks][kEpiCols]
-};
-}  // namespace mi_internal
-namespace {
 MI_DEV double clip_to(double v, int flags, double lo, double hi) {  // np.clip(reward, min_reward, max_reward)
     if (flags & 1) v = v < lo ? lo : v;
     if (flags & 2) v = v > hi ? hi : v;
@@ -847,33 +678,6 @@ __global__ __launch_bounds__(kBlock) void epilogue_finish(EpiDev e, int N, float
     }
 }
 
-}  // namespace
-namespace mi_internal {
-struct StepPtrs {
-    const void *actions;
-    float *obs;
-    double *reward;
-    uint8_t *terminated, *truncated;
-    float *final_obs;
-    double *ep_ret;
-    int32_t *ep_len;
-    // the on-device policy (mi_step with actions == NULL): per-lane states of the action stream [2][N] (lane i: the state whose output is draw
-    // pos + i * act_dim), where the drawn actions go (or nullptr), and the jump to the lane's slot in the next batch (N * act_dim draws on)
-    uint64_t *act_lane;
-    void *actions_out;
-    PcgJump act_jump;
-};
-}  // namespace mi_internal
-namespace {
-
-// XSL-RR output of a PCG64 state (the state AFTER its step: what the action-stream lanes hold)
-MI_DEV uint64_t pcg_output(u128 state) {
-    const uint64_t hi = (uint64_t)(state >> 64), lo = (uint64_t)state;
-    const uint64_t x = hi ^ lo;
-    const unsigned rot = (unsigned)(hi >> 58);
-    return (x >> rot) | (x << ((0u - rot) & 63u));
-}
-
 // action_space.sample() of one lane from the state of the action stream whose output is the lane's draw
 template <class E>
 MI_DEV typename E::Act action_of_state(u128 astate) {
@@ -999,77 +803,6 @@ __global__ __launch_bounds__(kBlock) void reset_kernel(DevEnv d, const uint8_t *
     }
 }
 
-}  // namespace
-namespace mi_internal {
-// Action stream of the batched action space: ONE PCG64 generator drawn in sub-environment index order, so lane i
-// consumes draw number t*N + i of the stream at step t.  jump[j] advances by 2^j draws; jump_n advances by N.
-struct ActionStream {
-    uint64_t state_hi, state_lo, inc_hi, inc_lo;
-    const PcgJump *pow2;  // [64] device
-    PcgJump jump_n;
-    // the classic kinds' sampling rollouts (rollout_kernel, rollout_duo_kernel): the per-lane states (act_lane[2][N], act_init_kernel's meaning)
-    // the launch leaves behind -- a lane writes its state after the last jump, i.e. its state for the position T * N draws on.  nullptr: none
-    // (the other kernels; a launch inside a stream capture).  lane_valid: they hold the launch's start already, so no skip-ahead from state_hi / lo.
-    uint64_t *lane;
-    int lane_valid;
-};
-
-struct RolloutPtrs {
-    const void *actions_in;
-    void *actions_out;
-    void *obs;
-    double *reward;
-    uint8_t *terminated, *truncated;
-};
-// What a rollout stores besides RolloutPtrs (mi_rollout_extra, same meaning; every member nullable): a kernel argument of its own, taken only by the
-// kernels that store them -- RolloutPtrs, which the two-role and the branch-free kernels take by value, stays what it is.
-struct RolloutExtra {
-    void *final_obs;
-    double *ep_ret;
-    int32_t *ep_len;
-    double *info, *final_info;
-};
-// MI_CFG_SHARED_RNG (include/mi355env.h): CartPoleVectorEnv's ONE generator on the device.  It is kept as a fixed BASE state (what mi_seed gave) plus
-// the number of draws taken since: draw number n of the stream is the output after skipping n steps ahead of the base (Brown's O(log n) jump through
-// the pow2 table), so every lane finds its own draws without a serial pass and nothing but two counters ever changes.
-struct SharedRng {
-    uint64_t *words;       // [8] device: base {state_hi, state_lo, inc_hi, inc_lo}, [4] consumed, [5] pos_base = first draw of the call in flight, [6] k = sub-envs it re-draws,
-                           // [7] != 0: a batch with an action outside the space was refused (shared_validate_kernel) -- every later step is a no-op until the host has raised it
-    const PcgJump *pow2;   // [64] device: jump by 2^j steps of the base generator's increment
-    uint32_t *blk_done;    // [grid] sub-environments of each step workgroup that finished an episode in the previous step
-    uint32_t *blk_prefix;  // [grid] exclusive scan of blk_done (shared_scan_kernel)
-    double low, high;      // self.low / self.high (cartpole.py:489-491): the bounds of the last reset() serve the autoresets
-};
-}  // namespace mi_internal
-// The classic-control kernels behind plain launch functions (defined in the MI_CLASSIC_TU unit, called from the other): what mi_step / mi_reset /
-// mi_rollout do for the kinds CARTPOLE ... MOUNTAIN_CAR_CONTINUOUS once the arguments are validated and the buffers chosen.
-namespace mi_classic {
-int step(mi_vecenv *v, const mi_internal::StepPtrs &p, int act_kind);                                           // launch_step<E> of the env's kind
-int reset(mi_vecenv *v, const uint8_t *device_mask, int has_bounds, double b0, double b1, float *device_obs);  // reset_kernel<E>
-int rollout(mi_vecenv *v, const mi_internal::RolloutPtrs &p, const mi_internal::ActionStream &as, int T, bool sample, int actions_in_kind);
-// ... and with the per-step extras (mi_rollout_infos): always the one-role kernel, the instantiations that store them
-int rollout_infos(mi_vecenv *v, const mi_internal::RolloutPtrs &p, const mi_internal::RolloutExtra &ex, const mi_internal::ActionStream &as, int T, bool sample,
-                  int actions_in_kind);
-// MI_CFG_SHARED_RNG (CartPole only): reset = [bookkeeping, reset kernel]; step = [scan of the finished sub-environments, step kernel];
-// rollout = T x [policy sample,] step; recount = blk_done from the flag words (after mi_set_state)
-int shared_reset(mi_vecenv *v, float *device_obs);
-int shared_step(mi_vecenv *v, const mi_internal::StepPtrs &p);
-int shared_rollout(mi_vecenv *v, const mi_internal::RolloutPtrs &p, const mi_internal::ActionStream &as, int T, bool sample, const mi_internal::RolloutExtra *ex = nullptr);
-int shared_recount(mi_vecenv *v);
-}  // namespace mi_classic
-// The one-lane MuJoCo kernels of an env with per-sub-environment model fields (mi_set_model_field) -- mj_step_kernel and mj_rollout_kernel over
-// mjx::LaneModel env types -- behind plain launch functions: they are instantiated in a translation unit of their own (mjx_model.hip: this file with
-// MI_MJ_MODEL_TU), which compiles side by side with the others.  `mj_step_ptrs` is an MjStepPtrs -- a type of the unnamed namespace, whose name is
-// part of the stock kernels' symbols and therefore stays where it is; both units compile the one definition.  d.mj.rows are the env's rows.
-// false: a kind the unit does not hold.
-namespace mi_mjmodel {
-bool step(int kind, int autoreset_mode, int grid, hipStream_t stream, const mi_internal::DevEnv &d, const void *mj_step_ptrs);
-// load the unit's code object on the current device now (kernels load on first use, which a stream capture must not trigger)
-bool preload(int kind);
-bool rollout(int kind, int autoreset_mode, bool sample, int grid, hipStream_t stream, const mi_internal::DevEnv &d, const mi_internal::RolloutPtrs &p,
-             const mi_internal::ActionStream &as, int T, int obs_dim, int in_f64, const mi_internal::RolloutExtra &ex);
-}  // namespace mi_mjmodel
-namespace {
 
 // FULL: every trajectory output is materialised -- the per-store null checks (five taken branches per step for a
 // wavefront that runs alone on its SIMD) disappear from the loop.
@@ -1966,260 +1699,9 @@ __global__ __launch_bounds__(kBlock) void shared_sample_kernel(DevEnv d, ActionS
 }
 
 #ifndef MI_CLASSIC_TU
-// ---------------------------------------------------------------------------------------------------------
-// MuJoCo-family kernels (mjx_kernels.h): same vectoriser state machine, float64 observations, float32 action rows
-// ---------------------------------------------------------------------------------------------------------
-struct MjStepPtrs {
-    const void *actions;  // [N][NU] float32 rows, or float64 rows taken un-rounded (act_f64; mujoco_env.py:148 data.ctrl[:] = ctrl)
-    double *obs, *reward;
-    uint8_t *terminated, *truncated;
-    double *final_obs, *ep_ret;
-    int32_t *ep_len;
-    double *info, *final_info;
-    int obs_dim;
-    const double *extras;  // [N][EX_TOTAL] rows written by mj_physics_kernel, or nullptr (one-lane simulator inside the step kernel)
-    int act_f64;
-};
-
-template <class E>
-struct MjLane {
-    double s[E::S];
-    uint32_t elapsed, flags;
-    double ep_ret;
-    int32_t ep_len;
-};
-// The sub-environment's own model fields of an env type over a mjx::LaneModel (void, and nothing to load, for the stock models): loaded once per launch
-template <class E>
-using MjLaneFields = typename mjx::ModelView<typename E::Model>::Fields;
-template <class E>
-struct MjLaneHolder {
-    static constexpr bool HAS = !std::is_void<MjLaneFields<E>>::value;
-    typename std::conditional<HAS, MjLaneFields<E>, char>::type fields;  // (a byte nobody touches for the stock models)
-    MI_DEV void load(const DevEnv &d, int i) {
-        if constexpr (HAS) fields.load(d.mj.rows, (size_t)d.N, (size_t)i);
-    }
-    MI_DEV const MjLaneFields<E> *get() const {
-        if constexpr (HAS)
-            return &fields;
-        else
-            return nullptr;
-    }
-};
-template <class E>
-MI_DEV void mj_load(const DevEnv &d, int i, MjLane<E> &L) {
-    for (int k = 0; k < E::S; k++) L.s[k] = d.state[(size_t)k * d.N + i];
-    const uint32_t m = d.meta[i];
-    L.elapsed = m & kElapsedMask, L.flags = m >> kFlagShift;
-    L.ep_ret = d.ep_ret[i], L.ep_len = d.ep_len[i];
-}
-template <class E>
-MI_DEV void mj_store(const DevEnv &d, int i, const MjLane<E> &L) {
-    for (int k = 0; k < E::S; k++) d.state[(size_t)k * d.N + i] = L.s[k];
-    d.meta[i] = (L.elapsed & kElapsedMask) | (L.flags << kFlagShift);
-    d.ep_ret[i] = L.ep_ret, d.ep_len[i] = L.ep_len;
-}
-template <class E>
-MI_DEV void mj_autoreset(const DevEnv &d, int i, MjLane<E> &L, double *obs) {
-    Pcg64 rng = load_rng(d, i);
-    E::reset(rng, L.s, d.P, obs);
-    store_rng_state(d, i, rng);
-    L.elapsed = 0, L.ep_ret = 0.0, L.ep_len = 0;
-}
-
-// one lockstep step of one MuJoCo sub-environment; obs / info rows are written straight to their destination
-// `extras` != nullptr: the physics of this step was already advanced by mj_physics_kernel (L.s holds the new qpos / qvel
-// and the old tracked point); nullptr: the one-lane simulator runs here.
-template <class E, int MODE, bool COOP = false>
-MI_DEV void mj_lane_step(const DevEnv &d, int i, MjLane<E> &L, const mjx::ActRow action, double *obs, double *final_obs, double *info,
-                         double &reward, bool &te, bool &tr, double &out_ret, int32_t &out_len, LaneStats &st,
-                         const double *extras = nullptr, double *final_info = nullptr, const MjLaneFields<E> *lane = nullptr) {
-    te = tr = false, reward = 0.0;
-    if (MODE == MI_AUTORESET_NEXT_STEP && (L.flags & kNeedsReset)) {
-        mj_autoreset<E>(d, i, L, obs);
-        if (info) E::reset_info(L.s, info);
-        st.reset_steps++;
-    } else if (MODE == MI_AUTORESET_DISABLED && (L.flags & kNeedsReset)) {
-        *d.error = kErrDisabledStepped;
-        out_ret = 0.0, out_len = 0;
-        return;
-    } else {
-        if (COOP) {
-            typedef mjx::coop::Sim<typename E::Model, E::COOP_G> S;
-            typename E::StepExtras x;
-            E::after_from_extras(L.s, extras, x.after);
-            x.cfrc = reinterpret_cast<const double (*)[6]>(extras + S::EX_CFRC);
-            x.cinert = reinterpret_cast<const double (*)[10]>(extras + S::EX_CINERT);
-            x.cvel = reinterpret_cast<const double (*)[6]>(extras + S::EX_CVEL);
-            x.qfrc_actuator = extras + S::EX_QFA;
-            x.qfrc_constraint = nullptr;
-            x.ten = extras + S::EX_TEN;
-            const double before[2] = {L.s[E::NQ + 2 * E::NV], L.s[E::NQ + 2 * E::NV + 1]};
-            E::finish(L.s, before, x, action, d.P, obs, reward, te, info);
-        } else {
-            E::step(L.s, action, d.P, obs, reward, te, info, d.solver_newton != 0, lane);
-        }
-        L.elapsed += 1;
-        tr = d.max_steps > 0 && (int)L.elapsed >= d.max_steps;
-        L.ep_ret += reward, L.ep_len += 1;
-        st.env_steps++;
-    }
-    const bool done = te || tr;
-    out_ret = done ? L.ep_ret : 0.0, out_len = done ? L.ep_len : 0;
-    if (done) st.episodes++, st.return_sum += L.ep_ret, st.length_sum += (uint64_t)L.ep_len;
-    if (MODE == MI_AUTORESET_SAME_STEP && done) {
-        if (final_obs)
-            for (int k = 0; k < E::obs_dim(d.P); k++) final_obs[k] = obs[k];
-        if (info && final_info)  // sync_vector_env.py:309-317: the finishing step's info goes to "final_info" ...
-            for (int k = 0; k < E::INFO; k++) final_info[k] = info[k];
-        mj_autoreset<E>(d, i, L, obs);
-        if (info) E::reset_info(L.s, info);  // ... and the top-level entries of this sub-env are its reset info (:319)
-    }
-    if (done && MODE != MI_AUTORESET_SAME_STEP)
-        L.flags |= kNeedsReset;
-    else
-        L.flags &= ~kNeedsReset;
-}
-
-template <class E, int MODE, bool COOP>
-__global__ __launch_bounds__(kBlock) void mj_step_kernel(DevEnv d, MjStepPtrs io) {
-    const int i = blockIdx.x * kBlock + threadIdx.x;
-    LaneStats st = {0u, 0u, 0u, 0ull, 0.0};
-    if (i < d.N) {
-        MjLane<E> L;
-        mj_load<E>(d, i, L);
-        double reward, out_ret;
-        int32_t out_len;
-        bool te, tr;
-        const mjx::ActRow a = {static_cast<const char *>(io.actions) + (size_t)i * E::NU * (io.act_f64 ? 8 : 4), io.act_f64 != 0};
-        // Two spellings of one call, on purpose: with a holder object in the stock instantiations -- even an empty one, as in mj_rollout_kernel -- the
-        // DISABLED-mode kernels of the stock robots come out with two instructions in another order (scripts/kernel_stream_diff.py), and the stock
-        // kernels are to stay what they were instruction for instruction.
-        if constexpr (MjLaneHolder<E>::HAS) {
-            MjLaneHolder<E> lane;
-            lane.load(d, i);
-            mj_lane_step<E, MODE, false>(d, i, L, a, io.obs + (size_t)i * io.obs_dim,
-                                         io.final_obs ? io.final_obs + (size_t)i * io.obs_dim : nullptr,
-                                         io.info ? io.info + (size_t)i * E::INFO : nullptr, reward, te, tr, out_ret, out_len, st, nullptr,
-                                         io.final_info ? io.final_info + (size_t)i * E::INFO : nullptr, lane.get());
-        } else {
-            mj_lane_step<E, MODE, COOP>(d, i, L, a, io.obs + (size_t)i * io.obs_dim,
-                                        io.final_obs ? io.final_obs + (size_t)i * io.obs_dim : nullptr,
-                                        io.info ? io.info + (size_t)i * E::INFO : nullptr, reward, te, tr, out_ret, out_len, st,
-                                        COOP ? io.extras + (size_t)i * mjx::coop::Sim<typename E::Model, E::COOP_G>::EX_TOTAL : nullptr,
-                                        io.final_info ? io.final_info + (size_t)i * E::INFO : nullptr);
-        }
-        mj_store<E>(d, i, L);
-        if (io.reward) io.reward[i] = reward;
-        if (io.terminated) io.terminated[i] = te;
-        if (io.truncated) io.truncated[i] = tr;
-        if (io.ep_ret) io.ep_ret[i] = out_ret;
-        if (io.ep_len) io.ep_len[i] = out_len;
-    }
-    block_accumulate(d, st);
-}
-
-template <class E>
-__global__ __launch_bounds__(kBlock) void mj_reset_kernel(DevEnv d, const uint8_t *mask, double *obs, int obs_dim) {
-    const int i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= d.N || (mask && !mask[i])) return;
-    MjLane<E> L;
-    mj_load<E>(d, i, L);
-    L.flags &= ~kNeedsReset;
-    mj_autoreset<E>(d, i, L, obs ? obs + (size_t)i * obs_dim : nullptr);
-    mj_store<E>(d, i, L);
-}
-
-// fused rollout: T steps per launch, Box action space sampled on device from the batched space's single PCG64 stream
-// (draw number (t*N + i)*NU + u belongs to lane i, component u, step t)
-// ex (mi_rollout_infos; all members NULL for mi_rollout): per step the info row, the finished episodes' return / length and, under SAME_STEP, the final
-// observation and info -- zeros in the rows that finished nothing.
-template <class E, int MODE, bool SAMPLE>
-__global__ __launch_bounds__(kBlock) void mj_rollout_kernel(DevEnv d, RolloutPtrs io, ActionStream as, int T, int obs_dim, int in_f64, RolloutExtra ex) {
-    const int i = blockIdx.x * kBlock + threadIdx.x;
-    LaneStats st = {0u, 0u, 0u, 0ull, 0.0};
-    if (i < d.N) {
-        MjLane<E> L;
-        mj_load<E>(d, i, L);
-        MjLaneHolder<E> lane;
-        lane.load(d, i);
-        u128 astate = 0;
-        const u128 ainc = make_u128(as.inc_hi, as.inc_lo);
-        if (SAMPLE) {
-            astate = make_u128(as.state_hi, as.state_lo);
-            uint64_t delta = (uint64_t)i * E::NU + 1u;
-            for (int j = 0; delta; j++, delta >>= 1)
-                if (delta & 1u) astate = as.pow2[j].mult * astate + as.pow2[j].plus;
-        }
-        const size_t N = (size_t)d.N;
-        double scratch_obs[E::MAX_OBS], scratch_info[E::INFO > 0 ? E::INFO : 1];
-        for (int t = 0; t < T; t++) {
-            float a[E::NU];
-            mjx::ActRow row = {a, false};
-            if (SAMPLE) {
-                for (int u = 0; u < E::NU; u++) {
-                    const uint64_t hi = (uint64_t)(astate >> 64), lo = (uint64_t)astate, x = hi ^ lo;
-                    const unsigned rot = (unsigned)(hi >> 58);
-                    const uint64_t out = (x >> rot) | (x << ((0u - rot) & 63u));
-                    const double lo_b = (double)(float)E::Model::actuator_ctrlrange[u][0], hi_b = (double)(float)E::Model::actuator_ctrlrange[u][1];
-                    a[u] = (float)(lo_b + (hi_b - lo_b) * ((double)(out >> 11) * (1.0 / 9007199254740992.0)));
-                    if (u + 1 < E::NU) astate = astate * pcg_mult() + ainc;
-                }
-                astate = as.jump_n.mult * astate + as.jump_n.plus;
-                if (io.actions_out)
-                    for (int u = 0; u < E::NU; u++) static_cast<float *>(io.actions_out)[(t * N + i) * E::NU + u] = a[u];
-            } else {  // the caller's rows, read in place
-                row.p = static_cast<const char *>(io.actions_in) + (t * N + i) * E::NU * (in_f64 ? 8 : 4), row.f64 = in_f64 != 0;
-            }
-            double reward, out_ret;
-            int32_t out_len;
-            bool te, tr;
-            double *obs = io.obs ? static_cast<double *>(io.obs) + (t * N + i) * obs_dim : scratch_obs;
-            double *fobs = ex.final_obs ? static_cast<double *>(ex.final_obs) + (t * N + i) * obs_dim : nullptr;
-            double *finfo = ex.final_info ? ex.final_info + (t * N + i) * E::INFO : nullptr;
-            // (the finishing step's info reaches final_info through the info row: without a caller's array a private row serves)
-            double *info = ex.info ? ex.info + (t * N + i) * E::INFO : (finfo ? scratch_info : nullptr);
-            mj_lane_step<E, MODE>(d, i, L, row, obs, fobs, info, reward, te, tr, out_ret, out_len, st, nullptr, finfo, lane.get());
-            if (io.reward) io.reward[t * N + i] = reward;
-            if (io.terminated) io.terminated[t * N + i] = te;
-            if (io.truncated) io.truncated[t * N + i] = tr;
-            if (ex.ep_ret) ex.ep_ret[t * N + i] = out_ret;
-            if (ex.ep_len) ex.ep_len[t * N + i] = out_len;
-            if (!(te || tr)) {
-                if (fobs)
-                    for (int k = 0; k < obs_dim; k++) fobs[k] = 0.0;
-                if (finfo)
-                    for (int k = 0; k < E::INFO; k++) finfo[k] = 0.0;
-            }
-        }
-        mj_store<E>(d, i, L);
-    }
-    block_accumulate(d, st);
-}
-
-#ifndef MI_MJ_MODEL_TU
 // ---- cooperative physics (mjx_coop.h): G lanes per sub-environment, 64 / G sub-environments per wavefront --------------
 // mj_physics_kernel lives in mjx_physics.h and is instantiated in physics16.hip / physics32.hip (their own compiler settings); here it
 // is only launched: mi_phys::launch16 / launch32.
-
-// Box.sample() of the batched action space for step t of a rollout: draw number (t N + i) NU + u of the stream
-template <class E>
-__global__ __launch_bounds__(kBlock) void mj_sample_kernel(DevEnv d, ActionStream as, int t, float *out) {
-    const int i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= d.N) return;
-    const u128 ainc = make_u128(as.inc_hi, as.inc_lo);
-    u128 astate = make_u128(as.state_hi, as.state_lo);
-    uint64_t delta = ((uint64_t)t * (uint64_t)d.N + (uint64_t)i) * E::NU + 1u;
-    for (int j = 0; delta; j++, delta >>= 1)
-        if (delta & 1u) astate = as.pow2[j].mult * astate + as.pow2[j].plus;
-    for (int u = 0; u < E::NU; u++) {
-        const uint64_t hi = (uint64_t)(astate >> 64), lo = (uint64_t)astate, x = hi ^ lo;
-        const unsigned rot = (unsigned)(hi >> 58);
-        const uint64_t o = (x >> rot) | (x << ((0u - rot) & 63u));
-        const double lo_b = (double)(float)E::Model::actuator_ctrlrange[u][0], hi_b = (double)(float)E::Model::actuator_ctrlrange[u][1];
-        out[(size_t)i * E::NU + u] = (float)(lo_b + (hi_b - lo_b) * ((double)(o >> 11) * (1.0 / 9007199254740992.0)));
-        astate = astate * pcg_mult() + ainc;
-    }
-}
 
 // ---------------------------------------------------------------------------------------------------------
 // ToyText: finite MDPs.  state row = {state index, probability of the last transition}; integer lookups only.
@@ -3005,7 +2487,6 @@ __global__ __launch_bounds__(kBlock) void model_transpose_kernel(const double *s
     for (int c = 0; c < width; c++) dst[(size_t)c * N + i] = src[(size_t)i * width + c];
 }
 
-#endif  // !MI_MJ_MODEL_TU
 #endif  // !MI_CLASSIC_TU
 
 // ---------------------------------------------------------------------------------------------------------
@@ -3013,65 +2494,6 @@ __global__ __launch_bounds__(kBlock) void model_transpose_kernel(const double *s
 // ---------------------------------------------------------------------------------------------------------
 
 }  // namespace
-#ifdef MI_MJ_MODEL_TU
-namespace mi_mjmodel {
-template <class M0, int KIND>
-using Env = mjx::MjEnv<mjx::LaneModel<M0>, KIND>;
-template <class F>
-static bool dispatch(int kind, F &&f) {
-    switch (kind) {
-    case MI_ENV_HALF_CHEETAH: f(Env<mjx::HalfCheetahModel, mjx::kHalfCheetah>()); return true;
-    case MI_ENV_ANT: f(Env<mjx::AntModel, mjx::kAnt>()); return true;
-    case MI_ENV_HUMANOID: f(Env<mjx::HumanoidModel, mjx::kHumanoid>()); return true;
-    case MI_ENV_HOPPER: f(Env<mjx::HopperModel, mjx::kHopper>()); return true;
-    case MI_ENV_WALKER2D: f(Env<mjx::Walker2dModel, mjx::kWalker2d>()); return true;
-    case MI_ENV_INVERTED_PENDULUM: f(Env<mjx::InvertedPendulumModel, mjx::kInvertedPendulum>()); return true;
-    case MI_ENV_INVERTED_DOUBLE_PENDULUM: f(Env<mjx::InvertedDoublePendulumModel, mjx::kInvertedDoublePendulum>()); return true;
-    case MI_ENV_REACHER: f(Env<mjx::ReacherModel, mjx::kReacher>()); return true;
-    case MI_ENV_HUMANOID_STANDUP: f(Env<mjx::HumanoidStandupModel, mjx::kHumanoidStandup>()); return true;
-    case MI_ENV_SWIMMER: f(Env<mjx::SwimmerModel, mjx::kSwimmer>()); return true;
-    case MI_ENV_PUSHER: f(Env<mjx::PusherModel, mjx::kPusher>()); return true;
-    }
-    return false;
-}
-bool preload(int kind) {
-    hipError_t err = hipSuccess;
-    const bool held = dispatch(kind, [&](auto env) {
-        hipFuncAttributes attr;
-        err = hipFuncGetAttributes(&attr, reinterpret_cast<const void *>(&mj_step_kernel<decltype(env), MI_AUTORESET_NEXT_STEP, false>));
-    });
-    return held && err == hipSuccess;
-}
-bool step(int kind, int mode, int grid, hipStream_t stream, const DevEnv &d, const void *mj_step_ptrs) {
-    const MjStepPtrs mp = *static_cast<const MjStepPtrs *>(mj_step_ptrs);
-    const dim3 g(grid), b(kBlock);
-    return dispatch(kind, [&](auto env) {
-        using E = decltype(env);
-        switch (mode) {
-        case MI_AUTORESET_NEXT_STEP: hipLaunchKernelGGL((mj_step_kernel<E, MI_AUTORESET_NEXT_STEP, false>), g, b, 0, stream, d, mp); break;
-        case MI_AUTORESET_SAME_STEP: hipLaunchKernelGGL((mj_step_kernel<E, MI_AUTORESET_SAME_STEP, false>), g, b, 0, stream, d, mp); break;
-        default: hipLaunchKernelGGL((mj_step_kernel<E, MI_AUTORESET_DISABLED, false>), g, b, 0, stream, d, mp); break;
-        }
-    });
-}
-bool rollout(int kind, int mode, bool sample, int grid, hipStream_t stream, const DevEnv &d, const RolloutPtrs &p, const ActionStream &as, int T, int obs_dim,
-             int in_f64, const RolloutExtra &ex) {
-    const dim3 g(grid), b(kBlock);
-    return dispatch(kind, [&](auto env) {
-        using E = decltype(env);
-        const bool next = mode == MI_AUTORESET_NEXT_STEP;  // (mi_rollout refuses a DISABLED env)
-        if (next && sample)
-            hipLaunchKernelGGL((mj_rollout_kernel<E, MI_AUTORESET_NEXT_STEP, true>), g, b, 0, stream, d, p, as, T, obs_dim, in_f64, ex);
-        else if (next)
-            hipLaunchKernelGGL((mj_rollout_kernel<E, MI_AUTORESET_NEXT_STEP, false>), g, b, 0, stream, d, p, as, T, obs_dim, in_f64, ex);
-        else if (sample)
-            hipLaunchKernelGGL((mj_rollout_kernel<E, MI_AUTORESET_SAME_STEP, true>), g, b, 0, stream, d, p, as, T, obs_dim, in_f64, ex);
-        else
-            hipLaunchKernelGGL((mj_rollout_kernel<E, MI_AUTORESET_SAME_STEP, false>), g, b, 0, stream, d, p, as, T, obs_dim, in_f64, ex);
-    });
-}
-}  // namespace mi_mjmodel
-#else  // every other translation unit: the rest of the file
 // shared with the other translation units of the library (hidden visibility): sets mi_last_error(), returns `code`
 namespace mi_internal {
 #ifndef MI_CLASSIC_TU
@@ -3086,23 +2508,6 @@ int set_error(int code, const char *msg);
 }  // namespace mi_internal
 namespace {
 
-int fail(int code, const char *fmt, const char *detail = "") {
-    char msg[512];
-    snprintf(msg, sizeof msg, fmt, detail);
-    return mi_internal::set_error(code, msg);
-}
-
-#define HIP_TRY(expr)                                                                                     \
-    do {                                                                                                  \
-        hipError_t e_ = (expr);                                                                           \
-        if (e_ != hipSuccess) {                                                                           \
-            char msg_[512];                                                                               \
-            snprintf(msg_, sizeof msg_, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-            return mi_internal::set_error((int)MI_ERR_HIP, msg_);                                          \
-        }                                                                                                 \
-    } while (0)
-
-constexpr int kClassicKinds = 5;
 const mi_layout kLayouts[kClassicKinds] = {
     {CartPole::OBS, MI_F32, 1, MI_I64, CartPole::S, 0, {0, 0}},
     {Pendulum::OBS, MI_F32, 1, MI_F32, Pendulum::S, 0, {0, 0}},
@@ -3113,85 +2518,6 @@ const mi_layout kLayouts[kClassicKinds] = {
 const int kNumActions[MI_ENV_KIND_COUNT] = {2, 0, 3, 3, 0, 0, 0, 0, 0};
 
 }  // namespace
-
-struct mi_vecenv {
-    mi_config cfg;
-    mi_layout lay;
-    int device;
-    hipStream_t stream, own_stream;
-    DevEnv d;
-    int grid;
-    bool seeded, was_reset, act_seeded;
-    bool has_epi;           // mi_set_step_epilogue: the wrappers run as the output stage of step_kernel
-    EpiDev epi;
-    mi_step_epilogue epi_host;  // what the caller attached: the statistics handles swap their two buffer sets every step, so epi is rebuilt
-    double *d_epi_partial;      // [grid][kEpiCols] column sums of the step workgroups
-    Pcg64 act_rng;          // host copy of the action-space generator
-    PcgJump *d_pow2;        // [64] device jump table for act_rng.inc
-    PcgJump jump_n;
-    // the action stream as per-lane states on the device (act_sample_kernel): act_lane_valid = they correspond to the stream's position;
-    // act_on_device = they ARE the position (the host copy act_rng is stale until act_sync_host reads lane 0 back)
-    uint64_t *d_act_lane;   // [2][N]
-    bool act_lane_valid, act_on_device;
-    void *d_act_stage;      // mi_action_sample(MI_HOST): where the kernel writes before the copy to the caller's array
-    size_t act_stage_bytes;
-    // Staging for the MI_HOST entry points (SURVEY 8(b) "Ownership"): every step output lives in ONE device block and ONE pinned host
-    // block of the same layout -- [error word | obs | reward | terminated | truncated | info | episode_return | episode_length | final_obs |
-    // final_info], 256-byte aligned sections -- so a host step is one H2D (actions), one launch and one D2H of the prefix in use.
-    // d_obs ... d_final_info / h_* are views into the two blocks.
-    char *d_out, *h_out, *h_out_dev;  // h_out_dev: the device address of the pinned block (zero-copy step of the classic kinds)
-    int *h_err;                       // sticky device error word, page-locked host memory
-    size_t out_bytes, off_end[9];  // end offset of each section in the order above (after the header)
-    void *d_actions, *h_actions;
-    void *d_obs, *d_final;
-    double *d_reward, *d_epret;
-    uint8_t *d_term, *d_trunc, *d_mask;
-    int32_t *d_eplen;
-    uint64_t *d_words;
-    size_t act_bytes, act_bytes_max, obs_bytes;
-    double *d_info, *d_final_info;
-    size_t info_bytes;
-    mi_step_io h_io;        // the pinned host arrays (mi_host_buffers)
-    mi_step_io pending;     // user pointers of a step that was enqueued by mi_step_async and not waited for yet
-    size_t pending_bytes;
-    bool has_pending;
-    void *tab_bufs[8];
-    bool tab_loaded;
-    int tab_start_state;  // the one state every episode starts in (its cumulative initial probability is >= 1), -1 when the start is drawn among several
-    // MuJoCo family: cooperative physics kernel (default) or the one-lane simulator (MI355ENV_MJ_SERIAL=1, cross-check)
-    bool mj_coop;
-    int extras_dim;
-    double *d_extras;       // [N][EX_TOTAL]
-    float *d_act_scratch;   // [N][NU] actions of the current rollout step when the caller does not keep them
-    void *d_obs_scratch;    // [N][obs_dim] observations of the current rollout step when the caller does not keep them
-    // MI_CFG_SHARED_RNG (CartPoleVectorEnv's semantics): the one generator and the bookkeeping of its draw positions, all device memory
-    bool shared_rng;
-    SharedRng shared;
-    PcgJump *d_shared_pow2;
-    Pcg64 shared_base;      // host copy of the base generator (mi_get_rng: base advanced by the device's `consumed` counter)
-    // mi_set_env_attr: [A][N] float64 rows of the per-sub-environment attributes (allocated by the first call) and the set of attributes that
-    // come from them.  attr_mask != 0 ("per-lane mode"): step and rollout run the *AttrT kernels (envs_classic.h); a bit, once set, stays set
-    double *d_attr;
-    uint32_t attr_mask;
-    // mi_set_model_field (MuJoCo kinds): [LaneFields::WIDTH][N] float64 rows of gravity, actuator_gear, dof_damping, pair_friction -- allocated by the first
-    // call, all fields at once, holding the compiled-in values -- and the set of fields a call has written (mi_get_model_field answers for the others without a copy).  d_model != NULL: step and rollout run the
-    // one-lane kernels over the mjx::LaneModel env types (mjx_model.hip) for good; mj_coop is cleared with it.
-    double *d_model;
-    uint32_t model_mask;
-    // mi_set_step_wrappers: RepeatAction / StickyAction of the sub-environments inside the step.  wrap_on: the *_wrapped_kernel entry points run, with
-    // `wrap` as their last argument (its two arrays are allocated by the first call that switches StickyAction on).  per_lane: some call has switched
-    // them on -- from then on the env stays on the per-lane types (envs_classic.h *AttrT) and their one-role kernels, as after mi_set_env_attr.
-    WrapDev wrap;
-    bool wrap_on, per_lane;
-    int wrap_act_kind;  // StickyAction: the element type of the action rows it has seen (last_action is kept in that type); -1: none yet
-    // sample(mask=...) / sample(probability=...) on the action stream (action_mask.hip): the pending 32-bit half and the words of the batch in flight,
-    // the per-workgroup counts, the per-row slots; d_arg_stage: where a host caller's masks / probabilities are staged (MI_HOST only)
-    mi_actmask::Ctl *d_act_ctl;
-    uint32_t *d_act_partial, *d_act_slot;
-    void *d_arg_stage;
-    size_t arg_stage_bytes;
-    bool masked_force_repair;  // MI355ENV_MASKED_FORCE_REPAIR=1 at mi_create
-};
 
 namespace {
 
@@ -3261,8 +2587,6 @@ typedef mjx::MjEnv<mjx::HumanoidStandupModel, mjx::kHumanoidStandup> HumanoidSta
 typedef mjx::MjEnv<mjx::SwimmerModel, mjx::kSwimmer> SwimmerEnv;
 typedef mjx::MjEnv<mjx::PusherModel, mjx::kPusher> PusherEnv;
 #endif
-bool is_mj(int kind) { return (kind >= kClassicKinds && kind <= MI_ENV_HUMANOID) || (kind >= MI_ENV_HOPPER && kind <= MI_ENV_INVERTED_DOUBLE_PENDULUM) || kind == MI_ENV_REACHER || kind == MI_ENV_HUMANOID_STANDUP || kind == MI_ENV_SWIMMER || kind == MI_ENV_PUSHER; }
-bool is_tab(int kind) { return kind == MI_ENV_TABULAR || kind == MI_ENV_BLACKJACK; }  // Blackjack rides on the tabular kernels
 #ifndef MI_CLASSIC_TU
 template <class F>
 int dispatch_mj(int kind, F &&f) {
@@ -4940,4 +4264,3 @@ int mi_set_state(mi_vecenv *v, const double *state, const int32_t *elapsed, cons
 }  // extern "C"
 #pragma GCC visibility pop
 #endif  // MI_CLASSIC_TU
-#endif  // !MI_MJ_MODEL_TU

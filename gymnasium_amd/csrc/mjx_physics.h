@@ -18,7 +18,7 @@
 
 namespace mi_phys {
 
-// what the kernel needs of the engine's device state (engine.hip DevEnv): the component-major state rows [S][N] (qpos, qvel, the
+// what the kernel needs of the engine's device state (engine_types.h DevEnv): the component-major state rows [S][N] (qpos, qvel, the
 // qacc_warmstart slot), the per-env meta word whose `needs_reset_mask` bits mark a sub-environment that resets instead of stepping
 struct Args {
     double *state;

@@ -1,7 +1,7 @@
 """-m gpu: the on-device policy's per-lane states kept across launches.
 
 The classic kinds' sampling rollouts (rollout_kernel, rollout_duo_kernel) start from the per-lane states of the action stream when they are
-current and leave them current for the next launch (engine.hip ActionStream::lane; mi_action_seed prepares them); the first launch after
+current and leave them current for the next launch (engine_types.h ActionStream::lane; mi_action_seed prepares them); the first launch after
 mi_action_skip or after a captured launch, and one inside a stream capture, skips ahead from the host copy instead.  Every sequence below mixes the consumers of the one stream -- rollout(),
 sample(), step(None), np_random, seed(), a skip, a captured launch -- and is checked bit for bit against the oracle stepped with the NumPy
 sampler of the same seeded space."""
