@@ -70,6 +70,9 @@ WRAPPER_SYMBOLS += ["per_env_normalize_step", "per_env_normalize_steps"]
 # FrameStackObservation / DelayObservation / TimeAwareObservation around every scalar env (csrc/stateful_observation.hip; added to ABI 10 as well).
 WRAPPER_SYMBOLS += ["stateful_observation_step", "stateful_observation_steps"]
 SO_FRAME_STACK, SO_DELAY, SO_TIME_AWARE = 0, 1, 2  # MI_SO_*
+# DiscretizeObservation / DiscretizeAction around every scalar env (csrc/discretize.hip; added to ABI 10 as well).
+WRAPPER_SYMBOLS += ["discretize_observations", "discretize_actions"]
+DISCRETIZE_MAX_DIM, DISCRETIZE_MAX_TABLE = 32, 2048  # MI_DISCRETIZE_*
 
 
 class MiConfig(C.Structure):
@@ -215,6 +218,11 @@ class NativeLib:
                 self.stateful_observation_step = f("stateful_observation_step", [i32, vp, C.POINTER(MiStatefulObservationState), i32, i32] + [vp] * 9, i32)
                 self.stateful_observation_steps = f("stateful_observation_steps", [i32, vp, C.POINTER(MiStatefulObservationState), i32, i32] + [vp] * 4, i32)
             except ImportError:  # (likewise: the per_env stateful observation wrappers refuse at their first call)
+                pass
+            try:
+                self.discretize_observations = f("discretize_observations", [i32, vp, vp, i32, C.c_int64, i32, vp, vp, vp, vp, i32, vp], i32)
+                self.discretize_actions = f("discretize_actions", [i32, vp, vp, i32, C.c_int64, i32, vp, vp, i32, vp, i32], i32)
+            except ImportError:  # (likewise: the Discretize wrappers refuse at their first device call)
                 pass
             try:
                 self.set_step_wrappers = f("set_step_wrappers", [vp, i32, dbl, i32], i32)

@@ -355,7 +355,7 @@ class Dict(Space):
 
 
 def batch_space(space, n=1):
-    """n independent copies of ``space`` as one batched space (space_utils.py:51-100; Box, Discrete, Tuple and Dict only)."""
+    """n independent copies of ``space`` as one batched space (space_utils.py:51-106; Box, Discrete, MultiDiscrete, Tuple and Dict only)."""
     if isinstance(space, Dict):
         return Dict({key: batch_space(sp, n) for key, sp in space.spaces.items()}, seed=deepcopy(space._np_random))
     if isinstance(space, Tuple):
@@ -367,4 +367,8 @@ def batch_space(space, n=1):
     if isinstance(space, Discrete):
         return MultiDiscrete(np.full((n,), space.n, dtype=space.dtype), dtype=space.dtype, seed=deepcopy(space.np_random),
                              start=np.full((n,), space.start, dtype=space.dtype))
+    if isinstance(space, MultiDiscrete):
+        repeats = tuple([n] + [1] * space.nvec.ndim)
+        low = np.tile(space.start, repeats)
+        return Box(low=low, high=low + np.tile(space.nvec, repeats) - 1, dtype=space.dtype, seed=deepcopy(space.np_random))
     raise TypeError(f"The space provided to `batch_space` is not a supported Space instance, type: {type(space)}, {space}")

@@ -1,0 +1,352 @@
+"""gymnasium.wrappers.DiscretizeObservation / DiscretizeAction around every sub-environment, with the batch kept in HBM.
+
+  gymnasium/wrappers/transform_observation.py:755-907   DiscretizeObservation
+  gymnasium/wrappers/transform_action.py:201-345        DiscretizeAction
+
+The reference has NO vector form of the two (``VectorizeTransformObservation(env, DiscretizeObservation, ...)`` raises AttributeError), so what these
+classes reproduce is ``SyncVectorEnv([lambda: DiscretizeAction(DiscretizeObservation(make(id), ...), ...)] * N)``: the scalar wrappers around every
+sub-environment, in all three autoreset modes.  Constructor arguments, attributes (``low``, ``high``, ``n_dims``, ``bins``, ``bin_edges`` /
+``bin_centers``, ``multidiscrete``), errors and ``revert_*`` follow the reference; the spaces are its batched ones: ``MultiDiscrete([n] * N)`` for the
+flat form, ``Box(0, bins - 1, (N, D), int64)`` for ``multidiscrete=True``.
+
+Every floating-point value is computed ON THE HOST by the reference's own NumPy expressions in the Box's dtype -- ``np.linspace(low[i], high[i],
+bins[i] + 1)`` (float32 edges and centres for a float32 Box under NumPy 2), the clip bound ``high - 1e-8`` (equal to ``high`` for a float32 0.6,
+different for 0.07) -- and uploaded once per device; the kernels (csrc/discretize.hip) compare, select and divide integers.
+
+* device tensors: ONE launch of mi_discretize_observations / mi_discretize_actions per ``step()`` / ``reset()`` / per ``rollout()`` block;
+* NumPy arrays, lists, host tensors: one vectorised NumPy expression.
+
+Deviations from the reference, all refused rather than approximated: a Box that is not 1-D (the reference reads ``low.shape[0]`` and misbehaves),
+a ``prod(bins)`` of 2^62 or more in the flat form (the reference's int64 product overflows silently), more than ``MI_DISCRETIZE_MAX_DIM`` dimensions
+or a table of more than ``MI_DISCRETIZE_MAX_TABLE`` entries (the kernels keep the table in LDS), and -- DiscretizeAction -- indices that are not
+integers (the reference truncates floats in the multidiscrete form and raises IndexError in the flat form).  docs/observation_wrappers.md has the rest.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from .. import _native
+from ..gym_api import AutoresetMode, batch_space, error, spaces
+from .vector import RepeatAction, StickyAction, VectorActionWrapper, VectorWrapper, _close_fusion, _refuse_capture, _torch
+
+
+def _setup(box, bins, what, flat, table_of):
+    """The reference's constructor checks (transform_observation.py:823-851, transform_action.py:273-301) plus the stated deviations; returns
+    (low, high, n_dims, bins)."""
+    if not isinstance(box, spaces.Box):
+        raise TypeError(f"Discretize{what.capitalize()} is only compatible with Box continuous {what}s.")
+    if len(box.shape) != 1:
+        raise ValueError(f"Discretize{what.capitalize()} of gymnasium_amd takes a 1-D Box, got shape {box.shape}")
+    low, high = box.low, box.high
+    n_dims = low.shape[0]
+    if np.any(np.isinf(low)) or np.any(np.isinf(high)):
+        raise ValueError(f"Discretization requires {what} space to be finite. Found: low={low}, high={high}")
+    if isinstance(bins, int):
+        bins = np.array([bins] * n_dims)
+    else:
+        if len(bins) != n_dims:
+            raise ValueError(f"bins must match action dimensions: expected {n_dims}, got {len(bins)}")
+        bins = np.array(bins)
+    if bins.dtype.kind not in "iu" or np.any(bins < 1):
+        raise ValueError(f"bins must be positive integers, got {bins}")
+    if flat and int(np.prod([int(b) for b in bins], dtype=object)) >= 1 << 62:
+        raise ValueError(f"prod(bins) = {int(np.prod([int(b) for b in bins], dtype=object))} does not fit in 2^62: use multidiscrete=True")
+    if n_dims > _native.DISCRETIZE_MAX_DIM or table_of(bins) > _native.DISCRETIZE_MAX_TABLE:
+        raise ValueError(f"Discretize{what.capitalize()} of gymnasium_amd takes up to {_native.DISCRETIZE_MAX_DIM} dimensions and a table of up to "
+                         f"{_native.DISCRETIZE_MAX_TABLE} entries (the kernels keep it in LDS), got {n_dims} dimensions and {table_of(bins)} entries")
+    return low, high, n_dims, bins
+
+
+def _unflatten_index(bins, flat_index):
+    indices = []
+    for b in reversed(bins):
+        indices.insert(0, flat_index % b)
+        flat_index //= b
+    return indices
+
+
+def _torch_dtype(np_dtype):
+    return getattr(_torch(), np.dtype(np_dtype).name)
+
+
+def _stream(device):
+    return C.c_void_p(_torch().cuda.current_stream(device).cuda_stream)
+
+
+class DiscretizeObservation(VectorWrapper):
+    """``SyncVectorEnv`` over scalar envs each wrapped in ``gymnasium.wrappers.DiscretizeObservation(env, bins, multidiscrete)``.  An observation is
+    clipped to ``[low, high - 1e-8]`` in the Box's dtype, every component goes through ``np.digitize`` against its interior edges (NaN lands in the
+    last bin, ``bins=1`` has no edge and gives 0, ``low == high`` gives duplicate edges), and the indices are returned as they are
+    (``multidiscrete=True``) or as one mixed-radix number.  Works in NEXT_STEP, SAME_STEP (``infos["final_obs"]`` is discretized too) and DISABLED;
+    ``reset`` takes ``reset_mask``; ``rollout(T)`` transforms the whole trajectory in one launch; ``capture_steps`` is refused.  Goes over any layer
+    whose single observation space is a finite 1-D Box of float32 / float64; vector wrappers go above it (``FlattenObservation`` over the flat form
+    gives one-hot tile codings)."""
+
+    def __init__(self, env, bins, multidiscrete: bool = False):
+        box = env.single_observation_space
+        self.low, self.high, self.n_dims, self.bins = _setup(box, bins, "observation", not multidiscrete, lambda b: int(np.sum(b - 1)))
+        if np.dtype(box.dtype) not in (np.float32, np.float64):
+            raise ValueError(f"DiscretizeObservation of gymnasium_amd takes float32 / float64 observations, the Box has {box.dtype}")
+        super().__init__(env)
+        self.multidiscrete = multidiscrete
+        self.bin_edges = [np.linspace(self.low[i], self.high[i], self.bins[i] + 1)[1:-1] for i in range(self.n_dims)]
+        self._np_dtype = np.dtype(box.dtype)
+        self._hi_clip = np.asarray(self.high - 1e-8, dtype=self._np_dtype)  # (transform_observation.py:870: the Box's dtype under NEP 50)
+        if self.multidiscrete:
+            self.single_observation_space = spaces.MultiDiscrete(self.bins)
+        else:
+            self.single_observation_space = spaces.Discrete(np.prod(self.bins))
+        self.observation_space = batch_space(self.single_observation_space, self.num_envs)
+        self._bins32 = np.ascontiguousarray(self.bins, dtype=np.int32)
+        self._on_device = {}  # device index -> [low, hi_clip, edges] as one tensor of the Box's dtype
+        _close_fusion(env)
+
+    # -- the transform ----------------------------------------------------------------------------------------------------------------------
+    def observations(self, observations):
+        """The discretized batch of ``[N, D]`` observations: a device tensor through the kernel, anything else through NumPy."""
+        return self._apply(observations, 1)
+
+    def _apply(self, obs, lead):
+        torch = _torch()
+        if isinstance(obs, torch.Tensor):
+            if obs.is_cuda:
+                return self._device(obs, lead)
+            return torch.from_numpy(self._numpy(obs.numpy(), lead))
+        return self._numpy(obs, lead)
+
+    def _numpy(self, obs, lead):
+        x = np.asarray(obs)
+        if x.ndim != lead + 1 or x.shape[-1] != self.n_dims:
+            raise ValueError(f"observations must have {lead} leading axes and rows of {self.n_dims} components, got shape {x.shape}")
+        with np.errstate(invalid="ignore"):
+            clipped = np.clip(x, self.low, self._hi_clip)
+        idx = np.stack([np.digitize(clipped[..., i], self.bin_edges[i]) for i in range(self.n_dims)], axis=-1).astype(np.int64)
+        if self.multidiscrete:
+            return idx
+        flat = np.zeros(x.shape[:-1], dtype=np.int64)
+        for i in range(self.n_dims):
+            flat = flat * np.int64(self.bins[i]) + idx[..., i]
+        return flat
+
+    def _device(self, obs, lead):
+        torch = _torch()
+        if obs.dtype != _torch_dtype(self._np_dtype):
+            raise TypeError(f"DiscretizeObservation on device tensors compares in the Box's dtype: the space is {self._np_dtype}, the tensor {obs.dtype}")
+        if obs.dim() != lead + 1 or obs.shape[-1] != self.n_dims:
+            raise ValueError(f"observations must have {lead} leading axes and rows of {self.n_dims} components, got shape {tuple(obs.shape)}")
+        lib = _native.load_library()
+        if not hasattr(lib, "discretize_observations"):
+            raise ImportError(f"{lib.path}: no mi_discretize_observations; the library is older than this binding, rebuild it")
+        params = self._on_device.get(obs.device.index)
+        if params is None:
+            host = np.concatenate([self.low, self._hi_clip] + self.bin_edges).astype(self._np_dtype)
+            params = self._on_device[obs.device.index] = torch.from_numpy(host).to(obs.device)
+        x = obs.contiguous()
+        lead_shape = tuple(x.shape[:-1])
+        rows, d = int(np.prod(lead_shape, dtype=np.int64)), self.n_dims
+        out = torch.empty(lead_shape + ((d,) if self.multidiscrete else ()), dtype=torch.int64, device=x.device)
+        size = params.element_size()
+        edges = params.data_ptr() + 2 * d * size if params.numel() > 2 * d else None
+        lib.check(lib.discretize_observations(x.device.index, _stream(x.device), C.c_void_p(x.data_ptr()),
+                                              _native.MI_F32 if self._np_dtype == np.float32 else _native.MI_F64, rows, d, self._bins32.ctypes.data,
+                                              C.c_void_p(params.data_ptr()), C.c_void_p(params.data_ptr() + d * size), C.c_void_p(edges),
+                                              int(bool(self.multidiscrete)), C.c_void_p(out.data_ptr())))
+        return out
+
+    def _final(self, infos):
+        """``infos`` with ``final_obs`` discretized (SAME_STEP): an int64 tensor beside its mask, or the object array of ints / int64 rows the
+        reference builds."""
+        if "final_obs" not in infos:
+            return infos
+        infos = dict(infos)
+        final, mask = infos["final_obs"], infos["_final_obs"]
+        if hasattr(final, "data_ptr"):
+            infos["final_obs"] = self._apply(final, final.dim() - 1)
+            return infos
+        arr = np.full(len(final), None, dtype=object)
+        done = np.flatnonzero(mask)
+        if done.size:
+            got = self._numpy(np.stack([np.asarray(final[i]) for i in done]), 1)
+            for k, i in enumerate(done):
+                arr[i] = got[k].copy() if self.multidiscrete else int(got[k])
+        infos["final_obs"] = arr
+        return infos
+
+    # -- API --------------------------------------------------------------------------------------------------------------------------------
+    def reset(self, *, seed=None, options=None):
+        obs, infos = self.env.reset(seed=seed, options=options)
+        return self.observations(obs), infos
+
+    def step(self, actions):
+        obs, rewards, terminations, truncations, infos = self.env.step(actions)
+        return self.observations(obs), rewards, terminations, truncations, self._final(infos)
+
+    def rollout(self, num_steps, actions=None, **kwargs):
+        """T x ``step()`` through this wrapper: the wrapped ``rollout`` with ``"obs"`` -- and, with ``infos=True`` under SAME_STEP, the infos'
+        ``final_obs`` -- discretized, one launch over the ``[T, N, D]`` block each.  Under DISABLED the engine has no rollout launch (a finished row
+        must be reset by the caller): over the env itself the raw trajectory is collected from T ``step()`` calls, as the per_env wrappers do, and
+        then discretized in one launch; ``infos=True`` is refused there."""
+        e = self.env
+        while isinstance(e, (VectorActionWrapper, RepeatAction, StickyAction)):
+            e = e.env
+        if self.env.metadata.get("autoreset_mode") == AutoresetMode.DISABLED and not isinstance(e, VectorWrapper):
+            out = self._rollout_by_steps(int(num_steps), actions, **kwargs)
+        else:
+            out = dict(self.env.rollout(num_steps, actions, **kwargs))
+        if int(out["obs"].shape[0]) > 0:
+            out["obs"] = self._apply(out["obs"], 2)
+            if "infos" in out:
+                out["infos"] = self._final(out["infos"])
+        return out
+
+    def _rollout_by_steps(self, steps, actions, return_actions=True, infos=False):
+        torch = _torch()
+        if getattr(self.unwrapped, "output", "torch") != "torch":
+            raise error.Error("rollout() returns device tensors; create the env with output='torch'")
+        if infos:
+            raise error.Error("rollout(infos=True) through DiscretizeObservation under DISABLED autoreset is not supported: the engine has no rollout "
+                              "launch in that mode")
+        if steps < 1:
+            raise ValueError(f"rollout() under DISABLED autoreset needs num_steps >= 1, got {steps}")
+        if actions is not None and len(actions) != steps:
+            raise ValueError(f"actions must hold {steps} batches, got {len(actions)}")
+        out, taken = None, []
+        for t in range(steps):
+            a = self.action_space.sample() if actions is None else actions[t]
+            o, r, te, tr, _ = self.env.step(a)
+            if out is None:
+                out = {k: torch.empty((steps,) + tuple(v.shape), dtype=v.dtype, device=v.device)
+                       for k, v in (("obs", o), ("rewards", r), ("terminations", te), ("truncations", tr))}
+            out["obs"][t].copy_(o), out["rewards"][t].copy_(r), out["terminations"][t].copy_(te), out["truncations"][t].copy_(tr)
+            taken.append(a if isinstance(a, torch.Tensor) else torch.from_numpy(np.asarray(a)))
+        if return_actions:
+            out["actions"] = torch.stack(taken).to(out["obs"].device)
+        return out
+
+    def capture_steps(self, *args, **kwargs):
+        _refuse_capture(self, "observations")
+
+    # -- the reference's host helpers -------------------------------------------------------------------------------------------------------------
+    def revert_observation(self, obs):
+        """transform_observation.py:879-893: the edges of the bin a discretized observation of ONE sub-environment belongs to, (lows, highs)."""
+        indices = np.asarray(obs, dtype=int) if self.multidiscrete else self._unflatten_index(obs)
+        lows, highs = [], []
+        for i, idx in enumerate(indices):
+            edges = np.linspace(self.low[i], self.high[i], self.bins[i] + 1)
+            lows.append(edges[idx]), highs.append(edges[idx + 1])
+        return np.array(lows, dtype=self._np_dtype), np.array(highs, dtype=self._np_dtype)
+
+    def _flatten_indices(self, indices):
+        flat_index = 0
+        for i in range(self.n_dims):
+            flat_index *= self.bins[i]
+            flat_index += indices[i]
+        return flat_index
+
+    def _unflatten_index(self, flat_index):
+        return _unflatten_index(self.bins, flat_index)
+
+
+class DiscretizeAction(VectorActionWrapper):
+    """``SyncVectorEnv`` over scalar envs each wrapped in ``gymnasium.wrappers.DiscretizeAction(env, bins, multidiscrete)``: the env receives the
+    centre of the chosen bin of every action dimension, in the Box's dtype.  A flat index is unravelled with Python's floor ``%`` and ``//``, last
+    dimension first -- ``-1`` over 7 bins is bin 6, ``100`` is bin 2: a flat index never clamps --, a ``multidiscrete=True`` index is clamped to
+    ``[0, bins[i] - 1]``.  Transparent to observations and rewards; sits wherever ``ClipAction`` may sit, over any layer whose single action space is a
+    finite 1-D Box.  ``step``, ``rollout(T, actions)`` (one launch over the ``[T, N(, A)]`` block) and ``capture_steps(actions= / policy=callable)``
+    apply it; ``action_space.sample()`` and ``rollout(T)`` without actions draw on the host from the wrapper's own seeded space.  DEVIATION: indices
+    that are not integers are refused with TypeError."""
+
+    def __init__(self, env, bins, multidiscrete: bool = False):
+        box = env.single_action_space
+        self.low, self.high, self.n_dims, self.bins = _setup(box, bins, "action", not multidiscrete, lambda b: int(np.sum(b)))
+        if np.dtype(box.dtype) not in (np.float32, np.float64):
+            raise ValueError(f"DiscretizeAction of gymnasium_amd takes float32 / float64 actions, the Box has {box.dtype}")
+        if self.n_dims > _native.TRANSFORM_MAX_ACT_DIM:
+            raise ValueError(f"DiscretizeAction of gymnasium_amd takes up to {_native.TRANSFORM_MAX_ACT_DIM} action dimensions, the env has {self.n_dims}")
+        super().__init__(env)
+        self.multidiscrete = multidiscrete
+        self.bin_centers = [0.5 * (np.linspace(self.low[i], self.high[i], self.bins[i] + 1)[:-1] + np.linspace(self.low[i], self.high[i], self.bins[i] + 1)[1:])
+                            for i in range(self.n_dims)]
+        self._np_dtype = np.dtype(box.dtype)
+        if self.multidiscrete:
+            self.single_action_space = spaces.MultiDiscrete(self.bins)
+        else:
+            self.single_action_space = spaces.Discrete(np.prod(self.bins))
+        self.action_space = batch_space(self.single_action_space, self.num_envs)
+        self._bins32 = np.ascontiguousarray(self.bins, dtype=np.int32)
+        self._bins64 = self.bins.astype(np.int64)
+        self._table = np.concatenate(self.bin_centers).astype(self._np_dtype)  # (transform_action.py:327: np.array(centers, dtype=the Box's))
+        self._offset = np.concatenate([[0], np.cumsum(self._bins64)[:-1]])
+        self._on_device = {}
+
+    def actions(self, actions):
+        return self._apply(actions, (self.num_envs,))
+
+    def _actions_of_steps(self, block, steps):
+        return self._apply(block, (steps, self.num_envs))
+
+    def _shape(self, lead):
+        return lead + (self.n_dims,) if self.multidiscrete else lead
+
+    def _apply(self, actions, lead):
+        if hasattr(actions, "data_ptr"):
+            if actions.is_cuda:
+                return self._device(actions, lead)
+            actions = actions.numpy()
+        a = np.asarray(actions)
+        if a.dtype.kind not in "iu":
+            raise TypeError(f"DiscretizeAction takes integer indices, got {a.dtype}")
+        if a.shape != self._shape(lead):
+            raise ValueError(f"actions must have shape {self._shape(lead)}, got {a.shape}")
+        a = a.astype(np.int64)
+        if self.multidiscrete:
+            digits = np.clip(a, 0, self._bins64 - 1)
+        else:
+            cols = []
+            for b in self._bins64[::-1]:  # _unflatten_index: NumPy's % and // on integers floor like Python's
+                cols.insert(0, a % b)
+                a = a // b
+            digits = np.stack(cols, axis=-1)
+        return self._table[digits + self._offset]
+
+    def _device(self, x, lead):
+        torch = _torch()
+        if x.dtype.is_floating_point or x.dtype.is_complex or x.dtype == torch.bool:
+            raise TypeError(f"DiscretizeAction takes integer indices, got {x.dtype}")
+        if tuple(x.shape) != self._shape(lead):
+            raise ValueError(f"actions must have shape {self._shape(lead)}, got {tuple(x.shape)}")
+        lib = _native.load_library()
+        if not hasattr(lib, "discretize_actions"):
+            raise ImportError(f"{lib.path}: no mi_discretize_actions; the library is older than this binding, rebuild it")
+        if x.dtype not in (torch.int64, torch.int32):
+            x = x.to(torch.int64)
+        x = x.contiguous()
+        table = self._on_device.get(x.device.index)
+        if table is None:
+            table = self._on_device[x.device.index] = torch.from_numpy(self._table).to(x.device)
+        out = torch.empty(lead + (self.n_dims,), dtype=_torch_dtype(self._np_dtype), device=x.device)
+        rows = int(np.prod(lead, dtype=np.int64))
+        lib.check(lib.discretize_actions(x.device.index, _stream(x.device), C.c_void_p(x.data_ptr()),
+                                         _native.MI_I64 if x.dtype == torch.int64 else _native.MI_I32, rows, self.n_dims, self._bins32.ctypes.data,
+                                         C.c_void_p(table.data_ptr()), int(bool(self.multidiscrete)), C.c_void_p(out.data_ptr()),
+                                         _native.MI_F32 if self._np_dtype == np.float32 else _native.MI_F64))
+        return out
+
+    def _before_capture(self):
+        torch = _torch()
+        dev = getattr(self.unwrapped, "_device_index", 0)
+        for dtype in (torch.int64, torch.int32):  # (loads the kernels and uploads the table: a capture must do neither)
+            self._device(torch.zeros(self._shape((self.num_envs,)), dtype=dtype, device=f"cuda:{dev}"), (self.num_envs,))
+
+    # -- the reference's host helpers -------------------------------------------------------------------------------------------------------------
+    def revert_action(self, action):
+        """transform_action.py:329-338: the index of the closest bin centre per dimension for ONE sub-environment's continuous action."""
+        indices = [np.argmin(np.abs(self.bin_centers[i] - action[i])) for i in range(self.n_dims)]
+        if self.multidiscrete:
+            return np.array(indices, dtype=int)
+        return np.ravel_multi_index(indices, self.bins)
+
+    def _unflatten_index(self, flat_index):
+        return _unflatten_index(self.bins, flat_index)

@@ -589,6 +589,35 @@ int mi_one_hot(int device, void *hip_stream, const int64_t *const *parts, int nu
                int64_t *out);
 
 /*
+ * gymnasium.wrappers.DiscretizeObservation / DiscretizeAction around EVERY SCALAR env (wrappers/transform_observation.py:755-907,
+ * transform_action.py:201-345; the reference has no vector form) over a block in device memory (csrc/discretize.hip; added to ABI 10, which they
+ * leave as it is).  Both calls only enqueue on hip_stream -- no allocation, no synchronisation, no state -- and may be captured into a graph.  The
+ * device compares, selects and divides integers; every floating-point value it uses was computed on the host by the reference's own NumPy
+ * expressions in the Box's dtype.  bins: HOST array of the dimension count's positive entries, copied into the kernel's arguments; lo, hi_clip, edges,
+ * centres: DEVICE arrays of the Box's dtype.  The concatenated table is staged in LDS: at most MI_DISCRETIZE_MAX_TABLE entries, a longer one is
+ * refused with MI_ERR_INVALID_ARGUMENT (the Python wrappers refuse it in their constructors).
+ *
+ * mi_discretize_observations: in [rows][obs_dim] MI_F32 / MI_F64 (rows = num_envs for step() and reset(), T * num_envs for a rollout),
+ * obs_dim <= MI_DISCRETIZE_MAX_DIM.  Per dimension d: x is clipped to [lo[d], hi_clip[d]] (hi_clip = high - 1e-8 rounded to the Box's dtype; NaN stays
+ * NaN), then i_d = the number of edges e of dimension d with !(x < e) -- np.digitize(x, edges) on non-decreasing edges, duplicates included, and NaN in
+ * the last bin.  edges: the bins[d] - 1 interior edges of every dimension, concatenated (sum(bins - 1) <= MI_DISCRETIZE_MAX_TABLE; NULL when that is 0).
+ * multidiscrete != 0: out [rows][obs_dim] int64 of the i_d; otherwise out [rows] int64 of the mixed-radix sum idx = idx * bins[d] + i_d over d
+ * (prod(bins) <= 2^62).
+ *
+ * mi_discretize_actions: in MI_I64 / MI_I32 indices, out [rows][act_dim] of out_dtype (MI_F32 / MI_F64), act_dim <= MI_TRANSFORM_MAX_ACT_DIM.  centres:
+ * the bins[d] bin centres of every dimension, concatenated (sum(bins) <= MI_DISCRETIZE_MAX_TABLE).  multidiscrete != 0: in [rows][act_dim], every index
+ * clamped to [0, bins[d] - 1].  Otherwise in [rows] flat indices, unravelled with floor division and floor modulo, last dimension first, in 64 bits
+ * (Python's % and //: -1 over 7 bins is bin 6, a flat index never clamps); indices in [0, 2^31) under a prod(bins) < 2^31 take a 32-bit path with the
+ * same results.
+ */
+#define MI_DISCRETIZE_MAX_DIM 32
+#define MI_DISCRETIZE_MAX_TABLE 2048
+int mi_discretize_observations(int device, void *hip_stream, const void *in, int in_dtype, int64_t rows, int obs_dim, const int32_t *bins,
+                               const void *lo, const void *hi_clip, const void *edges, int multidiscrete, int64_t *out);
+int mi_discretize_actions(int device, void *hip_stream, const void *in, int in_dtype, int64_t rows, int act_dim, const int32_t *bins,
+                          const void *centres, int multidiscrete, void *out, int out_dtype);
+
+/*
  * gymnasium.wrappers.NormalizeObservation / NormalizeReward around EVERY SCALAR env (wrappers/stateful_observation.py:464-561,
  * stateful_reward.py:20-142, wrappers/utils.py:33-71) -- what SyncVectorEnv over wrapped scalar envs computes: one set of running statistics per
  * sub-environment, each updated from a batch of one (csrc/per_env_normalize.hip, arithmetic in csrc/per_env_normalize_internal.h; added to ABI 10,
