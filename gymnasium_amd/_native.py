@@ -55,6 +55,10 @@ HOST_SYMBOLS += ["set_step_wrappers"]
 # takes a model as data for ALL its envs (orc_mj_register_model), and HipVectorEnv.set_attr tells the backends apart by whether the entry point is bound.
 HOST_SYMBOLS += ["model_field_width", "set_model_field", "get_model_field"]
 MODEL_GRAVITY, MODEL_ACTUATOR_GEAR, MODEL_DOF_DAMPING, MODEL_PAIR_FRICTION = 0, 1, 2, 3  # MI_MODEL_*
+# ... and the body mass scale with the constants the engine derives from it on the device (mi_get_model_derived; added to ABI 10 as well).
+HOST_SYMBOLS += ["get_model_derived"]
+MODEL_BODY_MASS_SCALE = 4
+MODEL_DERIVED_DOF_INVWEIGHT0, MODEL_DERIVED_BODY_INVWEIGHT0, MODEL_DERIVED_MEANINERTIA = 0, 1, 2  # MI_MODEL_DERIVED_*
 WRAPPER_SYMBOLS = ["rms_create", "rms_destroy", "rms_get", "rms_set", "normalize_observation", "normalize_reward", "clip_reward", "set_step_epilogue"]
 # The normalisations over a whole trajectory (ABI 9): what the wrappers' rollout() runs over the output of mi_rollout.
 WRAPPER_SYMBOLS += ["wrapper_steps_workspace", "normalize_observation_steps", "normalize_reward_steps"]
@@ -232,6 +236,7 @@ class NativeLib:
                 self.model_field_width = f("model_field_width", [vp, i32], i32)
                 self.set_model_field = f("set_model_field", [vp, i32, vp, i32], i32)
                 self.get_model_field = f("get_model_field", [vp, i32, vp], i32)
+                self.get_model_derived = f("get_model_derived", [vp, i32, vp], i32)
             except ImportError:  # (likewise: set_attr on a MuJoCo env refuses)
                 pass
 
@@ -538,6 +543,12 @@ class Engine:
             values = np.ascontiguousarray(values, dtype=np.float64)
             assert values.shape == (self.num_envs, self.model_field_width(field)), values.shape
         self.lib.check(self.lib.set_model_field(self.handle, int(field), _ptr(values), 1 if on_device else 0))
+
+    def get_model_derived(self, which: int, width: int) -> np.ndarray:
+        """mi_get_model_derived: [num_envs, width] float64 (width = nv, 2 nbody or 1 for MODEL_DERIVED_*)."""
+        out = np.empty((self.num_envs, int(width)), dtype=np.float64)
+        self.lib.check(self.lib.get_model_derived(self.handle, int(which), _ptr(out)))
+        return out
 
     def get_model_field(self, field: int) -> np.ndarray:
         out = np.empty((self.num_envs, self.model_field_width(field)), dtype=np.float64)

@@ -13,7 +13,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 # The translation units, each compiled on its own and linked into one library; what a unit is and why it is one stands at its head.  A unit's
 # dependencies are the quoted includes it reaches (includes()), so there is no header list to keep.
-SOURCES = ["engine.hip", "physics16.hip", "physics32.hip", "wrappers.hip", "classic.hip", "mjx_model.hip", "action_mask.hip", "action_wrappers.hip",
+SOURCES = ["engine.hip", "physics16.hip", "physics32.hip", "wrappers.hip", "classic.hip", "mjx_model.hip", "mjx_mass_model.hip", "action_mask.hip", "action_wrappers.hip",
            "observation_wrappers.hip", "per_env_normalize.hip", "stateful_observation.hip", "discretize.hip"]
 OUT = os.path.join(HERE, "libmi355env.so")
 ARCH = "gfx950"

@@ -2886,7 +2886,8 @@ int launch_mj_step(mi_vecenv *v, MjStepPtrs mp) {
     const int mode = v->cfg.autoreset_mode;
     mp.extras = nullptr;
     if (v->d_model) {  // per-sub-environment model fields: the one-lane simulator with the lane's view
-        if (!mi_mjmodel::step(v->cfg.kind, mode, v->grid, v->stream, v->d, &mp)) return fail(MI_ERR_UNSUPPORTED, "no per-lane-model kernel for this env kind");
+        const bool mass = (v->model_mask & (1u << MI_MODEL_BODY_MASS_SCALE)) != 0;  // a body mass scale is held: the kernels with the mass rows in their view
+        if (!(mass ? mi_mjmass::step : mi_mjmodel::step)(v->cfg.kind, mode, v->grid, v->stream, v->d, &mp)) return fail(MI_ERR_UNSUPPORTED, "no per-lane-model kernel for this env kind");
         HIP_TRY(hipGetLastError());
         return MI_OK;
     }
@@ -3257,14 +3258,22 @@ int mi_get_env_attr(mi_vecenv *v, int attr, double *host_out) {
 struct ModelFieldInfo {
     int width[MI_MODEL_FIELD_COUNT], offset[MI_MODEL_FIELD_COUNT], total;
     const double *defaults[MI_MODEL_FIELD_COUNT];
+    // the rows derived from the body mass scale (MI_MODEL_DERIVED_*) and the compiled model's values of them
+    int dwidth[MI_MODEL_DERIVED_COUNT], doffset[MI_MODEL_DERIVED_COUNT];
+    const double *dcompiled[MI_MODEL_DERIVED_COUNT];
 };
+static const double kUnitMassScale[32] = {1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1};
 static bool model_field_info(const mi_vecenv *v, ModelFieldInfo &out) {
     if (!v || !is_mj(v->cfg.kind)) return false;
     return dispatch_mj(v->cfg.kind, [&](auto env) -> int {
                typedef typename decltype(env)::Model M;
-               typedef mjx::LaneFields<M> V;
-               const ModelFieldInfo f = {{3, M::NU, M::NV, M::NPAIR}, {V::OFF_GRAVITY, V::OFF_GEAR, V::OFF_DAMPING, V::OFF_FRICTION}, V::WIDTH,
-                                         {M::gravity, M::actuator_gear, M::dof_damping, M::pair_friction}};
+               typedef mjx::MassLaneFields<M> V;
+               static_assert(M::NBODY <= 32, "kUnitMassScale");
+               static const double kMeanInertia = M::MEANINERTIA;  // (one per robot: the lambda is instantiated per env type)
+               const ModelFieldInfo f = {{3, M::NU, M::NV, M::NPAIR, M::NBODY}, {V::OFF_GRAVITY, V::OFF_GEAR, V::OFF_DAMPING, V::OFF_FRICTION, V::OFF_MASS_SCALE}, V::WIDTH,
+                                         {M::gravity, M::actuator_gear, M::dof_damping, M::pair_friction, kUnitMassScale},
+                                         {M::NV, 2 * M::NBODY, 1}, {V::OFF_DOF_INVWEIGHT, V::OFF_BODY_INVWEIGHT, V::OFF_MEANINERTIA},
+                                         {M::dof_invweight0, &M::body_invweight0[0][0], &kMeanInertia}};
                out = f;
                return (int)MI_OK;
            }) == MI_OK;
@@ -3294,6 +3303,7 @@ int mi_set_model_field(mi_vecenv *v, int field, const double *values, int on_dev
             if (!(x - x == 0.0)) return fail(MI_ERR_INVALID_ARGUMENT, "mi_set_model_field: non-finite value");
             if (field == MI_MODEL_DOF_DAMPING && x < 0.0) return fail(MI_ERR_INVALID_ARGUMENT, "mi_set_model_field: dof_damping must be >= 0");
             if (field == MI_MODEL_PAIR_FRICTION && x < 1e-5) return fail(MI_ERR_INVALID_ARGUMENT, "mi_set_model_field: pair_friction must be >= 1e-5 (MuJoCo's minimum)");
+            if (field == MI_MODEL_BODY_MASS_SCALE && x < 1e-3) return fail(MI_ERR_INVALID_ARGUMENT, "mi_set_model_field: body_mass_scale must be >= 1e-3");
         }
     if (set_device(v)) return MI_ERR_HIP;
     if (!v->d_model) {  // every field at once, at the compiled-in values: a later field needs no allocation (mi_step stays capturable)
@@ -3307,6 +3317,9 @@ int mi_set_model_field(mi_vecenv *v, int field, const double *values, int on_dev
         for (int a = 0; a < MI_MODEL_FIELD_COUNT; a++)
             for (int c = 0; c < f.width[a]; c++)
                 for (size_t i = 0; i < N; i++) host[(size_t)(f.offset[a] + c) * N + i] = f.defaults[a][c];
+        for (int a = 0; a < MI_MODEL_DERIVED_COUNT; a++)  // the compiled model's constants, copied: nothing is derived until a scale is set
+            for (int c = 0; c < f.dwidth[a]; c++)
+                for (size_t i = 0; i < N; i++) host[(size_t)(f.doffset[a] + c) * N + i] = f.dcompiled[a][c];
         if (hipMemcpyAsync(rows, host.data(), sizeof(double) * host.size(), hipMemcpyHostToDevice, v->stream) != hipSuccess ||
             hipStreamSynchronize(v->stream) != hipSuccess) {
             (void)hipFree(rows);
@@ -3314,6 +3327,10 @@ int mi_set_model_field(mi_vecenv *v, int field, const double *values, int on_dev
         }
         v->d_model = rows, v->d.mj.rows = rows;
         v->mj_coop = false;  // for good: the cooperative kernels read the compiled-in model
+    }
+    if (field == MI_MODEL_BODY_MASS_SCALE && values && !mi_mjmass::preload(v->cfg.kind)) {  // the kernels with the mass rows, loaded now like the others
+        (void)hipGetLastError();
+        return fail(MI_ERR_HIP, "mi_set_model_field: could not load the per-lane-model kernels");
     }
     v->model_mask |= 1u << field;
     if (w == 0) return MI_OK;  // (a robot without contact pairs)
@@ -3327,6 +3344,20 @@ int mi_set_model_field(mi_vecenv *v, int field, const double *values, int on_dev
             for (size_t i = 0; i < N; i++) host[(size_t)c * N + i] = values ? values[i * (size_t)w + c] : f.defaults[field][c];
         HIP_TRY(hipMemcpyAsync(dst, host.data(), sizeof(double) * host.size(), hipMemcpyHostToDevice, v->stream));
         HIP_TRY(hipStreamSynchronize(v->stream));
+    }
+    if (field != MI_MODEL_BODY_MASS_SCALE) return MI_OK;
+    if (values) {  // the constants the model compiler derives from the masses, per sub-environment, on the device and on the env's stream
+        if (!mi_mjmass::derive_constants(v->cfg.kind, v->grid, v->stream, v->d_model, (int)N)) return fail(MI_ERR_UNSUPPORTED, "no per-lane-model kernel for this env kind");
+        HIP_TRY(hipGetLastError());
+    } else {  // the stock model: its compiled-in constants, copied
+        const int first = f.doffset[0], rows = f.total - first;  // (the derived rows are the tail of the block)
+        std::vector<double> host((size_t)rows * N);
+        for (int a = 0; a < MI_MODEL_DERIVED_COUNT; a++)
+            for (int c = 0; c < f.dwidth[a]; c++)
+                for (size_t i = 0; i < N; i++) host[(size_t)(f.doffset[a] - first + c) * N + i] = f.dcompiled[a][c];
+        HIP_TRY(hipMemcpyAsync(v->d_model + (size_t)first * N, host.data(), sizeof(double) * host.size(), hipMemcpyHostToDevice, v->stream));
+        HIP_TRY(hipStreamSynchronize(v->stream));
+        v->model_mask &= ~(1u << MI_MODEL_BODY_MASS_SCALE);  // no scale is held: back to the kernels without the mass rows (mjx_model.hip)
     }
     return MI_OK;
 }
@@ -3346,6 +3377,27 @@ int mi_get_model_field(mi_vecenv *v, int field, double *host_out) {
     if (set_device(v)) return MI_ERR_HIP;
     std::vector<double> host((size_t)w * N);
     HIP_TRY(hipMemcpyAsync(host.data(), v->d_model + (size_t)f.offset[field] * N, sizeof(double) * host.size(), hipMemcpyDeviceToHost, v->stream));
+    HIP_TRY(hipStreamSynchronize(v->stream));
+    for (size_t i = 0; i < N; i++)
+        for (int c = 0; c < w; c++) host_out[i * (size_t)w + c] = host[(size_t)c * N + i];
+    return MI_OK;
+}
+
+int mi_get_model_derived(mi_vecenv *v, int which, double *host_out) {
+    ModelFieldInfo f;
+    if (const int rc = model_field_check(v, MI_MODEL_BODY_MASS_SCALE, f)) return rc;
+    if (which < 0 || which >= MI_MODEL_DERIVED_COUNT) return fail(MI_ERR_INVALID_ARGUMENT, "derived model constant id out of range");
+    if (!host_out) return fail(MI_ERR_INVALID_ARGUMENT, "null argument");
+    const size_t N = (size_t)v->cfg.num_envs;
+    const int w = f.dwidth[which];
+    if (!(v->model_mask & (1u << MI_MODEL_BODY_MASS_SCALE))) {  // no scale was ever set: the compiled model's values, no synchronisation
+        for (size_t i = 0; i < N; i++)
+            for (int c = 0; c < w; c++) host_out[i * (size_t)w + c] = f.dcompiled[which][c];
+        return MI_OK;
+    }
+    if (set_device(v)) return MI_ERR_HIP;
+    std::vector<double> host((size_t)w * N);
+    HIP_TRY(hipMemcpyAsync(host.data(), v->d_model + (size_t)f.doffset[which] * N, sizeof(double) * host.size(), hipMemcpyDeviceToHost, v->stream));
     HIP_TRY(hipStreamSynchronize(v->stream));
     for (size_t i = 0; i < N; i++)
         for (int c = 0; c < w; c++) host_out[i * (size_t)w + c] = host[(size_t)c * N + i];
@@ -3557,6 +3609,12 @@ int mi_reset(mi_vecenv *v, const uint8_t *mask, const double *bounds, void *obs,
     }
     int rc = is_mj(v->cfg.kind) ? dispatch_mj(v->cfg.kind, [&](auto env) -> int {
         using E = decltype(env);
+        // a body mass scale was set: the Humanoids' reset reads the lane's body masses (an env that never set one keeps the stock reset kernel, bit for bit)
+        if (v->d_model && (v->model_mask & (1u << MI_MODEL_BODY_MASS_SCALE))) {
+            if (!mi_mjmass::reset(v->cfg.kind, v->grid, v->stream, v->d, dm, (double *)dobs, v->lay.obs_dim)) return fail(MI_ERR_UNSUPPORTED, "no per-lane-model kernel for this env kind");
+            HIP_TRY(hipGetLastError());
+            return (int)MI_OK;
+        }
         hipLaunchKernelGGL((mj_reset_kernel<E>), dim3(v->grid), dim3(kBlock), 0, v->stream, v->d, dm, (double *)dobs, v->lay.obs_dim);
         HIP_TRY(hipGetLastError());
         return (int)MI_OK;
@@ -4032,7 +4090,7 @@ static int rollout_impl(mi_vecenv *v, int T, const mi_rollout_io *io, const Roll
             using E = decltype(env);
             const RolloutExtra e = ex ? *ex : RolloutExtra{};
             if (v->d_model) {
-                if (!mi_mjmodel::rollout(v->cfg.kind, v->cfg.autoreset_mode, sample, v->grid, v->stream, v->d, p, as, T, v->lay.obs_dim, in_f64, e))
+                if (!((v->model_mask & (1u << MI_MODEL_BODY_MASS_SCALE)) ? mi_mjmass::rollout : mi_mjmodel::rollout)(v->cfg.kind, v->cfg.autoreset_mode, sample, v->grid, v->stream, v->d, p, as, T, v->lay.obs_dim, in_f64, e))
                     return fail(MI_ERR_UNSUPPORTED, "no per-lane-model kernel for this env kind");
                 HIP_TRY(hipGetLastError());
                 return (int)MI_OK;

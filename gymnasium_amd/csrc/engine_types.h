@@ -36,7 +36,7 @@ struct TabTable {
 // Per-sub-environment model fields of a MuJoCo env (mi_set_model_field), as they ride in DevEnv.
 struct MjModelDev {
     int tab_ints[3];     // tab.nS, tab.nA, tab.K of the union below: always 0 here
-    const double *rows;  // [mjx::LaneFields::WIDTH][N], read by the mjx::LaneModel instantiations only; NULL until the first mi_set_model_field
+    const double *rows;  // [mjx::MassLaneFields::WIDTH][N], read by the mjx::LaneModel / MassLaneModel instantiations only; NULL until the first mi_set_model_field
 };
 // Device view of one vector environment (passed by value as a kernel argument).
 struct DevEnv {
@@ -178,6 +178,20 @@ bool preload(int kind);
 bool rollout(int kind, int autoreset_mode, bool sample, int grid, hipStream_t stream, const mi_internal::DevEnv &d, const mi_internal::RolloutPtrs &p,
              const mi_internal::ActionStream &as, int T, int obs_dim, int in_f64, const mi_internal::RolloutExtra &ex);
 }  // namespace mi_mjmodel
+// The same over the mjx::MassLaneModel env types (mjx_mass_model.hip): what an env runs while it holds a body mass scale (mi_set_model_field
+// MI_MODEL_BODY_MASS_SCALE with values; NULL takes it back to the kernels above).  A model type and a unit of their own, so that the kernels above stay
+// without the mass rows.
+namespace mi_mjmass {
+bool step(int kind, int autoreset_mode, int grid, hipStream_t stream, const mi_internal::DevEnv &d, const void *mj_step_ptrs);
+bool preload(int kind);  // (the constants kernel included)
+bool rollout(int kind, int autoreset_mode, bool sample, int grid, hipStream_t stream, const mi_internal::DevEnv &d, const mi_internal::RolloutPtrs &p,
+             const mi_internal::ActionStream &as, int T, int obs_dim, int in_f64, const mi_internal::RolloutExtra &ex);
+// mj_reset_kernel over the same env types: the Humanoids' reset observation and tracked point read the sub-environment's body masses
+bool reset(int kind, int grid, hipStream_t stream, const mi_internal::DevEnv &d, const uint8_t *mask, double *obs, int obs_dim);
+// mj_model_constants_kernel: dof_invweight0, body_invweight0 and meaninertia of every sub-environment from the body mass scale rows of `rows`
+// (the env's [mjx::MassLaneFields::WIDTH][N] block), written into the derived rows of the same block
+bool derive_constants(int kind, int grid, hipStream_t stream, double *rows, int N);
+}  // namespace mi_mjmass
 namespace {
 // argument of mj_step_kernel (mj_glue_kernels.h); crosses to mi_mjmodel::step as a const void *
 struct MjStepPtrs {
@@ -277,7 +291,8 @@ struct mi_vecenv {
     // come from them.  attr_mask != 0 ("per-lane mode"): step and rollout run the *AttrT kernels (envs_classic.h); a bit, once set, stays set
     double *d_attr;
     uint32_t attr_mask;
-    // mi_set_model_field (MuJoCo kinds): [LaneFields::WIDTH][N] float64 rows of gravity, actuator_gear, dof_damping, pair_friction -- allocated by the first
+    // mi_set_model_field (MuJoCo kinds): [MassLaneFields::WIDTH][N] float64 rows of gravity, actuator_gear, dof_damping, pair_friction, the body mass scale and the
+    // constants derived from it (dof_invweight0, body_invweight0, meaninertia: the compiled-in values until a scale is set) -- allocated by the first
     // call, all fields at once, holding the compiled-in values -- and the set of fields a call has written (mi_get_model_field answers for the others without a copy).  d_model != NULL: step and rollout run the
     // one-lane kernels over the mjx::LaneModel env types (mjx_model.hip) for good; mj_coop is cleared with it.
     double *d_model;

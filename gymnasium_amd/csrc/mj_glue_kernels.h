@@ -1,6 +1,6 @@
 // mj_glue_kernels.h -- the per-lane kernels of the MuJoCo family around the simulator of mjx_kernels.h: the vectoriser's state machine, reward,
 // observation and statistics of one sub-environment per lane.  engine.hip instantiates them over the stock models, mjx_model.hip over the
-// mjx::LaneModel env types.
+// mjx::LaneModel env types, mjx_mass_model.hip over the mjx::MassLaneModel ones.
 #ifndef MI355ENV_MJ_GLUE_KERNELS_H
 #define MI355ENV_MJ_GLUE_KERNELS_H
 #include <type_traits>
@@ -52,9 +52,12 @@ MI_DEV void mj_store(const DevEnv &d, int i, const MjLane<E> &L) {
     d.ep_ret[i] = L.ep_ret, d.ep_len[i] = L.ep_len;
 }
 template <class E>
-MI_DEV void mj_autoreset(const DevEnv &d, int i, MjLane<E> &L, double *obs) {
+MI_DEV void mj_autoreset(const DevEnv &d, int i, MjLane<E> &L, double *obs, const MjLaneFields<E> *lane = nullptr) {
     Pcg64 rng = load_rng(d, i);
-    E::reset(rng, L.s, d.P, obs);
+    if constexpr (mjx::ModelView<typename E::Model>::MASS_PER_LANE)
+        E::reset(rng, L.s, d.P, obs, lane);  // (the Humanoids' reset reads the lane's body masses)
+    else
+        E::reset(rng, L.s, d.P, obs);
     store_rng_state(d, i, rng);
     L.elapsed = 0, L.ep_ret = 0.0, L.ep_len = 0;
 }
@@ -68,7 +71,7 @@ MI_DEV void mj_lane_step(const DevEnv &d, int i, MjLane<E> &L, const mjx::ActRow
                          const double *extras = nullptr, double *final_info = nullptr, const MjLaneFields<E> *lane = nullptr) {
     te = tr = false, reward = 0.0;
     if (MODE == MI_AUTORESET_NEXT_STEP && (L.flags & kNeedsReset)) {
-        mj_autoreset<E>(d, i, L, obs);
+        mj_autoreset<E>(d, i, L, obs, lane);
         if (info) E::reset_info(L.s, info);
         st.reset_steps++;
     } else if (MODE == MI_AUTORESET_DISABLED && (L.flags & kNeedsReset)) {
@@ -104,7 +107,7 @@ MI_DEV void mj_lane_step(const DevEnv &d, int i, MjLane<E> &L, const mjx::ActRow
             for (int k = 0; k < E::obs_dim(d.P); k++) final_obs[k] = obs[k];
         if (info && final_info)  // sync_vector_env.py:309-317: the finishing step's info goes to "final_info" ...
             for (int k = 0; k < E::INFO; k++) final_info[k] = info[k];
-        mj_autoreset<E>(d, i, L, obs);
+        mj_autoreset<E>(d, i, L, obs, lane);
         if (info) E::reset_info(L.s, info);  // ... and the top-level entries of this sub-env are its reset info (:319)
     }
     if (done && MODE != MI_AUTORESET_SAME_STEP)
@@ -158,7 +161,13 @@ __global__ __launch_bounds__(kBlock) void mj_reset_kernel(DevEnv d, const uint8_
     MjLane<E> L;
     mj_load<E>(d, i, L);
     L.flags &= ~kNeedsReset;
-    mj_autoreset<E>(d, i, L, obs ? obs + (size_t)i * obs_dim : nullptr);
+    if constexpr (MjLaneHolder<E>::HAS) {  // (two spellings, as in mj_step_kernel: the stock kernels stay what they were)
+        MjLaneHolder<E> lane;
+        lane.load(d, i);
+        mj_autoreset<E>(d, i, L, obs ? obs + (size_t)i * obs_dim : nullptr, lane.get());
+    } else {
+        mj_autoreset<E>(d, i, L, obs ? obs + (size_t)i * obs_dim : nullptr);
+    }
     mj_store<E>(d, i, L);
 }
 

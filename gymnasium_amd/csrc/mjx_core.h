@@ -167,18 +167,27 @@ struct Contact {
 };
 
 // ---- model view -------------------------------------------------------------------------------------------------------
-// The four model fields a sub-environment may have values of its own for (mi_set_model_field): opt.gravity, actuator_gear[:, 0],
-// dof_damping and the sliding friction of the contact pairs.  No compiled-model quantity is derived from any of them
-// (tests/test_model_attrs_host.py), so they can be replaced without recompiling the model.  The simulator reads them through the view
-// that its Data inherits.  For a generated model the view is empty and folds to the model's constants: the code of every stock
+// The model fields a sub-environment may have values of its own for (mi_set_model_field): opt.gravity, actuator_gear[:, 0],
+// dof_damping, the sliding friction of the contact pairs and a scale of every body's mass and inertia tensor.  No compiled-model quantity
+// is derived from the first four (tests/test_model_attrs_host.py), so they can be replaced without recompiling the model.  The mass scale
+// drags dof_invweight0, body_invweight0 and meaninertia with it: the engine derives them per sub-environment on the device
+// (derive_mass_constants below, mj_model_constants_kernel) and keeps them in rows beside the fields.  The simulator reads all of them
+// through the view that its Data inherits.  For a generated model the view is empty and folds to the model's constants: the code of every stock
 // instantiation is what it was before the view existed.  LaneModel<M0> is M0 with a view that refers to one sub-environment's values
 // (LaneFields, loaded once per launch): the simulator instantiated for it is the per-lane one.  Like the rest of this pipeline their
 // parity with `mujoco` is UNPINNED; the CPU oracle, which takes the same fields as data, is the reference.
+// MassLaneModel<M0> is the same with the body mass scale and the constants derived from it in the view as well, a type of its own: an env
+// that sets only the first four fields keeps kernels that neither load nor carry the mass rows (docs/results_log.md: HalfCheetah lost 5.7 %
+// with them in the one view).
 template <class M0>
 struct LaneModel : M0 {};
+template <class M0>
+struct MassLaneModel : M0 {
+    typedef M0 Stock;
+};
 template <class M>
 struct LaneFields {
-    // rows of the engine's [WIDTH][N] float64 block (component-major, like the state rows)
+    // rows of the engine's float64 block (component-major, like the state rows, [MassLaneFields::WIDTH][N]); these four come first
     static constexpr int OFF_GRAVITY = 0, OFF_GEAR = 3, OFF_DAMPING = 3 + M::NU, OFF_FRICTION = 3 + M::NU + M::NV, WIDTH = 3 + M::NU + M::NV + M::NPAIR;
     double gravity[3], gear[M::NU], damping[M::NV], friction[M::NPAIR > 0 ? M::NPAIR : 1];
     // sub-environment i of N: one coalesced load per row
@@ -190,7 +199,34 @@ struct LaneFields {
     }
 };
 template <class M>
-struct ModelView {
+struct MassLaneFields : LaneFields<M> {
+    // behind the four fields: the scale of the bodies' mass and inertia, then what is derived from it: dof_invweight0[NV], body_invweight0[NBODY][2], meaninertia
+    static constexpr int OFF_MASS_SCALE = LaneFields<M>::WIDTH, OFF_DOF_INVWEIGHT = OFF_MASS_SCALE + M::NBODY, OFF_BODY_INVWEIGHT = OFF_DOF_INVWEIGHT + M::NV,
+                         OFF_MEANINERTIA = OFF_BODY_INVWEIGHT + 2 * M::NBODY, WIDTH = OFF_MEANINERTIA + 1;
+    double mass_scale[M::NBODY], dof_invweight0[M::NV], body_invweight0[M::NBODY], meaninertia;  // (the simulator reads the translational body weight only)
+    MJX_DEV void load(const double *rows, size_t N, size_t i) {
+        LaneFields<M>::load(rows, N, i);
+        load_mass_scale(rows, N, i);
+        for (int k = 0; k < M::NV; k++) dof_invweight0[k] = rows[(size_t)(OFF_DOF_INVWEIGHT + k) * N + i];
+        for (int k = 0; k < M::NBODY; k++) body_invweight0[k] = rows[(size_t)(OFF_BODY_INVWEIGHT + 2 * k) * N + i];
+        meaninertia = rows[(size_t)(OFF_MEANINERTIA)*N + i];
+    }
+    MJX_DEV void load_mass_scale(const double *rows, size_t N, size_t i) {
+        for (int k = 0; k < M::NBODY; k++) mass_scale[k] = rows[(size_t)(OFF_MASS_SCALE + k) * N + i];
+    }
+};
+// the masses and what is derived from them, as compiled: the view of a generated model and of LaneModel
+template <class M>
+struct CompiledMassView {
+    static constexpr bool MASS_PER_LANE = false;
+    static MJX_DEV double body_mass(int b) { return M::body_mass[b]; }
+    static MJX_DEV const double *body_inertia(int b, double *) { return M::body_inertia[b]; }  // (the table itself; the buffer is the lane view's)
+    static MJX_DEV double dof_invweight0(int i) { return M::dof_invweight0[i]; }
+    static MJX_DEV double body_invweight0(int b) { return M::body_invweight0[b][0]; }
+    static MJX_DEV double meaninertia() { return M::MEANINERTIA; }
+};
+template <class M>
+struct ModelView : CompiledMassView<M> {
     typedef void Fields;  // nothing to bind
     MJX_DEV void bind(const Fields *) {}
     static MJX_DEV double gravity(int k) { return M::gravity[k]; }
@@ -199,7 +235,7 @@ struct ModelView {
     static MJX_DEV double friction(int p) { return M::pair_friction[p]; }
 };
 template <class M0>
-struct ModelView<LaneModel<M0>> {
+struct ModelView<LaneModel<M0>> : CompiledMassView<M0> {
     typedef LaneFields<M0> Fields;
     const Fields *lane;
     MJX_DEV void bind(const Fields *f) { lane = f; }
@@ -207,6 +243,27 @@ struct ModelView<LaneModel<M0>> {
     MJX_DEV double gear(int u) const { return lane->gear[u]; }
     MJX_DEV double damping(int i) const { return lane->damping[i]; }
     MJX_DEV double friction(int p) const { return lane->friction[p]; }
+};
+template <class M0>
+struct ModelView<MassLaneModel<M0>> {
+    typedef MassLaneFields<M0> Fields;
+    static constexpr bool MASS_PER_LANE = true;
+    const Fields *lane;
+    MJX_DEV void bind(const Fields *f) { lane = f; }
+    MJX_DEV double gravity(int k) const { return lane->gravity[k]; }
+    MJX_DEV double gear(int u) const { return lane->gear[u]; }
+    MJX_DEV double damping(int i) const { return lane->damping[i]; }
+    MJX_DEV double friction(int p) const { return lane->friction[p]; }
+    // a density change: mass and inertia tensor times the lane's factor (the products compiler.scaled() forms)
+    MJX_DEV double body_mass(int b) const { return M0::body_mass[b] * lane->mass_scale[b]; }
+    MJX_DEV const double *body_inertia(int b, double *buf) const {
+#pragma unroll
+        for (int k = 0; k < 9; k++) buf[k] = M0::body_inertia[b][k] * lane->mass_scale[b];
+        return buf;
+    }
+    MJX_DEV double dof_invweight0(int i) const { return lane->dof_invweight0[i]; }
+    MJX_DEV double body_invweight0(int b) const { return lane->body_invweight0[b]; }
+    MJX_DEV double meaninertia() const { return lane->meaninertia; }
 };
 
 // per-lane simulation state of one forward evaluation
@@ -303,15 +360,16 @@ MJX_DEV void com_pos(Data<M> &d) {
     double mass = 0, c[3] = {0, 0, 0};
 #pragma unroll
     for (int b = 1; b < M::NBODY; b++) {
-        mass += M::body_mass[b];
-        c[0] += M::body_mass[b] * d.xipos[b][0], c[1] += M::body_mass[b] * d.xipos[b][1], c[2] += M::body_mass[b] * d.xipos[b][2];
+        mass += d.body_mass(b);
+        c[0] += d.body_mass(b) * d.xipos[b][0], c[1] += d.body_mass(b) * d.xipos[b][1], c[2] += d.body_mass(b) * d.xipos[b][2];
     }
     d.com[0] = c[0] / mass, d.com[1] = c[1] / mass, d.com[2] = c[2] / mass;
 #pragma unroll
     for (int k = 0; k < 10; k++) d.cinert[0][k] = 0;
 #pragma unroll
     for (int b = 1; b < M::NBODY; b++) {
-        const double *R = d.xmat[b], *I = M::body_inertia[b];
+        double scaled[9];
+        const double *R = d.xmat[b], *I = d.body_inertia(b, scaled);
         double off[3] = {d.xipos[b][0] - d.com[0], d.xipos[b][1] - d.com[1], d.xipos[b][2] - d.com[2]};
         double T[9], W[9];  // T = R I, W = T R^T
 #pragma unroll
@@ -322,7 +380,7 @@ MJX_DEV void com_pos(Data<M> &d) {
         for (int i = 0; i < 3; i++)
 #pragma unroll
             for (int j = 0; j < 3; j++) W[3 * i + j] = T[3 * i] * R[3 * j] + T[3 * i + 1] * R[3 * j + 1] + T[3 * i + 2] * R[3 * j + 2];
-        const double mm = M::body_mass[b], dd = dot3(off, off);
+        const double mm = d.body_mass(b), dd = dot3(off, off);
         double *ci = d.cinert[b];
         ci[0] = W[0] + mm * (dd - off[0] * off[0]), ci[1] = W[4] + mm * (dd - off[1] * off[1]), ci[2] = W[8] + mm * (dd - off[2] * off[2]);
         ci[3] = W[1] - mm * off[0] * off[1], ci[4] = W[2] - mm * off[0] * off[2], ci[5] = W[5] - mm * off[1] * off[2];
@@ -760,7 +818,7 @@ MJX_DEV void make_constraint(Data<M> &d) {
             if (dist < M::jnt_margin[j] && d.nlimit < M::NJNT) {
                 const int n = d.nlimit++, dof = M::jnt_dofadr[j];
                 double k, b, imp, R;
-                row_params<M>(M::jnt_solref[j], M::jnt_solimp[j], dist, M::jnt_margin[j], M::dof_invweight0[dof], k, b, imp, R);
+                row_params<M>(M::jnt_solref[j], M::jnt_solimp[j], dist, M::jnt_margin[j], d.dof_invweight0(dof), k, b, imp, R);
                 d.lim_dof[n] = dof, d.lim_sign[n] = -side, d.lim_D[n] = 1.0 / R;
                 d.lim_aref[n] = -b * (-side * d.qvel[dof]) - k * imp * (dist - M::jnt_margin[j]);
             }
@@ -770,7 +828,7 @@ MJX_DEV void make_constraint(Data<M> &d) {
         const Contact<M> &con = d.con[c];
         const int p = con.pair;
         const int b1 = M::geom_bodyid[M::pair_geom1[p]], b2 = M::geom_bodyid[M::pair_geom2[p]];
-        const double tran = M::body_invweight0[b1][0] + M::body_invweight0[b2][0], mu = d.friction(p);
+        const double tran = d.body_invweight0(b1) + d.body_invweight0(b2), mu = d.friction(p);
         double k, b, imp, R;
         const bool pyramid = M::pair_condim[p] > 1;
         row_params<M>(M::pair_solref[p], M::pair_solimp[p], con.dist, M::pair_margin[p], pyramid ? tran + mu * mu * tran : tran, k, b, imp, R);
@@ -853,7 +911,7 @@ MJX_DEV int solve_newton(Data<M> &d) {
     double x[NV], grad[NV], dir[NV], H[Data<M>::NTRI], HL[Data<M>::NTRI], dx[NV], Mdx[NV];
 #pragma unroll
     for (int i = 0; i < NV; i++) x[i] = d.qacc_warm[i];  // warm start; M (x - x_smooth) = M x - qfrc_smooth needs no x_smooth
-    const double scale = 1.0 / (M::MEANINERTIA * (NV > 1 ? NV : 1));
+    const double scale = 1.0 / (d.meaninertia() * (NV > 1 ? NV : 1));
     int it = 0;
     for (; it < 50; it++) {
         sym_mul<NV>(d.qM, x, dx);
@@ -996,7 +1054,7 @@ MJX_DEV int solve_pgs(Data<M> &d) {
     }
 #pragma unroll
     for (int i = 0; i < NV; i++) a[i] += d.qacc_smooth[i];
-    const double scale = 1.0 / (M::MEANINERTIA * (NV > 1 ? NV : 1));
+    const double scale = 1.0 / (d.meaninertia() * (NV > 1 ? NV : 1));
     int it = 0;
     for (; it < M::ITERATIONS;) {
         double improvement = 0;
@@ -1042,7 +1100,13 @@ MJX_DEV void fluid(const Data<M> &d, double *qfrc) {
     constexpr double PI = 3.14159265358979323846;
 #pragma unroll
     for (int b = 1; b < M::NBODY; b++) {
-        if (M::body_mass[b] < 1e-15) continue;
+        // (two spellings of one test, on purpose: through the view the stock Swimmer's forward pass comes out with other registers and other
+        // products contracted -- scripts/kernel_stream_diff.py -- and the stock kernels are to stay what they were instruction for instruction)
+        if constexpr (ModelView<M>::MASS_PER_LANE) {
+            if (d.body_mass(b) < 1e-15) continue;
+        } else {
+            if (M::body_mass[b] < 1e-15) continue;
+        }
         double R[9];
 #pragma unroll
         for (int i = 0; i < 3; i++)
@@ -1245,6 +1309,67 @@ MJX_DEV void contact_forces(const Data<M> &d, double cfrc_ext[M::NBODY][6]) {
             for (int k = 0; k < 3; k++) cfrc_ext[b][k] += sg * tq[k], cfrc_ext[b][3 + k] += sg * F[k];
         }
     }
+}
+
+// ---- the constants a model compiler derives from the masses (compiler.py derive_mass_constants) --------------------------------
+// For a sub-environment with a body mass scale of its own (d is bound to its fields; only the scale is read): the simulator's own
+// kinematics, com, cinert, composite-rigid-body pass and factorisation at qpos0, so M is the matrix the step kernels build; then
+//   dof_invweight0  = diag(M^-1), one triangular solve pair per dof, averaged over the translational and over the rotational dofs of a free joint,
+//   body_invweight0 = trace / 3 of the translational and of the rotational block of J M^-1 J^T, J at the body's centre of mass from cdof,
+//                     floored at kMinVal (a body without a dof above it -- Pusher's goal -- sits on the floor exactly, as in the compiler),
+//   meaninertia     = mean(diag M).
+template <class M>
+MJX_DEV void derive_mass_constants(Data<M> &d, double *dof_invweight0, double (*body_invweight0)[2], double &meaninertia) {
+    constexpr int NV = M::NV;
+#pragma unroll
+    for (int k = 0; k < M::NQ; k++) d.qpos[k] = M::qpos0[k];
+    kinematics<M>(d);
+    com_pos<M>(d);
+    crb<M>(d);
+    chol_factor<NV>(d.qM, d.qL);
+    double diag[NV], x[NV];
+    for (int i = 0; i < NV; i++) {
+        for (int k = 0; k < NV; k++) x[k] = k == i ? 1.0 : 0.0;
+        chol_solve<NV>(d.qL, x);
+        diag[i] = x[i];
+    }
+#pragma unroll
+    for (int j = 0; j < M::NJNT; j++) {
+        const int a = M::jnt_dofadr[j];
+        if (M::jnt_type[j] == FREE) {
+            const double t = (diag[a] + diag[a + 1] + diag[a + 2]) / 3.0, r = (diag[a + 3] + diag[a + 4] + diag[a + 5]) / 3.0;
+            for (int k = 0; k < 3; k++) dof_invweight0[a + k] = t, dof_invweight0[a + 3 + k] = r;
+        } else {
+            dof_invweight0[a] = diag[a];
+        }
+    }
+    body_invweight0[0][0] = body_invweight0[0][1] = 0.0;
+    for (int b = 1; b < M::NBODY; b++) {
+        int top = b;  // the nearest body, from b upwards, that has a dof
+        while (top > 0 && M::body_dofnum[top] == 0) top = M::body_parentid[top];
+        const double r[3] = {d.xipos[b][0] - d.com[0], d.xipos[b][1] - d.com[1], d.xipos[b][2] - d.com[2]};
+        double tr[2] = {0.0, 0.0};
+        for (int row = 0; row < 6; row++) {  // rows 0..2: translation of the centre of mass along x, y, z; 3..5: rotation
+            double J[NV];
+            for (int k = 0; k < NV; k++) J[k] = 0.0;
+            if (top > 0)
+                for (int i = M::body_dofadr[top] + M::body_dofnum[top] - 1; i >= 0; i = M::dof_parentid[i]) {
+                    double t[3];
+                    cross3(t, d.cdof[i], r);
+                    J[i] = row < 3 ? d.cdof[i][3 + row] + t[row] : d.cdof[i][row - 3];
+                }
+            for (int k = 0; k < NV; k++) x[k] = J[k];
+            chol_solve<NV>(d.qL, x);
+            double s = 0.0;
+            for (int k = 0; k < NV; k++) s += J[k] * x[k];
+            tr[row / 3] += s;
+        }
+        const double t = tr[0] / 3.0, w = tr[1] / 3.0;
+        body_invweight0[b][0] = t < kMinVal ? kMinVal : t, body_invweight0[b][1] = w < kMinVal ? kMinVal : w;
+    }
+    double s = 0.0;
+    for (int i = 0; i < NV; i++) s += d.qM[tri(i, i)];
+    meaninertia = s / NV;
 }
 
 }  // namespace mjx

@@ -190,13 +190,14 @@ struct MjEnv {
     // mass_center (humanoid_v5.py:17-21): einsum("b,bj->j", body_mass, xipos) / body_mass.sum()
     static MJX_DEV void mass_center_xy(const Data<M> &d, double *out) {
         double nx = 0, ny = 0, mass[NB];
-        for (int b = 0; b < NB; b++) nx += M::body_mass[b] * d.xipos[b][0], ny += M::body_mass[b] * d.xipos[b][1], mass[b] = M::body_mass[b];
+        for (int b = 0; b < NB; b++) nx += d.body_mass(b) * d.xipos[b][0], ny += d.body_mass(b) * d.xipos[b][1], mass[b] = d.body_mass(b);
         const double den = np_sum<double, NB>(mass);
         out[0] = nx / den, out[1] = ny / den;
     }
 
     // reset_model + set_state (-> mj_forward); writes the reset observation when obs != nullptr
-    static MJX_DEV void reset(mi::Pcg64 &rng, double *s, const mi::EnvParams &P, double *obs) {
+    // `lane`: as for step() below -- the Humanoids' reset observation (cinert) and tracked point (mass_center) read the lane's masses
+    static MJX_DEV void reset(mi::Pcg64 &rng, double *s, const mi::EnvParams &P, double *obs, const typename ModelView<M>::Fields *lane = nullptr) {
         if (KIND == kPusher) {
             // pusher_v5.py:293-315: the arm starts at init_qpos; the object's sliders (y first, then x: joint order of the XML) are re-drawn
             // until the object is farther than 0.17 from the goal; small arm velocities, object and goal at rest
@@ -258,6 +259,9 @@ struct MjEnv {
             // the observation shows cinert / cvel of the forward pass at the reset state, and the tracked point is the
             // whole-body centre of mass
             Data<M> d;
+            // only a view with the masses in it is bound: this reset reads none of the other four fields, and for LaneModel the view stays unbound, as it
+            // always was here (its callers pass no lane; a read of gravity, gear, damping or friction added to this branch must bind it first)
+            if constexpr (ModelView<M>::MASS_PER_LANE) d.bind(lane);
             for (int k = 0; k < NQ; k++) d.qpos[k] = s[k];
             for (int k = 0; k < NV; k++) d.qvel[k] = s[NQ + k];
             kinematics<M>(d);
@@ -297,8 +301,8 @@ struct MjEnv {
     }
 
     // One env.step() with the one-lane simulator (mjx_core.h): physics, then finish().
-    // `lane`: the sub-environment's own model fields when M is a LaneModel (mi_set_model_field); the view is all that differs -- reset() and finish()
-    // read none of the four fields (the reset observation's cinert / cvel do not depend on gravity)
+    // `lane`: the sub-environment's own model fields when M is a LaneModel (mi_set_model_field); the view is all that differs -- finish() reads none of
+    // the fields, reset() the body masses only (the reset observation's cinert / cvel do not depend on gravity)
     static MJX_DEV void step(double *s, const ActRow action, const mi::EnvParams &P, double *obs, double &reward, bool &terminated,
                              double *info, bool newton = false, const typename ModelView<M>::Fields *lane = nullptr) {
         Data<M> d;

@@ -348,6 +348,15 @@ def compile_model(desc, faithful_solver: bool = True) -> CompiledModel:
     m.pair_friction, m.pair_margin = np.array(P["friction"]).reshape(-1, 3), np.array(P["margin"])
     m.pair_solref, m.pair_solimp = np.array(P["solref"]).reshape(-1, 2), np.array(P["solimp"]).reshape(-1, 5)
 
+    derive_mass_constants(m)
+    return m
+
+
+def derive_mass_constants(m) -> None:
+    """``dof_invweight0``, ``body_invweight0``, ``meaninertia`` and ``total_mass`` of `m` from its masses and inertias: the diagonal of M^-1 at
+    qpos0 (averaged over the translational and over the rotational dofs of a free joint), the translational and rotational traces of
+    J M^-1 J^T at every body's centre of mass (floored at MINVAL), the mean diagonal of M, the sum of the body masses."""
+    nbody = m.nbody
     # ---- invweight0 at qpos0 --------------------------------------------------------------------------------------
     kin = kinematics(m, m.qpos0)
     M = mass_matrix(m, kin)
@@ -367,7 +376,22 @@ def compile_model(desc, faithful_solver: bool = True) -> CompiledModel:
         m.body_invweight0[bi] = [max(MINVAL, np.trace(A[:3, :3]) / 3), max(MINVAL, np.trace(A[3:, 3:]) / 3)]
     m.meaninertia = float(np.mean(np.diag(M)))
     m.total_mass = float(m.body_mass.sum())
-    return m
+
+
+def scaled(m, scale) -> CompiledModel:
+    """A deep copy of `m` whose body b has ``scale[b]`` times the mass and the inertia tensor: the same robot with links of another density.  The
+    centre of mass, the principal axes and the fluid box (sqrt(6 (Ii + Ij - Ik) / mass)) of a body do not move; ``dof_invweight0``,
+    ``body_invweight0``, ``meaninertia`` and ``total_mass`` are derived again.  What set_attr("body_mass_scale") holds per sub-environment."""
+    import copy
+
+    scale = np.asarray(scale, dtype=np.float64)
+    if scale.shape != (m.nbody,):
+        raise ValueError(f"scaled(): scale must have shape ({m.nbody},) = one factor per body (the world body included), got {scale.shape}")
+    out = copy.deepcopy(m)
+    out.body_mass = m.body_mass * scale
+    out.body_inertia = m.body_inertia * scale[:, None, None]
+    derive_mass_constants(out)
+    return out
 
 
 # ---- reference-style numpy kinematics (used for invweight0 and as a cross-check of the engine) -------------------

@@ -82,9 +82,16 @@ class _MujocoVectorEnv(HipVectorEnv):
     # sub-environment of a SyncVectorEnv.  An EXTENSION: the reference's scalar envs have no such attributes (there one writes to the mjModel).  Like
     # all MuJoCo physics here their parity with `mujoco` is UNPINNED; the CPU oracle, which takes the same fields as data, is the reference.  No
     # compiled-model quantity is derived from any of the four (tests/test_model_attrs_host.py), so the engine replaces them without recompiling.
+    # body_mass_scale (width nbody) multiplies the mass AND the inertia tensor of every body -- the same link at another density: centre of mass,
+    # principal axes and fluid box stay (compiler.scaled() is the same model as data).  It drags dof_invweight0, body_invweight0 and meaninertia
+    # with it; the engine derives those per sub-environment on the device and get_attr shows them under DERIVED_FIELDS, read-only.
     # (name, engine field id, minimum value or None): geom_friction is mixed into the engine's contact-pair rows on the host.
     MODEL_FIELDS = (("gravity", _native.MODEL_GRAVITY, None), ("actuator_gear", _native.MODEL_ACTUATOR_GEAR, None),
-                    ("dof_damping", _native.MODEL_DOF_DAMPING, 0.0), ("geom_friction", _native.MODEL_PAIR_FRICTION, 1e-5))  # 1e-5: MuJoCo's documented minimum
+                    ("dof_damping", _native.MODEL_DOF_DAMPING, 0.0), ("geom_friction", _native.MODEL_PAIR_FRICTION, 1e-5),  # 1e-5: MuJoCo's documented minimum
+                    # 1e-3: a stated floor -- Pusher's 4e-10 kg bodies stay above the simulator's 1e-15 mass test, M stays positive definite
+                    ("body_mass_scale", _native.MODEL_BODY_MASS_SCALE, 1e-3))
+    DERIVED_FIELDS = (("dof_invweight0", _native.MODEL_DERIVED_DOF_INVWEIGHT0), ("body_invweight0", _native.MODEL_DERIVED_BODY_INVWEIGHT0),
+                      ("meaninertia", _native.MODEL_DERIVED_MEANINERTIA))
     _COMPILED: dict = {}
 
     def _compiled_model(self):
@@ -102,15 +109,29 @@ class _MujocoVectorEnv(HipVectorEnv):
         for field, fid, lo in self.MODEL_FIELDS:
             if field == name:
                 m = self._compiled_model()
-                stock = {"gravity": m.gravity, "actuator_gear": m.actuator_gear, "dof_damping": m.dof_damping, "geom_friction": m.geom_friction[:, 0]}[name]
+                stock = {"gravity": m.gravity, "actuator_gear": m.actuator_gear, "dof_damping": m.dof_damping, "geom_friction": m.geom_friction[:, 0],
+                         "body_mass_scale": np.ones(m.nbody)}[name]
                 return fid, lo, np.array(stock, dtype=np.float64)
         raise UnknownEnvAttributeError(f"{type(self).__name__} has no per-sub-environment attribute {name!r}; the supported names are "
                                        f"{', '.join(f[0] for f in self.MODEL_FIELDS)} (model fields of the compiled robot: set_attr does not create new ones)")
 
+    def _derived(self, name: str):
+        """The constants derived from the body masses, per sub-environment: dof_invweight0 (nv,), body_invweight0 (nbody, 2), meaninertia ()."""
+        which = dict(self.DERIVED_FIELDS)[name]
+        m = self._compiled_model()
+        stock = np.asarray({"dof_invweight0": m.dof_invweight0, "body_invweight0": m.body_invweight0, "meaninertia": m.meaninertia}[name], dtype=np.float64)
+        if not (self._env_attr_mask >> _native.MODEL_BODY_MASS_SCALE) & 1 or not hasattr(self._engine.lib, "get_model_derived"):
+            return tuple(stock.copy() for _ in range(self.num_envs))
+        rows = self._engine.get_model_derived(which, stock.size)
+        return tuple(np.array(r, dtype=np.float64).reshape(stock.shape) for r in rows)
+
     def get_attr(self, name: str) -> tuple:
-        """The model field of every sub-environment: a tuple of num_envs float64 arrays; before any set_attr the compiled model's values."""
+        """The model field of every sub-environment: a tuple of num_envs float64 arrays; before any set_attr the compiled model's values.
+        "dof_invweight0", "body_invweight0" and "meaninertia" are read-only: what the engine derived from the sub-environment's body_mass_scale."""
         self._check_open()
         self._check_not_pending("get_attr")
+        if name in dict(self.DERIVED_FIELDS):
+            return self._derived(name)
         fid, _, stock = self._model_field(name)
         if not (self._env_attr_mask >> fid) & 1:
             return tuple(stock.copy() for _ in range(self.num_envs))
@@ -125,12 +146,17 @@ class _MujocoVectorEnv(HipVectorEnv):
         """Set a model field of the sub-environments, by SyncVectorEnv.set_attr's rule: a list or tuple gives one array per sub-environment,
         anything else that is not a tensor the same array for all; a float64 tensor of shape (num_envs, width) on the env's device is taken without
         a host round trip.  Widths: gravity 3, actuator_gear nu, dof_damping nv, geom_friction ngeom (the sliding coefficient; a contact pair
-        takes the larger of its two geoms' values, as the model compiler mixes them).  Takes effect from the next step(); reset() does not undo
+        takes the larger of its two geoms' values, as the model compiler mixes them), body_mass_scale nbody (>= 1e-3; body b gets that many times
+        its compiled mass and inertia tensor, the world body's column has no effect; the engine then derives dof_invweight0, body_invweight0 and
+        meaninertia of every sub-environment on the device -- get_attr shows them, set_attr on them raises AttributeError; while a scale is held the
+        env runs kernels of their own, None takes it back).  Takes effect from the next step(); reset() does not undo
         it.  The first call moves the env to the one-lane simulator for good (slower than the cooperative kernel for the large robots:
         docs/results_log.md) and loads those kernels, so capture_steps() may follow it without an eager step in between; a graph captured BEFORE it
         refuses to replay.  None restores the compiled model's values."""
         self._check_open()
         self._check_not_pending("set_attr")
+        if name in dict(self.DERIVED_FIELDS):
+            raise AttributeError(f"{name} is derived from body_mass_scale by the engine and is read-only; set_attr('body_mass_scale', ...) changes it")
         fid, lo, stock = self._model_field(name)
         N, W = self.num_envs, stock.shape[0]
         dev = None
@@ -182,7 +208,11 @@ class _MujocoVectorEnv(HipVectorEnv):
                 send = t.maximum(dev[:, g1], dev[:, g2]).reshape(N, len(m.pair_geom1))
         else:
             send = what
-        if dev is None:
+        if values is None and name == "body_mass_scale":
+            if not (self._env_attr_mask >> fid) & 1:
+                return  # no scale is held: nothing to restore, and the engine is not moved to the per-lane kernels for it
+            self._engine.set_model_field(fid, None)  # the engine's own restore: the compiled-in constants copied back, nothing derived
+        elif dev is None:
             self._engine.set_model_field(fid, np.ascontiguousarray(send))
         else:
             d = send.contiguous()
@@ -195,6 +225,8 @@ class _MujocoVectorEnv(HipVectorEnv):
         if name == "geom_friction":
             self._model_geom_friction = rows.copy() if dev is None else dev.clone()
         self._env_attr_mask = self._env_attr_mask | (1 << fid)
+        if values is None and name == "body_mass_scale":  # no scale is held any more: the engine is back on the kernels without the mass rows
+            self._env_attr_mask = self._env_attr_mask & ~(1 << fid)
 
     def _torch_module(self):
         return self._torch if "_torch" in self.__dict__ else __import__("torch")

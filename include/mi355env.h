@@ -443,22 +443,39 @@ int mi_get_env_attr(mi_vecenv *env, int attr, double *host_out);
  * maximum of the two geoms' geom_friction[:, 0]) in every sub-environment of a SyncVectorEnv.  An extension: the reference's scalar envs have no
  * such attributes.  Like all MuJoCo physics here the parity with `mujoco` is UNPINNED (no `mujoco` build to take fixtures from); the CPU oracle,
  * which takes the same fields as data, is the reference for these fields.  No compiled-model quantity is derived from any of them.
- * mi_model_field_width: 3 / nu / nv / number of contact pairs (0 for a robot without any); < 0: not a MuJoCo kind, or no such field.
+ * mi_model_field_width: 3 / nu / nv / number of contact pairs (0 for a robot without any) / nbody; < 0: not a MuJoCo kind, or no such field.
  * mi_set_model_field: `values` = [num_envs][width] row-major float64, host (on_device = 0: checked and staged before the call returns) or device
  * memory (on_device = 1: transposed into the env's rows by a small kernel on the env's stream; the caller has checked the values); NULL restores
  * the compiled-in values.  Takes effect from the next mi_step / mi_rollout; resets do not undo it and mi_get_state does not include it.  The
- * first call allocates the rows of all four fields at the compiled-in values and moves the env to the one-lane simulator for good (a robot whose
+ * first call allocates the rows of all fields at the compiled-in values and moves the env to the one-lane simulator for good (a robot whose
  * default is the cooperative kernel gets slower: docs/results_log.md; MI355ENV_MJ_COOP=1 does not bring it back); the values live in device
  * memory updated in place, so mi_step stays capturable and a HIP graph captured after the switch sees later calls.  That first call also loads
  * the per-lane kernels' code object (kernels otherwise load on first use, which a stream capture must not trigger): a capture may follow it at once.
  * Refused: a kind that is not a MuJoCo one (MI_ERR_UNSUPPORTED); a non-finite value, a negative damping, a friction below 1e-5 -- MuJoCo's
  * documented minimum (MI_ERR_INVALID_ARGUMENT).
  * mi_get_model_field: the current values into `host_out` ([num_envs][width] float64); synchronises.
+ *
+ * MI_MODEL_BODY_MASS_SCALE (added to ABI 10 as well; width nbody, the world body's column is accepted and has no effect): body b of a
+ * sub-environment has `scale` times the compiled mass AND inertia tensor -- the same link at another density, so its centre of mass, principal
+ * axes and fluid box stay.  Values must be finite and >= 1e-3 (a stated floor: the lightest compiled bodies stay above the simulator's 1e-15 mass
+ * test and M stays positive definite).  Unlike the other four fields this one drags compiled constants with it: dof_invweight0, body_invweight0
+ * and meaninertia (from M(qpos0) and its inverse).  The call derives them for every sub-environment on the device, one lane each, with the
+ * mass-matrix code of the step kernels (mj_model_constants_kernel, on the env's stream, no host work per sub-environment); every use site of the
+ * one-lane simulator reads the lane's values.  While a scale is held the env runs kernels of their own (mjx::MassLaneModel: the mass rows stay out of
+ * the kernels of the other four fields, which they would slow down).  NULL restores the scale 1 and the compiled-in constants, copied, not derived, and
+ * takes the env back to the kernels without the mass rows: an env that never sets this field runs on exactly what it ran before the field existed.
+ * Because the first call with values and the call with NULL change which kernels mi_step launches, a HIP graph captured before either of them must be
+ * captured again (it would go on launching the other kernels, which ignore, or keep, the scale); between the two, later calls with values are seen by a
+ * captured graph like those of the other fields.
+ * mi_get_model_derived: the derived constants of every sub-environment into `host_out` -- [num_envs][nv], [num_envs][nbody][2] or [num_envs][1]
+ * float64; the compiled model's values until a scale is set; synchronises.
  */
-enum { MI_MODEL_GRAVITY = 0, MI_MODEL_ACTUATOR_GEAR = 1, MI_MODEL_DOF_DAMPING = 2, MI_MODEL_PAIR_FRICTION = 3, MI_MODEL_FIELD_COUNT = 4 };
+enum { MI_MODEL_GRAVITY = 0, MI_MODEL_ACTUATOR_GEAR = 1, MI_MODEL_DOF_DAMPING = 2, MI_MODEL_PAIR_FRICTION = 3, MI_MODEL_BODY_MASS_SCALE = 4, MI_MODEL_FIELD_COUNT = 5 };
+enum { MI_MODEL_DERIVED_DOF_INVWEIGHT0 = 0, MI_MODEL_DERIVED_BODY_INVWEIGHT0 = 1, MI_MODEL_DERIVED_MEANINERTIA = 2, MI_MODEL_DERIVED_COUNT = 3 };
 int mi_model_field_width(mi_vecenv *env, int field);
 int mi_set_model_field(mi_vecenv *env, int field, const double *values, int on_device);
 int mi_get_model_field(mi_vecenv *env, int field, double *host_out);
+int mi_get_model_derived(mi_vecenv *env, int which, double *host_out);
 
 /*
  * The per-sub-environment action wrappers (added to ABI 10, which it leaves as it is): gymnasium.wrappers.RepeatAction and StickyAction
