@@ -1,4 +1,4 @@
-// engine_types.h -- what the engine's units (engine.hip, compiled as engine.o and through classic.hip as classic.o, and mjx_model.hip) agree on: the
+// engine_types.h -- what the engine's units (engine.hip, classic.hip, mjx_model.hip and mjx_mass_model.hip) agree on: the
 // constants of the lane's flag word, the plain structs that ride in kernel arguments and in mi_vecenv, the handle itself, the launch functions one
 // unit defines and another calls, and the error helpers of the host side.  No kernel and no device function lives here.
 #ifndef MI355ENV_ENGINE_TYPES_H
@@ -150,7 +150,7 @@ struct SharedRng {
     double low, high;      // self.low / self.high (cartpole.py:489-491): the bounds of the last reset() serve the autoresets
 };
 }  // namespace mi_internal
-// The classic-control kernels behind plain launch functions (defined in the MI_CLASSIC_TU unit of engine.hip, called from the other): what mi_step / mi_reset /
+// The classic-control kernels behind plain launch functions (defined in classic.hip, called from engine.hip): what mi_step / mi_reset /
 // mi_rollout do for the kinds CARTPOLE ... MOUNTAIN_CAR_CONTINUOUS once the arguments are validated and the buffers chosen.
 namespace mi_classic {
 int step(mi_vecenv *v, const mi_internal::StepPtrs &p, int act_kind);                                           // launch_step<E> of the env's kind

@@ -1,4 +1,4 @@
-// lane_common.h -- the device helpers every family's kernels use (the classic-control, ToyText and utility kernels of engine.hip, and
+// lane_common.h -- the device helpers every family's kernels use (classic_kernels.h, tabular_kernels.h, the utility kernels of engine.hip and
 // mj_glue_kernels.h): the lane's statistics and their per-workgroup totals, the sub-environment's generator in memory, the output function of a PCG64 state.
 #ifndef MI355ENV_LANE_COMMON_H
 #define MI355ENV_LANE_COMMON_H

@@ -1,5 +1,5 @@
-// wrappers_internal.h -- what wrappers.hip (the stand-alone wrapper passes) and engine.hip (the same wrappers as the output stage of the step
-// kernel) share: the statistics handle and RunningMeanStd's update in the dtype NumPy computes it in.
+// wrappers_internal.h -- what wrappers.hip (the stand-alone wrapper passes) and the step epilogue (the same wrappers as the output stage of the step
+// kernel: classic_kernels.h, bound to an env by engine.hip) share: the statistics handle and RunningMeanStd's update in the dtype NumPy computes it in.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

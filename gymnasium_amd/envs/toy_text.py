@@ -339,7 +339,7 @@ class TaxiVectorEnv(TabularVectorEnv):
         self._action_mask = np.stack([self.action_mask(s) for s in range(self.nS)])
 
     def _engine_params(self):
-        # params[2] != 0: the fickle-passenger rule of taxi.py:436-451 / :462-464 runs in the kernel (tab_fickle, engine.hip), params[3] = its probability
+        # params[2] != 0: the fickle-passenger rule of taxi.py:436-451 / :462-464 runs in the kernel (tab_fickle, tabular_kernels.h), params[3] = its probability
         return (float(self.nS), float(self.nA), 1.0 if self.fickle_passenger else 0.0, float(self.fickle_probability))
 
     @staticmethod

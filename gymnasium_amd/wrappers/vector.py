@@ -11,7 +11,7 @@ but the arithmetic runs in libmi355env.so on the GPU (the wrappers have no CPU i
 oracle/wrappers.py is test infrastructure), in one of two forms:
 
 * FUSED (classic-control HipVectorEnv directly underneath, possibly through RecordEpisodeStatistics / NumpyToTorch): the wrapper registers
-  itself with the env and its arithmetic becomes the output stage of the step kernel (mi_set_step_epilogue, csrc/engine.hip): the batch
+  itself with the env and its arithmetic becomes the output stage of the step kernel (mi_set_step_epilogue, csrc/classic_kernels.h): the batch
   statistics are gathered by the step kernel's workgroups, one small second launch normalises in place -- NumPy callers get the wrapped
   batch with the step's one device-to-host copy.  The fusion is SCOPED to the call: a ``step()`` entered through fused wrapper k runs the
   arithmetic of the fused wrappers up to k; stepping the env itself (``w.env.step``, ``w.unwrapped.step``) or an inner wrapper returns that

@@ -22,18 +22,26 @@ def test_closure_of_engine():
                  os.path.join("..", "..", "include", "mi355env.h")):
         assert name in deps, name
     assert not any(f.endswith(".hip") for f in deps)
+    assert "tabular_kernels.h" in deps and "classic_kernels.h" not in deps and "lane_step.h" not in deps
 
 
 def test_closure_of_classic():
-    """(classic.hip still reaches its kernels through engine.hip: which headers it must NOT depend on is pinned when it has become a unit of its own)"""
     deps = closure("classic.hip")
     assert "sincos_table.h" in deps and "envs_classic.h" in deps
+    assert "classic_kernels.h" in deps and "lane_step.h" in deps
+    assert not any(os.path.basename(f).startswith("mjx_") for f in deps), deps
+    assert "mj_glue_kernels.h" not in deps and "tabular_kernels.h" not in deps and not any(f.endswith(".hip") for f in deps)
 
 
 def test_closure_of_mjx_model():
     deps = closure("mjx_model.hip")
     assert "mj_glue_kernels.h" in deps and "engine_types.h" in deps and os.path.join("generated", "mjx_models.h") in deps
     assert "wrappers_internal.h" not in deps and "mjx_physics.h" not in deps and not any(f.endswith(".hip") for f in deps)
+
+
+@pytest.mark.parametrize("unit", B.SOURCES)
+def test_no_unit_includes_a_unit(unit):
+    assert not any(f.endswith(".hip") for f in closure(unit))
 
 
 @pytest.fixture(scope="module")
@@ -66,6 +74,7 @@ def stale_units(here):
 
 
 @pytest.mark.parametrize("header", ["mj_glue_kernels.h", "lane_common.h", "wrappers_internal.h", "pcg64_dev.h", "action_mask_internal.h",
+                                    "classic_kernels.h", "lane_step.h", "tabular_kernels.h",
                                     os.path.join("generated", "mjx_models.h"), os.path.join("..", "..", "include", "mi355env.h")])
 def test_touching_a_header_makes_its_includers_stale(copied_tree, header):
     os.utime(os.path.join(copied_tree, header), (1_000_200, 1_000_200))
@@ -78,6 +87,10 @@ def test_touching_a_header_makes_its_includers_stale(copied_tree, header):
         assert {"wrappers.hip"} <= expected and "mjx_model.hip" not in expected
     if header == "action_mask_internal.h":
         assert {"engine.hip", "action_mask.hip"} <= expected
+    if header in ("classic_kernels.h", "lane_step.h"):
+        assert "classic.hip" in expected and "engine.hip" not in expected
+    if header == "tabular_kernels.h":
+        assert "engine.hip" in expected and "classic.hip" not in expected
 
 
 def test_touching_a_unit_or_the_build_script(copied_tree):

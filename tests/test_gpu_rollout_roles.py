@@ -1,4 +1,4 @@
-"""-m gpu: the two-role rollout kernel (rollout_duo_kernel: an "env" and an "aux" wavefront per 64 sub-environments, engine.hip) against the one-role
+"""-m gpu: the two-role rollout kernel (rollout_duo_kernel: an "env" and an "aux" wavefront per 64 sub-environments, classic_kernels.h) against the one-role
 kernel it replaces for the collector's configuration (NEXT_STEP, on-device policy, every output) -- and both against step().
 
 The two kernels run the same arithmetic on different lanes, so everything must be bit-identical: the trajectory, the state and generators left

@@ -1,4 +1,4 @@
-"""The branch-free rollout of a plain transition table (engine.hip tab_rollout_lean_kernel: FrozenLake, CliffWalking, Taxi; NEXT_STEP, on-device policy)
+"""The branch-free rollout of a plain transition table (tabular_kernels.h tab_rollout_lean_kernel: FrozenLake, CliffWalking, Taxi; NEXT_STEP, on-device policy)
 against the CPU oracle stepped with the actions the rollout drew: every observation, reward and flag, then the state rows (state index and the
 ``prob`` of the last transition), the generators, the episode statistics -- and that stepping on from the rollout's final state continues in lockstep.
 

@@ -50,7 +50,7 @@ def test_step_kernel_on_rare_lanes(n):
 
 @pytest.fixture(params=[1, 0], ids=["two_roles", "one_role"])
 def rollout_kernel(request, monkeypatch):
-    """Both kernels behind rollout(): rollout_duo_kernel (the default for this configuration) and the one-role rollout_kernel it replaced (engine.hip)."""
+    """Both kernels behind rollout(): rollout_duo_kernel (the default for this configuration) and the one-role rollout_kernel it replaced (classic_kernels.h)."""
     monkeypatch.setenv("MI355ENV_ROLLOUT_DUO", str(request.param))
     return request.param
 
