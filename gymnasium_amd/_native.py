@@ -51,6 +51,9 @@ HOST_SYMBOLS += ["action_sample_masked", "action_sample_weighted", "action_get_b
 # RepeatAction / StickyAction of the sub-environments inside the step (mi_set_step_wrappers; added to ABI 10, which it leaves as it is): product library
 # only -- HipVectorEnv.set_step_wrappers tells the backends apart by whether the entry point is bound.
 HOST_SYMBOLS += ["set_step_wrappers"]
+# MaxAndSkipObservation of the sub-environments inside the step (mi_set_max_and_skip, mi_get_max_and_skip_frames; added to ABI 10 as well): product
+# library only -- HipVectorEnv.set_max_and_skip tells the backends apart by whether the entry point is bound.
+HOST_SYMBOLS += ["set_max_and_skip", "get_max_and_skip_frames"]
 # Per-sub-environment model fields of the MuJoCo kinds (mi_set_model_field; added to ABI 10, which it leaves as it is): product library only -- the oracle
 # takes a model as data for ALL its envs (orc_mj_register_model), and HipVectorEnv.set_attr tells the backends apart by whether the entry point is bound.
 HOST_SYMBOLS += ["model_field_width", "set_model_field", "get_model_field"]
@@ -231,6 +234,11 @@ class NativeLib:
             try:
                 self.set_step_wrappers = f("set_step_wrappers", [vp, i32, dbl, i32], i32)
             except ImportError:  # an ABI 10 build from before the entry point (MI355ENV_LIBRARY, A/B runs): HipVectorEnv.set_step_wrappers refuses
+                pass
+            try:
+                self.set_max_and_skip = f("set_max_and_skip", [vp, i32], i32)
+                self.get_max_and_skip_frames = f("get_max_and_skip_frames", [vp, vp, i32], i32)
+            except ImportError:  # (likewise: HipVectorEnv.set_max_and_skip refuses)
                 pass
             try:
                 self.model_field_width = f("model_field_width", [vp, i32], i32)
@@ -564,6 +572,16 @@ class Engine:
         """mi_set_step_wrappers: RepeatAction(num_repeats) / StickyAction(sticky_probability, sticky_duration) around every sub-environment; 0 = no
         such wrapper."""
         self.lib.check(self.lib.set_step_wrappers(self.handle, int(num_repeats), float(sticky_probability), int(sticky_duration)))
+
+    def set_max_and_skip(self, skip: int):
+        """mi_set_max_and_skip: MaxAndSkipObservation(skip) around every sub-environment, its frames zeroed; 0 = no such wrapper."""
+        self.lib.check(self.lib.set_max_and_skip(self.handle, int(skip)))
+
+    def get_max_and_skip_frames(self, obs_dim: int) -> np.ndarray:
+        """mi_get_max_and_skip_frames: the sub-environments' frame buffers, float32 [2, num_envs, obs_dim]."""
+        out = np.empty((2, self.num_envs, int(obs_dim)), dtype=np.float32)
+        self.lib.check(self.lib.get_max_and_skip_frames(self.handle, _ptr(out), 0))
+        return out
 
     def get_rng(self) -> np.ndarray:
         words = np.empty((self.num_envs, 4), dtype=np.uint64)

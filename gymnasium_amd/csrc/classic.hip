@@ -100,15 +100,31 @@ void launch_step_mode(mi_vecenv *v, const StepPtrs &p) {
     default: hipLaunchKernelGGL((step_kernel<E, MI_AUTORESET_DISABLED, EPI, SAMPLE>), g, b, 0, v->stream, v->d, p, v->epi, at); break;
     }
 }
-template <class E, bool SAMPLE>
+// the wrapped kernels' last argument; MAXSKIP (mi_set_max_and_skip): RepeatAction is off (the two refuse each other) and its loop runs `skip` trips
+template <bool MAXSKIP>
+WrapArg<MAXSKIP> wrap_arg(const mi_vecenv *v) {
+    WrapArg<MAXSKIP> w = v->wrap;
+    if constexpr (MAXSKIP) w.repeats = w.skip;
+    return w;
+}
+template <class E, bool SAMPLE, bool MAXSKIP = false>
 void launch_step_wrapped_mode(mi_vecenv *v, const StepPtrs &p) {
     const dim3 g(v->grid), b(kBlock);
     const AttrDev at = {v->d_attr, v->attr_mask};
+    const WrapArg<MAXSKIP> w = wrap_arg<MAXSKIP>(v);
     switch (v->cfg.autoreset_mode) {
-    case MI_AUTORESET_NEXT_STEP: hipLaunchKernelGGL((step_wrapped_kernel<E, MI_AUTORESET_NEXT_STEP, SAMPLE>), g, b, 0, v->stream, v->d, p, at, v->wrap); break;
-    case MI_AUTORESET_SAME_STEP: hipLaunchKernelGGL((step_wrapped_kernel<E, MI_AUTORESET_SAME_STEP, SAMPLE>), g, b, 0, v->stream, v->d, p, at, v->wrap); break;
-    default: hipLaunchKernelGGL((step_wrapped_kernel<E, MI_AUTORESET_DISABLED, SAMPLE>), g, b, 0, v->stream, v->d, p, at, v->wrap); break;
+    case MI_AUTORESET_NEXT_STEP: hipLaunchKernelGGL((step_wrapped_kernel<E, MI_AUTORESET_NEXT_STEP, SAMPLE, MAXSKIP>), g, b, 0, v->stream, v->d, p, at, w); break;
+    case MI_AUTORESET_SAME_STEP: hipLaunchKernelGGL((step_wrapped_kernel<E, MI_AUTORESET_SAME_STEP, SAMPLE, MAXSKIP>), g, b, 0, v->stream, v->d, p, at, w); break;
+    default: hipLaunchKernelGGL((step_wrapped_kernel<E, MI_AUTORESET_DISABLED, SAMPLE, MAXSKIP>), g, b, 0, v->stream, v->d, p, at, w); break;
     }
+}
+// (mi_set_max_and_skip: the MAXSKIP instantiations, chosen on the host)
+template <class E, bool SAMPLE>
+void launch_step_wrapped_form(mi_vecenv *v, const StepPtrs &p) {
+    if (v->wrap.skip)
+        launch_step_wrapped_mode<E, SAMPLE, true>(v, p);
+    else
+        launch_step_wrapped_mode<E, SAMPLE>(v, p);
 }
 template <class E>
 int launch_step(mi_vecenv *v, const StepPtrs &p) {
@@ -117,11 +133,11 @@ int launch_step(mi_vecenv *v, const StepPtrs &p) {
             return fail(MI_ERR_STATE, "mi_set_step_wrappers: the wrapped kernels exist for the per-lane types");
         } else if constexpr (E::ACT_KIND == MI_F32 || E::ACT_KIND == MI_I64) {
             if (p.act_lane)
-                launch_step_wrapped_mode<E, true>(v, p);
+                launch_step_wrapped_form<E, true>(v, p);
             else
-                launch_step_wrapped_mode<E, false>(v, p);
+                launch_step_wrapped_form<E, false>(v, p);
         } else {
-            launch_step_wrapped_mode<E, false>(v, p);
+            launch_step_wrapped_form<E, false>(v, p);
         }
     } else if (!v->has_epi) {
         // the on-device policy draws the space's own dtype (float32 rows / int64): the float64-row instantiations never sample (the caller, step_enqueue,
@@ -149,26 +165,33 @@ int launch_step(mi_vecenv *v, const StepPtrs &p) {
     return MI_OK;
 }
 
-// mi_rollout / mi_rollout_infos with mi_set_step_wrappers on: one kernel stores whatever is asked for
-template <class E>
-int launch_rollout_wrapped(mi_vecenv *v, const RolloutPtrs &p, const RolloutExtra &ex, const ActionStream &as, int T, bool sample) {
+// mi_rollout / mi_rollout_infos with mi_set_step_wrappers (MAXSKIP: mi_set_max_and_skip) on: one kernel stores whatever is asked for
+template <class E, bool MAXSKIP>
+int launch_rollout_wrapped_form(mi_vecenv *v, const RolloutPtrs &p, const RolloutExtra &ex, const ActionStream &as, int T, bool sample) {
     const bool next_step = v->cfg.autoreset_mode == MI_AUTORESET_NEXT_STEP;
     const AttrDev at = {v->d_attr, v->attr_mask};
     const dim3 g(v->grid), b(kBlock);
+    const WrapArg<MAXSKIP> w = wrap_arg<MAXSKIP>(v);
     constexpr bool F64 = E::ACT_KIND == MI_F64 || E::ACT_KIND == MI_F64_WEAK;  // float64 action rows are always the caller's (the sampler draws float32)
     if (F64 && sample) return fail(MI_ERR_INVALID_ARGUMENT, "the on-device policy samples float32 actions");
     if constexpr (!HasAttrs<E>::value) {  // (the env is on the per-lane types once the wrappers were on: the others have no such kernels)
         return fail(MI_ERR_STATE, "mi_set_step_wrappers: the wrapped kernels exist for the per-lane types");
     } else {
     if constexpr (!F64) {
-        if (sample && next_step) hipLaunchKernelGGL((rollout_wrapped_kernel<E, MI_AUTORESET_NEXT_STEP, true>), g, b, 0, v->stream, v->d, p, as, T, at, ex, v->wrap);
-        if (sample && !next_step) hipLaunchKernelGGL((rollout_wrapped_kernel<E, MI_AUTORESET_SAME_STEP, true>), g, b, 0, v->stream, v->d, p, as, T, at, ex, v->wrap);
+        if (sample && next_step) hipLaunchKernelGGL((rollout_wrapped_kernel<E, MI_AUTORESET_NEXT_STEP, true, MAXSKIP>), g, b, 0, v->stream, v->d, p, as, T, at, ex, w);
+        if (sample && !next_step) hipLaunchKernelGGL((rollout_wrapped_kernel<E, MI_AUTORESET_SAME_STEP, true, MAXSKIP>), g, b, 0, v->stream, v->d, p, as, T, at, ex, w);
     }
-    if (!sample && next_step) hipLaunchKernelGGL((rollout_wrapped_kernel<E, MI_AUTORESET_NEXT_STEP, false>), g, b, 0, v->stream, v->d, p, as, T, at, ex, v->wrap);
-    if (!sample && !next_step) hipLaunchKernelGGL((rollout_wrapped_kernel<E, MI_AUTORESET_SAME_STEP, false>), g, b, 0, v->stream, v->d, p, as, T, at, ex, v->wrap);
+    if (!sample && next_step) hipLaunchKernelGGL((rollout_wrapped_kernel<E, MI_AUTORESET_NEXT_STEP, false, MAXSKIP>), g, b, 0, v->stream, v->d, p, as, T, at, ex, w);
+    if (!sample && !next_step) hipLaunchKernelGGL((rollout_wrapped_kernel<E, MI_AUTORESET_SAME_STEP, false, MAXSKIP>), g, b, 0, v->stream, v->d, p, as, T, at, ex, w);
     HIP_TRY(hipGetLastError());
     return MI_OK;
     }
+}
+
+template <class E>
+int launch_rollout_wrapped(mi_vecenv *v, const RolloutPtrs &p, const RolloutExtra &ex, const ActionStream &as, int T, bool sample) {
+    if (v->wrap.skip) return launch_rollout_wrapped_form<E, true>(v, p, ex, as, T, sample);
+    return launch_rollout_wrapped_form<E, false>(v, p, ex, as, T, sample);
 }
 
 template <class E, int MODE, bool SAMPLE, bool FULL>

@@ -247,15 +247,19 @@ __global__ __launch_bounds__(kBlock) void step_kernel(DevEnv d, StepPtrs io, Epi
 
 // mi_set_step_wrappers: step_kernel (without an epilogue) with RepeatAction / StickyAction around E::step -- lane_step_wrapped in place of lane_step, and
 // StickyAction's two words per lane requested and stored with the rest of the lane.  The generator is always loaded: the sticky draw needs it.
-template <class E, int MODE, bool SAMPLE>
-__global__ __launch_bounds__(kBlock) void step_wrapped_kernel(DevEnv d, StepPtrs io, AttrDev at, WrapDev w) {
+// MAXSKIP (mi_set_max_and_skip): the lane's two frames are requested with them, before the barrier, and go back when the step wrote a slot.
+template <class E, int MODE, bool SAMPLE, bool MAXSKIP = false>
+__global__ __launch_bounds__(kBlock) void step_wrapped_kernel(DevEnv d, StepPtrs io, AttrDev at, WrapArg<MAXSKIP> w) {
     const int i = blockIdx.x * kBlock + threadIdx.x;
     LaneStats st = {0u, 0u, 0u, 0ull, 0.0};
     StepOut<E> o;
     LaneRequest<E> rq;
     AttrRequest<E> ar;
-    WrapLane<E> sl;
+    WrapLaneOf<E, MAXSKIP> sl;
     if (i < d.N) rq.template request<SAMPLE>(d, io.actions, io.act_lane, i, true), ar.request(at, d, i), load_wrap_lane(w, i, sl);
+    if constexpr (MAXSKIP) {
+        if (i < d.N) load_skip_lane(w, d, i, sl);
+    }
     BlockTotals before = block_totals_load(d);
     tables_init<E>();
     hold_opaque(before.count), hold_opaque(before.ret);
@@ -272,9 +276,11 @@ __global__ __launch_bounds__(kBlock) void step_wrapped_kernel(DevEnv d, StepPtrs
             io.act_lane[i] = (uint64_t)(next >> 64), io.act_lane[(size_t)d.N + i] = (uint64_t)next;
             if (io.actions_out) static_cast<typename E::Act *>(io.actions_out)[i] = a;  // the policy's action, not the effective one
         }
-        lane_step_wrapped<E, MODE>(d, w, sl, i, L, a, o, st, nullptr, &gen);
+        if constexpr (MAXSKIP) arrive_skip_lane(sl);
+        lane_step_wrapped<E, MODE, MAXSKIP>(d, w, sl, i, L, a, o, st, nullptr, &gen);
         store_lane<E>(d, i, L);
         store_wrap_lane(w, i, sl);
+        if constexpr (MAXSKIP) store_skip_lane(w, d, i, sl);
         if (io.obs) store_row<E::OBS>(io.obs + (size_t)i * E::OBS, o.obs);
         if (io.reward) io.reward[i] = o.reward;
         if (io.terminated) io.terminated[i] = o.terminated;
@@ -466,8 +472,9 @@ __global__ __launch_bounds__(kBlock) void rollout_infos_kernel(DevEnv d, Rollout
 // mi_set_step_wrappers: the loop of rollout_infos_kernel with lane_step_wrapped as its step, for mi_rollout (ex: all null) and mi_rollout_infos alike.
 // The generator and StickyAction's state stay in registers for the launch; nothing is drawn ahead (lane_step_wrapped), so the generator that goes back
 // to memory is at the reference's position.  actions_out are the policy's actions, not the effective ones.
-template <class E, int MODE, bool SAMPLE>
-__global__ __launch_bounds__(kBlock) void rollout_wrapped_kernel(DevEnv d, RolloutPtrs io, ActionStream as, int T, AttrDev at, RolloutExtra ex, WrapDev w) {
+// MAXSKIP (mi_set_max_and_skip): the lane's two frames are loaded once, live in registers across the T steps and are stored once.
+template <class E, int MODE, bool SAMPLE, bool MAXSKIP = false>
+__global__ __launch_bounds__(kBlock) void rollout_wrapped_kernel(DevEnv d, RolloutPtrs io, ActionStream as, int T, AttrDev at, RolloutExtra ex, WrapArg<MAXSKIP> w) {
     tables_init<E>();
     const int i = blockIdx.x * kBlock + threadIdx.x;
     LaneStats st = {0u, 0u, 0u, 0ull, 0.0};
@@ -494,8 +501,9 @@ __global__ __launch_bounds__(kBlock) void rollout_wrapped_kernel(DevEnv d, Rollo
         ResetQueue<E> q;
         q.have = 0u;
         q.rng = load_rng(d, i);
-        WrapLane<E> sl;
+        WrapLaneOf<E, MAXSKIP> sl;
         load_wrap_lane(w, i, sl);
+        if constexpr (MAXSKIP) load_skip_lane(w, d, i, sl);
         for (int t = 0; t < T; t++) {
             typename E::Act a;
             if (SAMPLE) {
@@ -510,7 +518,8 @@ __global__ __launch_bounds__(kBlock) void rollout_wrapped_kernel(DevEnv d, Rollo
 #pragma unroll
                 for (int k = 0; k < E::OBS; k++) o.final_obs[k] = 0.0f;
             }
-            lane_step_wrapped<E, MODE>(d, w, sl, i, L, a, o, st, &q, nullptr);
+            if constexpr (MAXSKIP) q.have = 0u;  // (nothing is drawn ahead here: said aloud, the queue's draws need no registers across the loop)
+            lane_step_wrapped<E, MODE, MAXSKIP>(d, w, sl, i, L, a, o, st, &q, nullptr);
             if (io.obs) store_row<E::OBS>(static_cast<float *>(io.obs) + (t * N + i) * E::OBS, o.obs);
             if (io.reward) io.reward[t * N + i] = o.reward;
             if (io.terminated) io.terminated[t * N + i] = o.terminated;
@@ -519,14 +528,29 @@ __global__ __launch_bounds__(kBlock) void rollout_wrapped_kernel(DevEnv d, Rollo
             if (ex.ep_len) ex.ep_len[t * N + i] = o.ep_len;
             if (MODE == MI_AUTORESET_SAME_STEP && ex.final_obs) store_row<E::OBS>(static_cast<float *>(ex.final_obs) + (t * N + i) * E::OBS, o.final_obs);
         }
-        store_lane<E>(d, i, L);
-        store_wrap_lane(w, i, sl);
-        if (q.have) {  // (a reset's refill is consumed by that reset: never taken, kept for the invariant)
+        if constexpr (MAXSKIP) {
+            // the addresses of the launch's last stores from an opaque copy of i: the compiler otherwise keeps the 64-bit addresses of the loads at the
+            // head of the kernel live through the loop (rollout_infos_kernel does the same for the action stream's rows).  With them Pendulum's sampled
+            // rollout took 258 - 262 VGPRs -- past the 256 architectural ones values go to AGPRs, which the inline-asm Horner steps of ExactMath must
+            // not sit next to (sincos_exact.h fma_k, tests/test_kernel_resources.py) --; without, 235 - 238.
+            int wi = i;
+            hold_opaque(wi);
+            store_lane<E>(d, wi, L);
+            store_wrap_lane(w, wi, sl);
+            sl.written = 1u;  // (stored whether or not a slot was written: the rows it read, at worst)
+            store_skip_lane(w, d, wi, sl);
+            store_rng_state(d, wi, q.rng);  // (the queue is empty: nothing to hand back)
+            if (SAMPLE && as.lane) as.lane[wi] = (uint64_t)(astate >> 64), as.lane[N + wi] = (uint64_t)astate;
+        } else {
+            store_lane<E>(d, i, L);
+            store_wrap_lane(w, i, sl);
+            if (q.have) {  // (a reset's refill is consumed by that reset: never taken, kept for the invariant)
 #pragma unroll
-            for (int k = 0; k < E::NDRAWS; k++) q.rng.unstep();
+                for (int k = 0; k < E::NDRAWS; k++) q.rng.unstep();
+            }
+            store_rng_state(d, i, q.rng);
+            if (SAMPLE && as.lane) as.lane[i] = (uint64_t)(astate >> 64), as.lane[N + i] = (uint64_t)astate;
         }
-        store_rng_state(d, i, q.rng);
-        if (SAMPLE && as.lane) as.lane[i] = (uint64_t)(astate >> 64), as.lane[N + i] = (uint64_t)astate;
     }
     block_accumulate(d, st);
 }

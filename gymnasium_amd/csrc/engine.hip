@@ -489,7 +489,7 @@ void mi_destroy(mi_vecenv *v) {
     (void)hipStreamSynchronize(v->stream);
     void *ptrs[] = {v->d.state, v->d.meta, v->d.rng, v->d.ep_ret, v->d.ep_len, v->d.blk_count, v->d.blk_ret, v->d_out,
                     v->d_pow2, v->d_act_lane, v->d_act_stage, v->d_actions, v->d_mask, v->d_words, v->d_extras, v->d_act_scratch, v->d_obs_scratch,
-                    v->shared.words, v->d_shared_pow2, v->shared.blk_done, v->shared.blk_prefix, v->d_attr, v->d_model, v->wrap.last_action, v->wrap.sticky_word,
+                    v->shared.words, v->d_shared_pow2, v->shared.blk_done, v->shared.blk_prefix, v->d_attr, v->d_model, v->wrap.last_action, v->wrap.sticky_word, v->wrap.frames,
                     v->d_act_ctl, v->d_act_partial, v->d_act_slot, v->d_arg_stage};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
@@ -740,6 +740,8 @@ int mi_set_step_wrappers(mi_vecenv *v, int num_repeats, double sticky_probabilit
     if (v->cfg.reserved[0] & MI_CFG_FAST_MATH) return fail(MI_ERR_UNSUPPORTED, "mi_set_step_wrappers: not with MI_CFG_FAST_MATH");
     if (v->has_epi) return fail(MI_ERR_UNSUPPORTED, "mi_set_step_wrappers: not with a step epilogue attached (mi_set_step_epilogue)");
     if (v->has_pending) return fail(MI_ERR_STATE, "an asynchronous step is pending (mi_step_wait)");
+    if (v->wrap.skip && num_repeats > 0)
+        return fail(MI_ERR_UNSUPPORTED, "mi_set_step_wrappers: not RepeatAction with mi_set_max_and_skip on (fold the repeat into skip)");
     if (num_repeats < 0 || sticky_duration < 0 || sticky_duration >= (1 << 30))
         return fail(MI_ERR_INVALID_ARGUMENT, "mi_set_step_wrappers: num_repeats and sticky_duration must be >= 0 (0: no such wrapper)");
     if (sticky_duration && !(sticky_probability >= 0.0 && sticky_probability < 1.0))
@@ -754,9 +756,41 @@ int mi_set_step_wrappers(mi_vecenv *v, int num_repeats, double sticky_probabilit
         HIP_TRY(hipMemsetAsync(v->wrap.sticky_word, 0, sizeof(uint32_t) * N, v->stream));
     }
     v->wrap.repeats = num_repeats, v->wrap.sticky_duration = sticky_duration, v->wrap.sticky_p = sticky_duration ? sticky_probability : 0.0;
-    v->wrap_on = num_repeats > 0 || sticky_duration > 0;
+    v->wrap_on = num_repeats > 0 || sticky_duration > 0 || v->wrap.skip > 0;
     v->wrap_act_kind = -1;
     if (v->wrap_on) v->per_lane = true;
+    return MI_OK;
+}
+
+// MaxAndSkipObservation of the sub-environments (include/mi355env.h mi_set_max_and_skip; device side: lane_step_wrapped<..., MAXSKIP>).
+int mi_set_max_and_skip(mi_vecenv *v, int skip) {
+    if (!v) return fail(MI_ERR_INVALID_ARGUMENT, "null env");
+    if (v->cfg.kind < 0 || v->cfg.kind >= kClassicKinds) return fail(MI_ERR_UNSUPPORTED, "mi_set_max_and_skip: the five classic-control kinds only");
+    if (v->shared_rng) return fail(MI_ERR_UNSUPPORTED, "mi_set_max_and_skip: not with MI_CFG_SHARED_RNG (CartPoleVectorEnv has no sub-environments to wrap)");
+    if (v->cfg.reserved[0] & MI_CFG_FAST_MATH) return fail(MI_ERR_UNSUPPORTED, "mi_set_max_and_skip: not with MI_CFG_FAST_MATH");
+    if (v->has_epi) return fail(MI_ERR_UNSUPPORTED, "mi_set_max_and_skip: not with a step epilogue attached (mi_set_step_epilogue)");
+    if (v->wrap.repeats > 0) return fail(MI_ERR_UNSUPPORTED, "mi_set_max_and_skip: not with RepeatAction on (mi_set_step_wrappers; fold the repeat into skip)");
+    if (v->has_pending) return fail(MI_ERR_STATE, "an asynchronous step is pending (mi_step_wait)");
+    if (skip < 0 || skip == 1) return fail(MI_ERR_INVALID_ARGUMENT, "mi_set_max_and_skip: skip must be >= 2 (0: no such wrapper)");
+    if (set_device(v)) return MI_ERR_HIP;
+    if (skip) {  // a newly constructed MaxAndSkipObservation: np.zeros((2, *shape))
+        const size_t bytes = sizeof(float) * 2 * (size_t)v->cfg.num_envs * (size_t)v->lay.obs_dim;
+        if (!v->wrap.frames) HIP_TRY(hipMalloc(&v->wrap.frames, bytes));
+        HIP_TRY(hipMemsetAsync(v->wrap.frames, 0, bytes, v->stream));
+    }
+    v->wrap.skip = skip;
+    v->wrap_on = v->wrap.repeats > 0 || v->wrap.sticky_duration > 0 || skip > 0;
+    if (v->wrap_on) v->per_lane = true;
+    return MI_OK;
+}
+int mi_get_max_and_skip_frames(mi_vecenv *v, float *dst, int on_device) {
+    if (!v || !dst) return fail(MI_ERR_INVALID_ARGUMENT, "null argument");
+    if (!v->wrap.skip) return fail(MI_ERR_STATE, "mi_get_max_and_skip_frames: MaxAndSkipObservation is not on (mi_set_max_and_skip)");
+    if (v->has_pending) return fail(MI_ERR_STATE, "an asynchronous step is pending (mi_step_wait)");
+    if (set_device(v)) return MI_ERR_HIP;
+    const size_t bytes = sizeof(float) * 2 * (size_t)v->cfg.num_envs * (size_t)v->lay.obs_dim;
+    HIP_TRY(hipMemcpyAsync(dst, v->wrap.frames, bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, v->stream));
+    if (!on_device) HIP_TRY(hipStreamSynchronize(v->stream));
     return MI_OK;
 }
 

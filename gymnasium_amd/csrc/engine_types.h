@@ -7,6 +7,8 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <type_traits>
+
 #include "../../include/mi355env.h"
 #include "envs_classic.h"
 #include "pcg64_dev.h"
@@ -78,6 +80,16 @@ struct WrapDev {
     uint64_t *last_action;  // [N] StickyAction.last_action: the bits of the lane's last effective action (E::Act)
     uint32_t *sticky_word;  // [N] bit 31: last_action is not None; bits 0..30: repeats_taken (is_sticky_actions <=> > 0; num_repeats is then the duration)
 };
+// ... and with MaxAndSkipObservation(env, skip) (wrappers/stateful_observation.py:564-649; mi_set_max_and_skip): what the env holds (mi_vecenv::wrap) and
+// what the MAXSKIP instantiations of the two kernels take.  The others go on taking the WrapDev part alone: a longer argument would move the hidden
+// kernel arguments behind it, and with them a literal in every existing instantiation.  In the env `repeats` is 0 while `skip` is on; the copy that
+// a MAXSKIP kernel is launched with carries the skip as `repeats` too (classic.hip wrap_arg): RepeatAction's loop runs it.
+struct WrapSkipDev : WrapDev {
+    int skip;       // inner steps per step(); 0: no such wrapper
+    float *frames;  // [2][N][OBS] the wrappers' _obs_buffer: slot-major, one OBS-wide row per lane (load_row / store_row: consecutive lanes, consecutive rows)
+};
+template <bool MAXSKIP>
+using WrapArg = std::conditional_t<MAXSKIP, WrapSkipDev, WrapDev>;
 }  // namespace mi_internal
 using namespace mi_internal;
 namespace {
@@ -300,7 +312,8 @@ struct mi_vecenv {
     // mi_set_step_wrappers: RepeatAction / StickyAction of the sub-environments inside the step.  wrap_on: the *_wrapped_kernel entry points run, with
     // `wrap` as their last argument (its two arrays are allocated by the first call that switches StickyAction on).  per_lane: some call has switched
     // them on -- from then on the env stays on the per-lane types (envs_classic.h *AttrT) and their one-role kernels, as after mi_set_env_attr.
-    WrapDev wrap;
+    // mi_set_max_and_skip: wrap.skip / wrap.frames (allocated by the first call that switches it on); wrap_on covers it too.
+    WrapSkipDev wrap;
     bool wrap_on, per_lane;
     int wrap_act_kind;  // StickyAction: the element type of the action rows it has seen (last_action is kept in that type); -1: none yet
     // sample(mask=...) / sample(probability=...) on the action stream (action_mask.hip): the pending 32-bit half and the words of the batch in flight,

@@ -356,14 +356,35 @@ MI_DEV void store_wrap_lane(const WrapDev &w, int i, const WrapLane<E> &s) {
     if (w.sticky_duration) w.last_action[i] = action_bits(s.last), w.sticky_word[i] = s.word;
 }
 constexpr uint32_t kStickyHasLast = 1u << 31;
+// ... and, for the MAXSKIP instantiations (mi_set_max_and_skip), MaxAndSkipObservation's _obs_buffer of the lane (WrapSkipDev::frames), in registers
+// for the launch like the words above.  `written`: a slot was written since the load.  (load_skip_lane / store_skip_lane: behind the row stores below.)
+template <class E>
+struct SkipWrapLane : WrapLane<E> {
+    float f[2][E::OBS];
+    uint32_t written;
+    // np.max(self._obs_buffer, axis=0): a plain comparison, which also hands a NaN on from either slot as np.max does (unreachable from the five
+    // kinds).  Which zero comes out of +0 and -0 is not pinned by NumPy's reduction and not pinned here.
+    MI_DEV void max_frame(float dst[E::OBS]) const {
+#pragma unroll
+        for (int k = 0; k < E::OBS; k++) dst[k] = (f[0][k] > f[1][k] || f[0][k] != f[0][k]) ? f[0][k] : f[1][k];
+    }
+};
+template <class E, bool MAXSKIP>
+using WrapLaneOf = std::conditional_t<MAXSKIP, SkipWrapLane<E>, WrapLane<E>>;
 
 // lane_step with the two wrappers around E::step.  The plain form of lane_step (branches, not lane_step_fused's selects): the repeat loop has a
 // wave-uniform trip count (w.repeats), and a lane whose episode ended inside it is masked off for the remaining trips (`active`), so the wavefront
 // stays in step.  Order of the generator's draws, as in the reference: the sticky draw (StickyAction.action, :118-142), then each inner step's own
 // draw (STEP_DRAWS), then a SAME_STEP reset's.  Nothing is drawn ahead: with a queue (rollouts) the generator is q->rng and the queue is filled
 // only by the reset that empties it; without (step_kernel) it is a copy of `preloaded` that goes back to memory when it moved.
-template <class E, int MODE>
-MI_DEV void lane_step_wrapped(const DevEnv &d, const WrapDev &w, WrapLane<E> &sl, int i, Lane<E> &L, typename E::Act a, StepOut<E> &o, LaneStats &st,
+// MAXSKIP: MaxAndSkipObservation(env, skip) (wrappers/stateful_observation.py:623-649) in RepeatAction's place.  The loop is RepeatAction's -- the host
+// hands the skip over as w.repeats --; the observation after inner step skip - 2 goes to frame slot 0, the one after skip - 1 to slot 1 (E::obs is
+// evaluated at those two only), and what the step returns where RepeatAction returns the last inner observation is the element-wise maximum of the two
+// slots AS THEY THEN STAND: nothing ever clears them (they are read and written here and nowhere else), so a step that ended before it wrote a slot
+// returns what an earlier step -- of an earlier episode, or the constructor's zeros -- left there.  The other instantiations are, statement for
+// statement, the function they were: everything added stands under `if constexpr (MAXSKIP)`.
+template <class E, int MODE, bool MAXSKIP = false>
+MI_DEV void lane_step_wrapped(const DevEnv &d, const WrapArg<MAXSKIP> &w, WrapLaneOf<E, MAXSKIP> &sl, int i, Lane<E> &L, typename E::Act a, StepOut<E> &o, LaneStats &st,
                               ResetQueue<E> *q, const Pcg64 *preloaded) {
     o.has_final = false;
     Pcg64 own;
@@ -412,6 +433,18 @@ MI_DEV void lane_step_wrapped(const DevEnv &d, const WrapDev &w, WrapLane<E> &sl
             tr = d.max_steps > 0 && (int)L.elapsed >= d.max_steps;
             total += rew;  // total_reward = 0.0; total_reward += float(reward), in inner order
             active = !(te || tr);
+            if constexpr (MAXSKIP) {
+                // before the `break`, as in the reference.  j is wave-uniform: a scalar branch around ONE inlined E::obs for the two trips that
+                // write a slot (two call sites cost Pendulum's rollout ~25 VGPRs: past the 256 that keep its inline-asm FMAs clear of AGPR copies)
+                if (j >= trips - 2) {
+                    float frame[E::OBS];
+                    E::obs(L.s, L.flags, frame, L.trig);
+                    const bool last = j == trips - 1;
+#pragma unroll
+                    for (int k = 0; k < E::OBS; k++) sl.f[0][k] = last ? sl.f[0][k] : frame[k], sl.f[1][k] = last ? frame[k] : sl.f[1][k];
+                    sl.written = 1u;
+                }
+            }
         }
     }
     if (w.repeats > 0) rew = total;  // (without RepeatAction the one reward as it is, the sign of a zero included)
@@ -427,14 +460,24 @@ MI_DEV void lane_step_wrapped(const DevEnv &d, const WrapDev &w, WrapLane<E> &sl
         st.length_sum += (uint64_t)L.ep_len;
     }
     if (MODE == MI_AUTORESET_SAME_STEP && done) {
-        E::obs(L.s, L.flags, o.final_obs, L.trig);  // the last INNER observation
+        if constexpr (MAXSKIP)
+            sl.max_frame(o.final_obs);
+        else
+            E::obs(L.s, L.flags, o.final_obs, L.trig);  // the last INNER observation
         o.has_final = true;
         lane_autoreset<E>(d, i, L, q, &own);  // (without a queue: continues from `own` and stores it)
         sl.word = 0u;
     } else if (!q && drew) {
         store_rng_state(d, i, own);
     }
-    E::obs(L.s, L.flags, o.obs, L.trig);
+    if constexpr (MAXSKIP) {
+        if (MODE == MI_AUTORESET_SAME_STEP && done)
+            E::obs(L.s, L.flags, o.obs, L.trig);  // the reset's observation
+        else
+            sl.max_frame(o.obs);
+    } else {
+        E::obs(L.s, L.flags, o.obs, L.trig);
+    }
     o.reward = rew, o.terminated = te, o.truncated = tr;
     if (done && MODE != MI_AUTORESET_SAME_STEP)
         L.flags |= kNeedsReset;
@@ -461,6 +504,26 @@ template <int W>
 MI_DEV void load_row(const float *src, float *dst) {
 #pragma unroll
     for (int k = 0; k < W; k++) dst[k] = src[k];
+}
+
+// The lane's two frames: requested with the rest of the lane (arrive_skip_lane pins the loads where they were issued, like LaneRequest::arrive) and
+// stored back by a launch that wrote a slot.  mi_reset, mi_set_state and the autoreset paths never come here.
+template <class E>
+MI_DEV void load_skip_lane(const WrapSkipDev &w, const DevEnv &d, int i, SkipWrapLane<E> &s) {
+    load_row<E::OBS>(w.frames + (size_t)i * E::OBS, s.f[0]);
+    load_row<E::OBS>(w.frames + ((size_t)d.N + i) * E::OBS, s.f[1]);
+    s.written = 0u;
+}
+template <class E>
+MI_DEV void arrive_skip_lane(SkipWrapLane<E> &s) {
+#pragma unroll
+    for (int k = 0; k < E::OBS; k++) hold_opaque(s.f[0][k]), hold_opaque(s.f[1][k]);
+}
+template <class E>
+MI_DEV void store_skip_lane(const WrapSkipDev &w, const DevEnv &d, int i, const SkipWrapLane<E> &s) {
+    if (!s.written) return;
+    store_row<E::OBS>(w.frames + (size_t)i * E::OBS, s.f[0]);
+    store_row<E::OBS>(w.frames + ((size_t)d.N + i) * E::OBS, s.f[1]);
 }
 
 }  // namespace

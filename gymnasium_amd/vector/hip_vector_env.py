@@ -96,7 +96,7 @@ class HipVectorEnv(VectorEnv):
 
     def _can_fuse(self) -> bool:
         return (self.FUSES_WRAPPERS and self._engine_factory is None and hasattr(self._engine.lib, "set_step_epilogue")
-                and not self._fusion_state()["closed"] and self._step_wrappers == (0, 0.0, 0))
+                and not self._fusion_state()["closed"] and self._step_wrappers == (0, 0.0, 0) and self._max_and_skip == 0)
 
     def _fuse(self, wrapper, slot: str) -> int:
         """Register ``wrapper`` as the next member of the fused unit; returns its position in the chain."""
@@ -1115,8 +1115,54 @@ class HipVectorEnv(VectorEnv):
         refusal = self._step_wrappers_refusal()
         if refusal:
             raise error.Error(refusal)
+        if num_repeats and self._max_and_skip:
+            raise error.Error("this env runs MaxAndSkipObservation, which repeats the action itself: fold the repeat into its `skip` "
+                              "(env.set_max_and_skip() switches it off)")
         self._engine.set_step_wrappers(num_repeats, sticky_probability, sticky_duration)
         self._step_wrappers = (int(num_repeats), float(sticky_probability), int(sticky_duration))
+
+    # -- MaxAndSkipObservation of the sub-environments (gymnasium_amd.wrappers.MaxAndSkipObservation; mi_set_max_and_skip) ------------------------
+    _max_and_skip = 0  # the skip the engine runs; 0 = no such wrapper
+
+    def _max_and_skip_refusal(self) -> str | None:
+        if self.KIND not in ("cartpole", "pendulum", "acrobot", "mountain_car", "mountain_car_continuous"):
+            return (f"{type(self).__name__}: MaxAndSkipObservation of the sub-environments exists for CartPole-v1, Pendulum-v1, Acrobot-v1, "
+                    "MountainCar-v0 and MountainCarContinuous-v0 only (the MuJoCo and ToyText kernels have no inner-step loop)")
+        if getattr(self, "_shared_rng", False):
+            return "rng='shared' is the reference's NumPy CartPoleVectorEnv: it has no sub-environments that a scalar wrapper could wrap"
+        if getattr(self, "fast_math", False):
+            return "MaxAndSkipObservation of the sub-environments runs the exact kernels only: not with fast_math=True"
+        st = self.__dict__.get("_fused")
+        if st is not None and st["chain"]:
+            return "vector wrappers are already fused into this env's step kernel: MaxAndSkipObservation goes directly over the env, the vector wrappers above it"
+        if not hasattr(getattr(self._engine, "lib", None), "set_max_and_skip"):
+            return "the engine behind this env has no MaxAndSkipObservation of the sub-environments (mi_set_max_and_skip)"
+        return None
+
+    def set_max_and_skip(self, skip: int = 0) -> None:
+        """What ``wrappers.MaxAndSkipObservation`` switches on: every sub-environment steps as if it were wrapped in
+        ``MaxAndSkipObservation(env, skip)`` (0: the plain step again).  Each call constructs the wrapper anew: all frames are zeros.  Not together
+        with ``RepeatAction`` (fold the repeat into ``skip``); ``StickyAction`` goes over it."""
+        self._check_open()
+        self._check_not_pending("set_max_and_skip")
+        refusal = self._max_and_skip_refusal()
+        if refusal:
+            raise error.Error(refusal)
+        if skip and self._step_wrappers[0] > 0:
+            raise error.Error("this env runs RepeatAction: MaxAndSkipObservation repeats the action itself, fold the repeat into `skip` "
+                              "(env.set_step_wrappers() switches RepeatAction off)")
+        self._engine.set_max_and_skip(skip)
+        self._max_and_skip = int(skip)
+
+    def max_and_skip_frames(self) -> np.ndarray:
+        """The sub-environments' ``_obs_buffer``: float32 ``[2, num_envs, *obs_shape]`` (tests, checkpoints).  Nothing but ``set_max_and_skip``
+        ever clears it: ``reset()``, a masked reset and ``set_state()`` leave it as it is."""
+        self._check_open()
+        self._check_not_pending("max_and_skip_frames")
+        if not self._max_and_skip:
+            raise error.Error("MaxAndSkipObservation is not on (set_max_and_skip)")
+        dim = int(np.prod(self.single_observation_space.shape))
+        return self._engine.get_max_and_skip_frames(dim).reshape((2, self.num_envs) + tuple(self.single_observation_space.shape))
 
     # -- bookkeeping -----------------------------------------------------------------------------------
     def statistics(self) -> dict:
@@ -1205,6 +1251,7 @@ class GraphedSteps:
         self.env, self.steps, self.actions, self.policy = env, steps, actions, policy
         self.attr_mask = env._env_attr_mask  # which kernels the graph holds (per-lane attributes: set_attr)
         self.step_wrappers = env._step_wrappers  # ... and whose parameters they carry (RepeatAction / StickyAction: set_step_wrappers)
+        self.max_and_skip = env._max_and_skip  # (MaxAndSkipObservation: set_max_and_skip)
         self._capture()
 
     def _prepare_capture(self):
@@ -1251,6 +1298,9 @@ class GraphedSteps:
         if env._step_wrappers != getattr(self, "step_wrappers", env._step_wrappers):
             raise error.Error("RepeatAction / StickyAction of the sub-environments were switched since this graph was captured; its kernels carry the "
                               "old setting: capture the steps again")
+        if env._max_and_skip != getattr(self, "max_and_skip", env._max_and_skip):
+            raise error.Error("MaxAndSkipObservation of the sub-environments was switched since this graph was captured; its kernels carry the old "
+                              "setting: capture the steps again")
         env._bind_stream()  # statistics() / synchronize() wait on the engine's stream: keep it the one the replay runs on
         if self.policy == "random":
             space = env.action_space

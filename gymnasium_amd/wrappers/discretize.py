@@ -29,7 +29,7 @@ import numpy as np
 
 from .. import _native
 from ..gym_api import AutoresetMode, batch_space, error, spaces
-from .vector import RepeatAction, StickyAction, VectorActionWrapper, VectorWrapper, _close_fusion, _refuse_capture, _torch
+from .vector import MaxAndSkipObservation, RepeatAction, StickyAction, VectorActionWrapper, VectorWrapper, _close_fusion, _refuse_capture, _torch
 
 
 def _setup(box, bins, what, flat, table_of):
@@ -189,7 +189,7 @@ class DiscretizeObservation(VectorWrapper):
         must be reset by the caller): over the env itself the raw trajectory is collected from T ``step()`` calls, as the per_env wrappers do, and
         then discretized in one launch; ``infos=True`` is refused there."""
         e = self.env
-        while isinstance(e, (VectorActionWrapper, RepeatAction, StickyAction)):
+        while isinstance(e, (VectorActionWrapper, RepeatAction, StickyAction, MaxAndSkipObservation)):
             e = e.env
         if self.env.metadata.get("autoreset_mode") == AutoresetMode.DISABLED and not isinstance(e, VectorWrapper):
             out = self._rollout_by_steps(int(num_steps), actions, **kwargs)

@@ -13,7 +13,7 @@ lane runs the reference's float32 / float64 recurrence (csrc/per_env_normalize.h
 ``NormalizeReward`` are the VECTOR wrappers (one set of statistics over the batch).  The split is gymnasium's ``wrappers`` / ``wrappers.vector`` in
 reverse: in this package the default namespace is the vector one.
 
-Placement: directly over a ``HipVectorEnv`` or over ``RepeatAction`` / ``StickyAction`` (normalisation then sees the outer steps, as in the reference);
+Placement: directly over a ``HipVectorEnv`` or over ``RepeatAction`` / ``MaxAndSkipObservation`` / ``StickyAction`` (normalisation then sees the outer steps, as in the reference);
 one may sit on the other, in either order, with identical results; every vector wrapper (``ClipReward``, ``TransformObservation``,
 ``RecordEpisodeStatistics``, ``ClipAction`` ...) goes above.  A ``step()`` of the pair is ONE launch behind the env's own; ``rollout(T)`` is one launch
 behind the rollout's.  Device tensors pass straight through; NumPy batches are staged through the device (a correctness path).
@@ -52,7 +52,7 @@ import numpy as np
 
 from .. import _native
 from ..gym_api import AutoresetMode, batch_space, error, spaces
-from .vector import RepeatAction, StickyAction, VectorWrapper, _base_env, _close_fusion, _refuse_capture, _torch
+from .vector import MaxAndSkipObservation, RepeatAction, StickyAction, VectorWrapper, _base_env, _close_fusion, _refuse_capture, _torch
 
 _MODES = {AutoresetMode.NEXT_STEP: 0, AutoresetMode.SAME_STEP: 1, AutoresetMode.DISABLED: 2}
 
@@ -89,7 +89,7 @@ class _PerEnvWrapper(VectorWrapper):
         e = inner
         if isinstance(e, _PerEnvWrapper):
             raise error.Error(f"the sub-environments are already wrapped in per_env.NormalizeObservation and per_env.NormalizeReward: at most one of each")
-        while isinstance(e, (RepeatAction, StickyAction)):
+        while isinstance(e, (RepeatAction, StickyAction, MaxAndSkipObservation)):
             e = e.env
         if isinstance(e, VectorWrapper) or not hasattr(e, "_engine"):
             raise error.Error(f"per_env.{name} wraps every SUB-environment, below the vector level: it goes directly over a HipVectorEnv "
@@ -450,7 +450,8 @@ class _StatefulObservation(VectorWrapper):
 
     There is no CPU implementation: over a backend without the device engine the constructors validate their arguments and build their spaces --
     which can be inspected --, and the first ``reset`` / ``step`` / ``rollout`` raises ``error.Error``.
-    Out of scope: ``MaxAndSkipObservation`` (an inner-step wrapper: it belongs in the step kernel next to ``RepeatAction``), fusing these passes into
+    ``MaxAndSkipObservation`` is an inner-step wrapper and lives in the step kernel next to ``RepeatAction`` (``wrappers.MaxAndSkipObservation``): these
+    wrappers go over it as they go over ``RepeatAction``.  Out of scope: fusing these passes into
     the step / rollout kernels, rollouts under SAME_STEP, ToyText observations, the normalisers above these wrappers."""
 
     _what = "observations"
@@ -459,7 +460,7 @@ class _StatefulObservation(VectorWrapper):
     def __init__(self, env):
         name = type(self).__name__
         e = env
-        while isinstance(e, (_StatefulObservation, _PerEnvWrapper, RepeatAction, StickyAction)):
+        while isinstance(e, (_StatefulObservation, _PerEnvWrapper, RepeatAction, StickyAction, MaxAndSkipObservation)):
             e = e.env
         if isinstance(e, VectorWrapper) or not hasattr(e, "_engine"):
             raise error.Error(f"per_env.{name} wraps every SUB-environment, below the vector level: it goes over a HipVectorEnv (gymnasium_amd.make_vec(...)), "

@@ -293,6 +293,9 @@ class RepeatAction(VectorWrapper):
             raise TypeError(f"The num_repeats is expected to be an integer, actual type: {type(num_repeats)}")
         if num_repeats < 1:
             raise ValueError(f"The num_repeats value needs to be equal or greater than one, actual value: {num_repeats}")
+        if isinstance(env, MaxAndSkipObservation):
+            raise error.Error("RepeatAction over MaxAndSkipObservation: MaxAndSkipObservation repeats the action itself -- fold the repeat into its "
+                              f"`skip` (MaxAndSkipObservation(env, {int(env.skip) * int(num_repeats)}) runs as many inner steps)")
         base = _bare_env(env, "RepeatAction")
         if base._step_wrappers != (0, 0.0, 0):
             raise error.Error("this env already runs RepeatAction / StickyAction: switch them off first (env.set_step_wrappers())")
@@ -302,13 +305,46 @@ class RepeatAction(VectorWrapper):
         self.num_repeats = num_repeats
 
 
+class MaxAndSkipObservation(VectorWrapper):
+    """``SyncVectorEnv`` over scalar envs each wrapped in ``gymnasium.wrappers.MaxAndSkipObservation(env, skip)`` (stateful_observation.py:564-649;
+    the reference has no vector version): a ``step()`` runs up to ``skip`` inner steps of every sub-environment with the same action IN ONE
+    LAUNCH, as ``RepeatAction`` does (TimeLimit counts inner steps, the reward is ``0.0 + r0 + r1 ...``, episode statistics count one step per
+    ``step()``), and returns the element-wise maximum of the sub-environment's two frames: frame 0 is written after inner step ``skip - 2``, frame 1
+    after inner step ``skip - 1``.  The frames start as zeros and are NEVER cleared -- not by ``reset()``, a masked reset, an autoreset or
+    ``set_state()`` -- so a step whose episode ended before it wrote a frame returns the maximum over what an earlier step, possibly of an earlier
+    episode, left there (``env.max_and_skip_frames()`` shows them).  Which zero comes out of ``+0`` and ``-0`` is not pinned (NumPy's reduction
+    does not promise one).  The NEXT_STEP autoreset step returns the plain reset observation; under SAME_STEP ``final_obs`` is the max frame.
+    Goes directly over the env of the five classic-control ids; ``StickyAction`` may go over it, ``RepeatAction`` neither over nor under it (fold
+    the repeat into ``skip``); the ``per_env`` wrappers, the Discretize wrappers and every vector wrapper go above.  ``step``, ``step(None)``,
+    ``rollout`` and ``capture_steps`` all follow."""
+
+    def __init__(self, env, skip: int = 4):
+        if not np.issubdtype(type(skip), np.integer):
+            raise TypeError(f"The skip is expected to be an integer, actual type: {type(skip)}")
+        if skip < 2:
+            raise ValueError(f"The skip value needs to be equal or greater than two, actual value: {skip}")
+        if isinstance(env, RepeatAction):
+            raise error.Error("MaxAndSkipObservation over RepeatAction: MaxAndSkipObservation repeats the action itself -- fold the repeat into "
+                              f"`skip` (MaxAndSkipObservation(env, {int(skip) * int(env.num_repeats)}) over the bare env runs as many inner steps)")
+        base = _bare_env(env, "MaxAndSkipObservation")
+        if not hasattr(base, "set_max_and_skip"):
+            raise error.Error(f"{type(base).__name__} has no MaxAndSkipObservation of the sub-environments (mi_set_max_and_skip)")
+        if base._step_wrappers != (0, 0.0, 0) or base._max_and_skip:
+            raise error.Error("this env already runs RepeatAction / StickyAction / MaxAndSkipObservation: switch them off first "
+                              "(env.set_step_wrappers(), env.set_max_and_skip()); a repeat is folded into `skip`")
+        super().__init__(env)
+        base.set_max_and_skip(int(skip))
+        _close_fusion(env)
+        self.skip = skip
+
+
 class StickyAction(VectorWrapper):
     """``SyncVectorEnv`` over scalar envs each wrapped in ``gymnasium.wrappers.StickyAction(env, repeat_action_probability,
     repeat_action_duration)`` (stateful_action.py:16-142, Machado et al. 2018; the reference has no vector version).  Before a step, a
     sub-environment that has a last action and is not inside a series draws ``np_random.uniform()`` from ITS OWN generator (the one its resets
     consume: ``get_rng_state()`` shows it) and with that probability repeats its last action for ``repeat_action_duration`` steps; every reset
-    of a sub-environment clears its state.  Goes directly over the env of the five classic-control ids or over ``RepeatAction`` (one decision per
-    outer step); every vector wrapper goes above.  Two deliberate differences: actions are validated as given (the reference never looks at an
+    of a sub-environment clears its state.  Goes directly over the env of the five classic-control ids or over ``RepeatAction`` /
+    ``MaxAndSkipObservation`` (one decision per outer step); every vector wrapper goes above.  Two deliberate differences: actions are validated as given (the reference never looks at an
     action that a sticky one replaces), and the element type of the action batch (float32 / float64 rows) must not change between steps.
     ``repeat_action_duration`` is an int: a (low, high) range is drawn by ``Generator.integers`` from PCG64's buffered 32-bit half, which the
     sub-environments' generators on the device do not carry -- refused, not approximated."""
@@ -332,6 +368,8 @@ class StickyAction(VectorWrapper):
         repeats = 0
         if isinstance(env, RepeatAction):
             inner, repeats = env.env, int(env.num_repeats)
+        elif isinstance(env, MaxAndSkipObservation):  # (one decision per outer step, as over RepeatAction; the engine keeps the skip apart)
+            inner = env.env
         base = _bare_env(inner, "StickyAction")
         if base._step_wrappers != (repeats, 0.0, 0):
             raise error.Error("this env already runs StickyAction (RepeatAction goes UNDER StickyAction, never over it): switch them off first "

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-/* Entry points that were only ADDED since (mi_action_sample_masked and its three companions, mi_set_step_wrappers) leave the number where it is: nothing an ABI 10
+/* Entry points that were only ADDED since (mi_action_sample_masked and its three companions, mi_set_step_wrappers, mi_set_max_and_skip) leave the number where it is: nothing an ABI 10
  * caller uses changed, and a caller that needs them finds out by looking the symbol up. */
 #define MI355ENV_ABI_VERSION 10
 
@@ -502,6 +502,30 @@ int mi_get_model_derived(mi_vecenv *env, int which, double *host_out);
  * action rows (mi_step_io.actions_dtype) must not change from call to call: MI_ERR_UNSUPPORTED.
  */
 int mi_set_step_wrappers(mi_vecenv *env, int num_repeats, double sticky_probability, int sticky_duration);
+
+/*
+ * gymnasium.wrappers.MaxAndSkipObservation(env, skip) (wrappers/stateful_observation.py:564-649) around every scalar env, outside its TimeLimit --
+ * what make_vec(id, n, "sync", wrappers=(lambda e: MaxAndSkipObservation(e, skip),)) builds; the reference has no vector form.  Added to ABI 10, which
+ * it leaves as it is.  The five classic-control kinds, under the conditions of mi_set_step_wrappers; mi_step, mi_rollout and mi_rollout_infos follow.
+ *   A step runs up to `skip` inner steps with the same action and stops after the first that terminates or truncates (TimeLimit counts INNER steps);
+ *   reward = 0.0 + r_0 + r_1 ... in that order.  Each sub-environment owns two observation frames (float32, the observation's dtype): the observation
+ *   after inner step skip - 2 is written to frame 0, the one after inner step skip - 1 to frame 1, and the step returns the element-wise maximum of the
+ *   two frames AS THEY THEN STAND (obs; under SAME_STEP final_obs, with obs the reset observation).  The frames are zeros when the wrapper is
+ *   constructed and NOTHING clears them afterwards: not mi_reset (with or without mask), not mi_set_state, not an autoreset.  A step that ended before
+ *   it wrote a frame returns the maximum over what an earlier step -- of an earlier episode, or the constructor -- left there.  The NEXT_STEP
+ *   autoreset step returns the plain reset observation, reward 0, and repeats nothing; DISABLED refuses a finished row as mi_step always does.
+ *   A NaN in either frame comes out (np.max); which zero comes out of +0 and -0 is not pinned, by NumPy's reduction or here.
+ *   episode_return / episode_length and mi_stats count one step per call with the summed reward, as under RepeatAction.
+ * skip >= 2 switches the wrapper on and zeroes the frames (every call constructs it anew); 0 switches it off; 1 or a negative value:
+ * MI_ERR_INVALID_ARGUMENT.  MI_ERR_UNSUPPORTED: another kind, MI_CFG_SHARED_RNG, MI_CFG_FAST_MATH, a step epilogue attached, or RepeatAction on
+ * (mi_set_step_wrappers with num_repeats > 0 is refused likewise while this is on: fold the repeat into skip).  StickyAction (num_repeats == 0)
+ * composes with it as with RepeatAction: one decision per call, taken first.  The first call that switches it on moves the env to the per-lane
+ * kernels for good; the frames live in device memory, allocated by that call: mi_step stays capturable.  mi_get_state / mi_set_state do not carry them;
+ * mi_get_max_and_skip_frames copies them out as float32 [2][num_envs][obs_dim] (on_device = 0: host memory, synchronises; 1: device memory,
+ * enqueued on the env's stream); MI_ERR_STATE while the wrapper is off.
+ */
+int mi_set_max_and_skip(mi_vecenv *env, int skip);
+int mi_get_max_and_skip_frames(mi_vecenv *env, float *dst, int on_device);
 
 /*
  * Stateful vector wrappers as device epilogues of the step path.  All array arguments are DEVICE

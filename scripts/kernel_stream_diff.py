@@ -4,7 +4,10 @@ s_add_u32 / s_addc_u32), which is the distance to a constant table and moves whe
 listed as new.  A function that several translation units emit (a non-template kernel or out-of-line device function of a shared header, each unit
 with its own flags) has several copies under one name: every copy of the first file must be among the second file's, in whatever order the units
 were linked.
-usage: python scripts/kernel_stream_diff.py OLD.so NEW.so      (exit status 1 if a common symbol differs or one is missing)"""
+usage: python scripts/kernel_stream_diff.py OLD.so NEW.so [--added-default VALUE]     (exit status 1 if a common symbol differs or one is missing)
+--added-default VALUE: a template of NEW gained a trailing parameter whose default is VALUE (e.g. `false`), which renames every instantiation.  A
+symbol of OLD that NEW lacks is then compared with NEW's symbol whose demangled name has `, VALUE` appended to the function's template arguments (the
+parameter list is not compared), and counts as identical / differing under that name."""
 import hashlib
 import os
 import re
@@ -50,6 +53,19 @@ def streams(path):
 
 def main():
     old, new = streams(sys.argv[1]), streams(sys.argv[2])
+    if "--added-default" in sys.argv:
+        value = sys.argv[sys.argv.index("--added-default") + 1]
+        lacking, fresh = sorted(set(old) - set(new)), sorted(set(new) - set(old))
+        plain = subprocess.run(["c++filt"], input="\n".join(lacking + fresh), capture_output=True, text=True).stdout.splitlines()
+        # (by the name and its template arguments alone: a parameter type that depends on the new template parameter is spelt differently too)
+        by_name = {name.split(">(", 1)[0]: k for name, k in zip(plain[len(lacking):], fresh)}
+        renamed = 0
+        for k, name in zip(lacking, plain):
+            target = by_name.get(name.split(">(", 1)[0] + f", {value}") if ">(" in name else None
+            if target is not None:
+                new[k] = new.pop(target)
+                renamed += 1
+        print(f"{renamed} symbols of the first file compared under their name with `, {value}` appended to the template arguments")
     missing = sorted(set(old) - set(new))
     differ = sorted(k for k in old if k in new and not old[k] <= new[k])
     added = sorted(set(new) - set(old))
