@@ -1,6 +1,7 @@
 // engine.hip -- libmi355env.so: the host side and the C ABI of include/mi355env.h for the lockstep vector-environment kernels for MI355X (gfx950).
-// The ToyText kernels (tabular_kernels.h), the per-lane MuJoCo kernels over the stock models (mj_glue_kernels.h; mjx_model.hip and mjx_mass_model.hip
-// instantiate them over the per-sub-environment model fields) and the small family-independent kernels (seeding, the action stream, transposes) are
+// The ToyText kernels (tabular_kernels.h), the per-lane MuJoCo kernels over the stock models (mj_glue_kernels.h, and mj_wrapped_kernels.h for their step
+// under RepeatAction / StickyAction; mjx_model.hip and mjx_mass_model.hip instantiate both over the per-sub-environment model fields) and the small
+// family-independent kernels (seeding, the action stream, transposes) are
 // instantiated here; the classic-control kernels are classic.hip's, behind the launch functions of namespace mi_classic.  What the units of the library
 // share is in engine_types.h (structs, mi_vecenv, cross-unit launch functions) and lane_common.h (device helpers).
 //
@@ -10,7 +11,8 @@
 // API-typed outputs (obs rows, reward, flags) are written straight from registers as contiguous per-wavefront
 // segments.  TimeLimit, the autoreset state machine, the per-env PCG64 streams and the episode-return bookkeeping
 // all live on device; a step() is ONE kernel launch, a rollout(T) is ONE launch for T steps with the state held
-// in registers in between.  There is no CPU fallback anywhere in this file.
+// in registers in between (the MuJoCo kinds: physics + glue per step for the cooperative robots, and a series of such trips per step while
+// RepeatAction / StickyAction are on, launch_mj_step_wrapped).  There is no CPU fallback anywhere in this file.
 //
 // Reference semantics reproduced (paths relative to the reference tree):
 //   vector/sync_vector_env.py:187-337  SyncVectorEnv.reset/step incl. NEXT_STEP / SAME_STEP / DISABLED autoreset
@@ -35,6 +37,7 @@
 #include "lane_common.h"
 #include "wrappers_internal.h"
 #include "mj_glue_kernels.h"
+#include "mj_wrapped_kernels.h"
 #include "mjx_physics.h"
 #include "tabular_kernels.h"
 
@@ -207,9 +210,49 @@ int check_device_error(mi_vecenv *v) {
 
 namespace {
 
+// One vector step of a MuJoCo env with RepeatAction / StickyAction on (mi_set_step_wrappers; mj_wrapped_kernels.h): the opening kernel, then per trip
+// what the plain step launches -- [cooperative physics ->] glue, the wrapped instantiation -- all on the env's stream, nothing synchronised.  The physics
+// launch of a trip takes the inner-step words as its meta (their skip bit as the mask: rows that finished inside the repeat, or that reset instead of
+// stepping, retire) and the effective action rows as its actions.
+template <class E>
+int launch_mj_step_wrapped(mi_vecenv *v, MjStepPtrs mp) {
+    const dim3 g(v->grid), b(kBlock);
+    const int mode = v->cfg.autoreset_mode;
+    const MjWrapDev w = {v->wrap.repeats, v->wrap.sticky_duration, v->wrap.sticky_p, v->wrap.last_action, v->wrap.sticky_word, v->d_wrap_acc, v->d_wrap_inner};
+    hipLaunchKernelGGL(mj_wrap_open_kernel, g, b, 0, v->stream, v->d, w, mp.actions, (int)E::NU, mp.act_f64, mode);
+    if (w.sticky_duration) mp.actions = w.last_action;
+    mp.extras = nullptr;
+    const int trips = w.repeats > 0 ? w.repeats : 1;
+    for (int trip = 0; trip < trips; trip++) {
+        if (v->d_model) {  // per-sub-environment model fields: the one-lane simulator with the lane's view
+            const bool mass = (v->model_mask & (1u << MI_MODEL_BODY_MASS_SCALE)) != 0;
+            if (!(mass ? mi_mjmass::step_wrapped : mi_mjmodel::step_wrapped)(v->cfg.kind, mode, trip, v->grid, v->stream, v->d, &mp, w))
+                return fail(MI_ERR_UNSUPPORTED, "no per-lane-model kernel for this env kind");
+            continue;
+        }
+        if constexpr (E::HAS_COOP) {
+            if (v->mj_coop) {
+                mi_phys::Args pa;
+                pa.state = v->d.state, pa.meta = w.inner, pa.needs_reset_mask = kMjInnerSkip, pa.N = v->d.N, pa.frame_skip = (int)v->d.P.p[4];
+                pa.newton = v->d.solver_newton, pa.act_f64 = mp.act_f64;
+                const bool ok = E::COOP_G == 16 ? mi_phys::launch16(v->cfg.kind, pa, true, mp.actions, v->d_extras, v->stream)
+                                                : mi_phys::launch32(v->cfg.kind, pa, true, mp.actions, v->d_extras, v->stream);
+                if (!ok) return fail(MI_ERR_UNSUPPORTED, "no cooperative physics kernel for this env kind");
+                mp.extras = v->d_extras;
+                hipLaunchKernelGGL((mj_trip_kernel<E, true>), g, b, 0, v->stream, v->d, mp, w, mode, trip);
+                continue;
+            }
+        }
+        hipLaunchKernelGGL((mj_trip_kernel<E, false>), g, b, 0, v->stream, v->d, mp, w, mode, trip);
+    }
+    HIP_TRY(hipGetLastError());
+    return MI_OK;
+}
+
 // One vector step of a MuJoCo env: [cooperative physics ->] per-lane glue (autoreset state machine, reward, observation, stats)
 template <class E>
 int launch_mj_step(mi_vecenv *v, MjStepPtrs mp) {
+    if (v->wrap_on) return launch_mj_step_wrapped<E>(v, mp);
     const dim3 g(v->grid), b(kBlock);
     const int mode = v->cfg.autoreset_mode;
     mp.extras = nullptr;
@@ -256,7 +299,9 @@ int launch_mj_step(mi_vecenv *v, MjStepPtrs mp) {
     }
 }
 
-// T vector steps with the cooperative physics: per step [sample actions ->] physics -> glue, all on the env's stream
+// T vector steps with the cooperative physics: per step [sample actions ->] physics -> glue, all on the env's stream.  Every MuJoCo kind's rollout
+// takes this form while RepeatAction / StickyAction are on (launch_mj_step_wrapped): a sticky action then replaces the drawn one, whose draws are
+// consumed either way.
 template <class E>
 int launch_mj_rollout_coop(mi_vecenv *v, const RolloutPtrs &p, const ActionStream &as, int T, bool sample, int in_f64, const RolloutExtra &ex) {
     const size_t N = (size_t)v->cfg.num_envs;
@@ -490,7 +535,7 @@ void mi_destroy(mi_vecenv *v) {
     void *ptrs[] = {v->d.state, v->d.meta, v->d.rng, v->d.ep_ret, v->d.ep_len, v->d.blk_count, v->d.blk_ret, v->d_out,
                     v->d_pow2, v->d_act_lane, v->d_act_stage, v->d_actions, v->d_mask, v->d_words, v->d_extras, v->d_act_scratch, v->d_obs_scratch,
                     v->shared.words, v->d_shared_pow2, v->shared.blk_done, v->shared.blk_prefix, v->d_attr, v->d_model, v->wrap.last_action, v->wrap.sticky_word, v->wrap.frames,
-                    v->d_act_ctl, v->d_act_partial, v->d_act_slot, v->d_arg_stage};
+                    v->d_act_ctl, v->d_act_partial, v->d_act_slot, v->d_arg_stage, v->d_wrap_acc, v->d_wrap_inner};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     if (v->h_out) (void)hipHostFree(v->h_out);
@@ -735,7 +780,9 @@ int mi_get_model_derived(mi_vecenv *v, int which, double *host_out) {
 // RepeatAction / StickyAction of the sub-environments (include/mi355env.h mi_set_step_wrappers; device side: lane_step_wrapped).
 int mi_set_step_wrappers(mi_vecenv *v, int num_repeats, double sticky_probability, int sticky_duration) {
     if (!v) return fail(MI_ERR_INVALID_ARGUMENT, "null env");
-    if (v->cfg.kind < 0 || v->cfg.kind >= kClassicKinds) return fail(MI_ERR_UNSUPPORTED, "mi_set_step_wrappers: the five classic-control kinds only");
+    const bool mj = is_mj(v->cfg.kind);  // the MuJoCo kinds: trips of the plain step's launches (launch_mj_step_wrapped)
+    if (!mj && (v->cfg.kind < 0 || v->cfg.kind >= kClassicKinds))
+        return fail(MI_ERR_UNSUPPORTED, "mi_set_step_wrappers: the five classic-control kinds and the eleven MuJoCo kinds only");
     if (v->shared_rng) return fail(MI_ERR_UNSUPPORTED, "mi_set_step_wrappers: not with MI_CFG_SHARED_RNG (CartPoleVectorEnv has no sub-environments to wrap)");
     if (v->cfg.reserved[0] & MI_CFG_FAST_MATH) return fail(MI_ERR_UNSUPPORTED, "mi_set_step_wrappers: not with MI_CFG_FAST_MATH");
     if (v->has_epi) return fail(MI_ERR_UNSUPPORTED, "mi_set_step_wrappers: not with a step epilogue attached (mi_set_step_epilogue)");
@@ -749,16 +796,21 @@ int mi_set_step_wrappers(mi_vecenv *v, int num_repeats, double sticky_probabilit
     if (set_device(v)) return MI_ERR_HIP;
     const size_t N = (size_t)v->cfg.num_envs;
     if (sticky_duration) {
-        if (!v->wrap.last_action) HIP_TRY(hipMalloc(&v->wrap.last_action, sizeof(uint64_t) * N));
+        const size_t last_bytes = sizeof(uint64_t) * N * (mj ? (size_t)v->lay.act_dim : 1);  // (a MuJoCo row: act_dim components at 8 bytes)
+        if (!v->wrap.last_action) HIP_TRY(hipMalloc(&v->wrap.last_action, last_bytes));
         if (!v->wrap.sticky_word) HIP_TRY(hipMalloc(&v->wrap.sticky_word, sizeof(uint32_t) * N));
         // a newly constructed StickyAction: last_action None, not stuck
-        HIP_TRY(hipMemsetAsync(v->wrap.last_action, 0, sizeof(uint64_t) * N, v->stream));
+        HIP_TRY(hipMemsetAsync(v->wrap.last_action, 0, last_bytes, v->stream));
         HIP_TRY(hipMemsetAsync(v->wrap.sticky_word, 0, sizeof(uint32_t) * N, v->stream));
+    }
+    if (mj && (num_repeats > 0 || sticky_duration > 0)) {  // what a row carries from trip to trip; mj_wrap_open_kernel initialises both every step
+        if (!v->d_wrap_acc) HIP_TRY(hipMalloc(&v->d_wrap_acc, sizeof(double) * N));
+        if (!v->d_wrap_inner) HIP_TRY(hipMalloc(&v->d_wrap_inner, sizeof(uint32_t) * N));
     }
     v->wrap.repeats = num_repeats, v->wrap.sticky_duration = sticky_duration, v->wrap.sticky_p = sticky_duration ? sticky_probability : 0.0;
     v->wrap_on = num_repeats > 0 || sticky_duration > 0 || v->wrap.skip > 0;
     v->wrap_act_kind = -1;
-    if (v->wrap_on) v->per_lane = true;
+    if (v->wrap_on && !mj) v->per_lane = true;
     return MI_OK;
 }
 
@@ -1451,6 +1503,7 @@ static int rollout_impl(mi_vecenv *v, int T, const mi_rollout_io *io, const Roll
         rc = dispatch_mj(v->cfg.kind, [&](auto env) -> int {
             using E = decltype(env);
             const RolloutExtra e = ex ? *ex : RolloutExtra{};
+            if (v->wrap_on) return launch_mj_rollout_coop<E>(v, p, as, T, sample, in_f64, e);
             if (v->d_model) {
                 if (!((v->model_mask & (1u << MI_MODEL_BODY_MASS_SCALE)) ? mi_mjmass::rollout : mi_mjmodel::rollout)(v->cfg.kind, v->cfg.autoreset_mode, sample, v->grid, v->stream, v->d, p, as, T, v->lay.obs_dim, in_f64, e))
                     return fail(MI_ERR_UNSUPPORTED, "no per-lane-model kernel for this env kind");

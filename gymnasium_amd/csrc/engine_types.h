@@ -90,6 +90,17 @@ struct WrapSkipDev : WrapDev {
 };
 template <bool MAXSKIP>
 using WrapArg = std::conditional_t<MAXSKIP, WrapSkipDev, WrapDev>;
+// The same two wrappers for the MuJoCo kinds (mj_wrapped_kernels.h): an outer step is `repeats` trips of the plain step's launches, and what a row
+// carries from trip to trip lives here.  Everything but the arrays is grid-uniform.
+struct MjWrapDev {
+    int repeats, sticky_duration;  // as WrapDev
+    double sticky_p;
+    void *last_action;      // [N][NU] StickyAction.last_action in the element type of the action rows (allocated at 8 bytes per component); after
+                            // mj_wrap_open_kernel it IS the effective action row of the step, which the trips read.  NULL without StickyAction
+    uint32_t *sticky_word;  // [N] as WrapDev::sticky_word
+    double *acc;            // [N] RepeatAction's total_reward of the outer step in flight
+    uint32_t *inner;        // [N] inner-step word: bit 31 the row sits the remaining trips out (the cooperative physics kernel's `meta`), bits 0..30 inner steps taken
+};
 }  // namespace mi_internal
 using namespace mi_internal;
 namespace {
@@ -185,6 +196,9 @@ int shared_recount(mi_vecenv *v);
 // false: a kind the unit does not hold.
 namespace mi_mjmodel {
 bool step(int kind, int autoreset_mode, int grid, hipStream_t stream, const mi_internal::DevEnv &d, const void *mj_step_ptrs);
+// mj_trip_kernel (mj_wrapped_kernels.h) over the same env types: trip `trip` of an outer step with RepeatAction / StickyAction on (mi_set_step_wrappers)
+bool step_wrapped(int kind, int autoreset_mode, int trip, int grid, hipStream_t stream, const mi_internal::DevEnv &d, const void *mj_step_ptrs,
+                  const mi_internal::MjWrapDev &w);
 // load the unit's code object on the current device now (kernels load on first use, which a stream capture must not trigger)
 bool preload(int kind);
 bool rollout(int kind, int autoreset_mode, bool sample, int grid, hipStream_t stream, const mi_internal::DevEnv &d, const mi_internal::RolloutPtrs &p,
@@ -195,6 +209,8 @@ bool rollout(int kind, int autoreset_mode, bool sample, int grid, hipStream_t st
 // without the mass rows.
 namespace mi_mjmass {
 bool step(int kind, int autoreset_mode, int grid, hipStream_t stream, const mi_internal::DevEnv &d, const void *mj_step_ptrs);
+bool step_wrapped(int kind, int autoreset_mode, int trip, int grid, hipStream_t stream, const mi_internal::DevEnv &d, const void *mj_step_ptrs,
+                  const mi_internal::MjWrapDev &w);
 bool preload(int kind);  // (the constants kernel included)
 bool rollout(int kind, int autoreset_mode, bool sample, int grid, hipStream_t stream, const mi_internal::DevEnv &d, const mi_internal::RolloutPtrs &p,
              const mi_internal::ActionStream &as, int T, int obs_dim, int in_f64, const mi_internal::RolloutExtra &ex);
@@ -316,6 +332,9 @@ struct mi_vecenv {
     WrapSkipDev wrap;
     bool wrap_on, per_lane;
     int wrap_act_kind;  // StickyAction: the element type of the action rows it has seen (last_action is kept in that type); -1: none yet
+    // ... of a MuJoCo env (MjWrapDev; wrap.last_action is then [N][NU] at 8 bytes per component): the reward accumulator and the inner-step word of every row
+    double *d_wrap_acc;
+    uint32_t *d_wrap_inner;
     // sample(mask=...) / sample(probability=...) on the action stream (action_mask.hip): the pending 32-bit half and the words of the batch in flight,
     // the per-workgroup counts, the per-row slots; d_arg_stage: where a host caller's masks / probabilities are staged (MI_HOST only)
     mi_actmask::Ctl *d_act_ctl;

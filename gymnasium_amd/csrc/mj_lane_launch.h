@@ -1,9 +1,10 @@
-// mj_lane_launch.h -- the launchers of the one-lane MuJoCo kernels (mj_glue_kernels.h) over the env types of one per-lane model template:
+// mj_lane_launch.h -- the launchers of the one-lane MuJoCo kernels (mj_glue_kernels.h, mj_wrapped_kernels.h) over the env types of one per-lane model template:
 // mjx::LaneModel (mjx_model.hip, namespace mi_mjmodel) or mjx::MassLaneModel (mjx_mass_model.hip, namespace mi_mjmass).  Each of the two units
 // instantiates the kernels it launches; engine_types.h declares the plain functions engine.hip calls.
 #ifndef MI355ENV_MJ_LANE_LAUNCH_H
 #define MI355ENV_MJ_LANE_LAUNCH_H
 #include "mj_glue_kernels.h"
+#include "mj_wrapped_kernels.h"
 
 namespace {
 template <template <class> class LM>
@@ -46,6 +47,11 @@ struct MjLaneLaunch {
             default: hipLaunchKernelGGL((mj_step_kernel<E, MI_AUTORESET_DISABLED, false>), g, b, 0, stream, d, mp); break;
             }
         });
+    }
+    // trip `trip` of an outer step with RepeatAction / StickyAction on (mj_wrapped_kernels.h)
+    static bool step_wrapped(int kind, int mode, int trip, int grid, hipStream_t stream, const DevEnv &d, const void *mj_step_ptrs, const MjWrapDev &w) {
+        const MjStepPtrs mp = *static_cast<const MjStepPtrs *>(mj_step_ptrs);
+        return dispatch(kind, [&](auto env) { hipLaunchKernelGGL((mj_trip_kernel<decltype(env), false>), dim3(grid), dim3(kBlock), 0, stream, d, mp, w, mode, trip); });
     }
     static bool reset(int kind, int grid, hipStream_t stream, const DevEnv &d, const uint8_t *mask, double *obs, int obs_dim) {
         return dispatch(kind, [&](auto env) { hipLaunchKernelGGL((mj_reset_kernel<decltype(env)>), dim3(grid), dim3(kBlock), 0, stream, d, mask, obs, obs_dim); });

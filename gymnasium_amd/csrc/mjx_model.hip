@@ -9,6 +9,9 @@ namespace mi_mjmodel {
 typedef MjLaneLaunch<mjx::LaneModel> Launch;
 bool preload(int kind) { return Launch::preload(kind); }
 bool step(int kind, int mode, int grid, hipStream_t stream, const DevEnv &d, const void *mj_step_ptrs) { return Launch::step(kind, mode, grid, stream, d, mj_step_ptrs); }
+bool step_wrapped(int kind, int mode, int trip, int grid, hipStream_t stream, const DevEnv &d, const void *mj_step_ptrs, const MjWrapDev &w) {
+    return Launch::step_wrapped(kind, mode, trip, grid, stream, d, mj_step_ptrs, w);
+}
 bool rollout(int kind, int mode, bool sample, int grid, hipStream_t stream, const DevEnv &d, const RolloutPtrs &p, const ActionStream &as, int T, int obs_dim,
              int in_f64, const RolloutExtra &ex) {
     return Launch::rollout(kind, mode, sample, grid, stream, d, p, as, T, obs_dim, in_f64, ex);

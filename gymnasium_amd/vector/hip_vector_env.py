@@ -1091,8 +1091,17 @@ class HipVectorEnv(VectorEnv):
     # -- RepeatAction / StickyAction of the sub-environments (gymnasium_amd.wrappers.RepeatAction / StickyAction; mi_set_step_wrappers) ------
     _step_wrappers = (0, 0.0, 0)  # (num_repeats, sticky probability, sticky duration) the engine runs; 0 = no such wrapper
 
+    _MUJOCO_KINDS = ("half_cheetah", "ant", "humanoid", "humanoid_standup", "hopper", "walker2d", "inverted_pendulum", "inverted_double_pendulum",
+                     "reacher", "pusher", "swimmer")
+
     def _step_wrappers_refusal(self) -> str | None:
-        if self.KIND not in ("cartpole", "pendulum", "acrobot", "mountain_car", "mountain_car_continuous"):
+        # the eleven MuJoCo ids: trips of the plain step's launches, in the product engine (a backend without the entry point has no such step)
+        has_entry = hasattr(getattr(self._engine, "lib", None), "set_step_wrappers")
+        mujoco = self.KIND in self._MUJOCO_KINDS and has_entry
+        if not mujoco and self.KIND not in ("cartpole", "pendulum", "acrobot", "mountain_car", "mountain_car_continuous"):
+            if has_entry:
+                return (f"{type(self).__name__}: RepeatAction / StickyAction of the sub-environments exist for the five classic-control ids and the "
+                        "eleven MuJoCo v5 ids only (the ToyText kernels have no such step)")
             return (f"{type(self).__name__}: RepeatAction / StickyAction of the sub-environments exist for CartPole-v1, Pendulum-v1, Acrobot-v1, "
                     "MountainCar-v0 and MountainCarContinuous-v0 only (the MuJoCo and ToyText kernels have no such step)")
         if getattr(self, "_shared_rng", False):

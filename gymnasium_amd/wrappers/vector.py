@@ -275,8 +275,8 @@ _InvalidBound = getattr(error, "InvalidBound", error.Error)
 def _bare_env(env, what):
     """``env`` if it is a HipVectorEnv with nothing around it; error.Error otherwise."""
     if isinstance(env, VectorWrapper) or not hasattr(env, "set_step_wrappers"):
-        raise error.Error(f"{what} wraps every SUB-environment, below the vector level: it goes directly over the classic-control HipVectorEnv "
-                          f"(gymnasium_amd.make_vec(...)), and the vector wrappers go above it; got {type(env).__name__}")
+        raise error.Error(f"{what} wraps every SUB-environment, below the vector level: it goes directly over the HipVectorEnv "
+                          f"(gymnasium_amd.make_vec(...) of a classic-control or MuJoCo id), and the vector wrappers go above it; got {type(env).__name__}")
     return env
 
 
@@ -285,8 +285,12 @@ class RepeatAction(VectorWrapper):
     reference has no vector version): a ``step()`` runs up to ``num_repeats`` inner steps of every sub-environment with the same action IN ONE
     LAUNCH -- a sub-environment stops after the inner step that terminates or truncates it (TimeLimit counts inner steps) while its neighbours
     go on --, returns the last inner observation and ``0.0 + r1 + r2 ...``.  Episode statistics count what the vector level sees: one step
-    per ``step()``.  The NEXT_STEP autoreset step repeats nothing.  Goes directly over the env of the five classic-control ids;
-    ``StickyAction`` may go over it, every vector wrapper goes above both.  ``step``, ``step(None)``, ``rollout`` and ``capture_steps`` all follow."""
+    per ``step()``.  The NEXT_STEP autoreset step repeats nothing.  Goes directly over the env of the five classic-control ids or the eleven
+    MuJoCo v5 ids; ``StickyAction`` may go over it, every vector wrapper goes above both.  ``step``, ``step(None)``, ``rollout`` and ``capture_steps``
+    all follow.  Over a MuJoCo id a ``step()`` is a series of launches on the env's stream instead of one -- an opening kernel, then ``num_repeats``
+    trips of the plain step's launches, nothing synchronised in between (docs/mujoco_design.md) --, a finished sub-environment sits the remaining
+    trips out, and the observation and the info entries (``x_position``, ``reward_ctrl``, ...; ``final_info`` under SAME_STEP) are the last executed
+    inner step's."""
 
     def __init__(self, env, num_repeats: int):
         if not np.issubdtype(type(num_repeats), np.integer):
@@ -347,7 +351,11 @@ class StickyAction(VectorWrapper):
     ``MaxAndSkipObservation`` (one decision per outer step); every vector wrapper goes above.  Two deliberate differences: actions are validated as given (the reference never looks at an
     action that a sticky one replaces), and the element type of the action batch (float32 / float64 rows) must not change between steps.
     ``repeat_action_duration`` is an int: a (low, high) range is drawn by ``Generator.integers`` from PCG64's buffered 32-bit half, which the
-    sub-environments' generators on the device do not carry -- refused, not approximated."""
+    sub-environments' generators on the device do not carry -- refused, not approximated.
+    Over the eleven MuJoCo v5 ids likewise (directly over the env or over ``RepeatAction``): the decision is taken by a small kernel that opens the
+    step, before anything else the sub-environment's generator does in it; the MuJoCo kinds validate no action.  The engine keeps a COPY of every
+    sub-environment's last action row; the reference keeps a view of the caller's batch, so overwriting that batch in place between steps changes the
+    reference's sticky action and not this one's."""
 
     def __init__(self, env, repeat_action_probability: float, repeat_action_duration=1):
         if not 0 <= repeat_action_probability < 1:

@@ -481,8 +481,8 @@ int mi_get_model_derived(mi_vecenv *env, int which, double *host_out);
  * The per-sub-environment action wrappers (added to ABI 10, which it leaves as it is): gymnasium.wrappers.RepeatAction and StickyAction
  * (wrappers/stateful_action.py:16-220) around every scalar env, outside its TimeLimit -- what
  * make_vec(id, n, "sync", wrappers=(lambda e: StickyAction(RepeatAction(e, k), p, d),)) builds -- for the five classic-control kinds (not with
- * MI_CFG_SHARED_RNG or MI_CFG_FAST_MATH, not with a step epilogue attached).  They live below the vector level, so the engine steps each lane
- * differently; mi_step, mi_rollout and mi_rollout_infos all follow, in one launch as before.
+ * MI_CFG_SHARED_RNG or MI_CFG_FAST_MATH, not with a step epilogue attached) and the eleven MuJoCo kinds (below).  They live below the vector level, so
+ * the engine steps each lane differently; mi_step, mi_rollout and mi_rollout_infos all follow, for the classic kinds in one launch as before.
  *   num_repeats >= 1: RepeatAction(env, num_repeats).  A step runs up to num_repeats inner steps with the same action and stops after the first that
  *     terminates or truncates; reward = 0.0 + r_1 + r_2 ... in that order; obs (and final_obs under SAME_STEP) is the last inner step's; TimeLimit
  *     counts INNER steps.  The NEXT_STEP autoreset step repeats nothing.  episode_return / episode_length and mi_stats count what the vector level
@@ -500,6 +500,20 @@ int mi_get_model_derived(mi_vecenv *env, int which, double *host_out);
  * mi_get_state / mi_set_state do not carry it.  Actions are validated as given (stricter than the reference, which never sees an action that a
  * sticky one replaces); mi_rollout's actions_out are the policy's actions, not the effective ones.  With StickyAction on, the element type of the
  * action rows (mi_step_io.actions_dtype) must not change from call to call: MI_ERR_UNSUPPORTED.
+ * The MuJoCo kinds (both kernel paths, MI_CFG_SOLVER_NEWTON, float32 and float64 action rows, with or without mi_set_model_field, set before or after
+ * this call): the same semantics, float64 observations, the info row (and final_info under SAME_STEP) of the last executed inner step.  One call of
+ * mi_step is a series of launches on the env's stream with no synchronisation between them: a small kernel that takes every row's sticky decision (the
+ * draw from the row's generator, before anything else that generator does in the step) and leaves the effective action row, then num_repeats trips
+ * of what the plain step launches ([cooperative physics ->] glue).  A row that terminated or was truncated inside the repeat, or that is in its
+ * NEXT_STEP autoreset step, sits the remaining trips out, the cooperative physics included; its outputs, episode bookkeeping and mi_stats are
+ * written by the trip in which it finishes.  mi_rollout / mi_rollout_infos are then a host loop over the T steps on the stream (the form the
+ * cooperative kinds' rollout always had): sampled actions are drawn first, a sticky action replaces the drawn one, the draw is consumed either way.
+ * The state -- the sticky word, the last action row ([num_envs][act_dim] at 8 bytes per component, which after the opening kernel IS the effective
+ * row), a reward accumulator and an inner-step word per row -- is device memory allocated by this call; nothing of it appears in mi_get_state, whose
+ * flag bits are the two they were.  The env stays on its plain kernels: with (0, any, 0) mi_step launches exactly what it launched before.  Actions are
+ * not validated (these kinds never validate a Box action).  The engine keeps a COPY of the last action row; the reference keeps a view of the
+ * caller's batch, so a caller that overwrites that batch in place changes the reference's sticky action and not this one's.  mi_set_max_and_skip stays
+ * with the classic kinds.
  */
 int mi_set_step_wrappers(mi_vecenv *env, int num_repeats, double sticky_probability, int sticky_duration);
 
