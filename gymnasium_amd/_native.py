@@ -60,6 +60,9 @@ HOST_SYMBOLS += ["model_field_width", "set_model_field", "get_model_field"]
 MODEL_GRAVITY, MODEL_ACTUATOR_GEAR, MODEL_DOF_DAMPING, MODEL_PAIR_FRICTION = 0, 1, 2, 3  # MI_MODEL_*
 # ... and the body mass scale with the constants the engine derives from it on the device (mi_get_model_derived; added to ABI 10 as well).
 HOST_SYMBOLS += ["get_model_derived"]
+# The return of K candidate action sequences from every sub-environment's present state (mi_lookahead; added to ABI 10, which it leaves as it is): product
+# library only -- HipVectorEnv.lookahead tells the backends apart by whether the entry point is bound.
+HOST_SYMBOLS += ["lookahead"]
 MODEL_BODY_MASS_SCALE = 4
 MODEL_DERIVED_DOF_INVWEIGHT0, MODEL_DERIVED_BODY_INVWEIGHT0, MODEL_DERIVED_MEANINERTIA = 0, 1, 2  # MI_MODEL_DERIVED_*
 WRAPPER_SYMBOLS = ["rms_create", "rms_destroy", "rms_get", "rms_set", "normalize_observation", "normalize_reward", "clip_reward", "set_step_epilogue"]
@@ -108,6 +111,13 @@ class MiRolloutIO(C.Structure):
 class MiRolloutExtra(C.Structure):
     _fields_ = [("final_obs", C.c_void_p), ("episode_return", C.c_void_p), ("episode_length", C.c_void_p), ("info", C.c_void_p),
                 ("final_info", C.c_void_p)]
+
+
+class MiLookaheadIO(C.Structure):
+    """mi_lookahead_io (include/mi355env.h): device pointers; every output nullable."""
+    _fields_ = [("struct_size", C.c_int32), ("actions_dtype", C.c_int32), ("actions", C.c_void_p), ("returns", C.c_void_p), ("steps", C.c_void_p),
+                ("terminated", C.c_void_p), ("truncated", C.c_void_p), ("final_obs", C.c_void_p), ("horizon", C.c_int32), ("candidates", C.c_int32),
+                ("gamma", C.c_double)]
 
 
 class MiTabularTable(C.Structure):
@@ -246,6 +256,10 @@ class NativeLib:
                 self.get_model_field = f("get_model_field", [vp, i32, vp], i32)
                 self.get_model_derived = f("get_model_derived", [vp, i32, vp], i32)
             except ImportError:  # (likewise: set_attr on a MuJoCo env refuses)
+                pass
+            try:
+                self.lookahead = f("lookahead", [vp, C.POINTER(MiLookaheadIO)], i32)
+            except ImportError:  # (likewise: HipVectorEnv.lookahead refuses)
                 pass
 
     def _fn(self, name, argtypes, restype):
@@ -489,6 +503,15 @@ class Engine:
         for name, _ in MiRolloutExtra._fields_:
             setattr(ex, name, _ptr(extra.get(name)))
         self.lib.check(self.lib.rollout_infos(self.handle, int(T), C.byref(io), C.byref(ex)))
+
+    def lookahead(self, actions, horizon: int, candidates: int, gamma: float, returns=None, steps=None, terminated=None, truncated=None, final_obs=None,
+                  actions_dtype=MI_F32):
+        """mi_lookahead: device addresses; actions [horizon][candidates][num_envs][act_dim], every output [candidates][num_envs][...] or None."""
+        io = MiLookaheadIO()
+        io.struct_size, io.actions_dtype, io.actions = C.sizeof(MiLookaheadIO), int(actions_dtype), _ptr(actions)
+        io.returns, io.steps, io.terminated, io.truncated, io.final_obs = _ptr(returns), _ptr(steps), _ptr(terminated), _ptr(truncated), _ptr(final_obs)
+        io.horizon, io.candidates, io.gamma = int(horizon), int(candidates), float(gamma)
+        self.lib.check(self.lib.lookahead(self.handle, C.byref(io)))
 
     def stats(self) -> dict:
         st = MiStats()

@@ -1548,6 +1548,29 @@ int mi_rollout_infos(mi_vecenv *v, int T, const mi_rollout_io *io, const mi_roll
     return rollout_impl(v, T, io, &ex);
 }
 
+// The return of K candidate action sequences from every sub-environment's present state (include/mi355env.h mi_lookahead; device side: lookahead.hip).
+int mi_lookahead(mi_vecenv *v, const mi_lookahead_io *io) {
+    if (!v || !io) return fail(MI_ERR_INVALID_ARGUMENT, "null argument");
+    if (io->struct_size != (int32_t)sizeof(mi_lookahead_io)) return fail(MI_ERR_INVALID_ARGUMENT, "mi_lookahead: struct_size != sizeof(mi_lookahead_io)");
+    if (v->cfg.kind < 0 || v->cfg.kind >= kClassicKinds) return fail(MI_ERR_UNSUPPORTED, "mi_lookahead: the five classic-control kinds only");
+    if (v->shared_rng) return fail(MI_ERR_UNSUPPORTED, "mi_lookahead: not with MI_CFG_SHARED_RNG (CartPoleVectorEnv has no sub-environment generators to copy)");
+    if (v->cfg.reserved[0] & MI_CFG_FAST_MATH) return fail(MI_ERR_UNSUPPORTED, "mi_lookahead: not with MI_CFG_FAST_MATH");
+    if (v->wrap_on) return fail(MI_ERR_UNSUPPORTED, "mi_lookahead: not with mi_set_step_wrappers / mi_set_max_and_skip on");
+    if (v->has_epi) return fail(MI_ERR_UNSUPPORTED, "mi_lookahead: not with a step epilogue attached (mi_set_step_epilogue)");
+    if (v->has_pending) return fail(MI_ERR_STATE, "an asynchronous step is pending (mi_step_wait)");
+    if (!v->was_reset) return fail(MI_ERR_STATE, "lookahead before reset");
+    if (!io->actions) return fail(MI_ERR_INVALID_ARGUMENT, "mi_lookahead: actions must not be NULL");
+    if (io->horizon < 1 || io->candidates < 1) return fail(MI_ERR_INVALID_ARGUMENT, "mi_lookahead: horizon and candidates must be >= 1");
+    if ((int64_t)io->candidates * (int64_t)v->cfg.num_envs >= ((int64_t)1 << 31)) return fail(MI_ERR_INVALID_ARGUMENT, "mi_lookahead: candidates * num_envs must be < 2^31");
+    if (!(io->gamma >= 0.0 && io->gamma <= 1.0)) return fail(MI_ERR_INVALID_ARGUMENT, "mi_lookahead: gamma must be in [0, 1]");
+    const bool box = v->lay.act_dtype == MI_F32;
+    if (box && io->actions_dtype != MI_F32 && io->actions_dtype != MI_F64 && io->actions_dtype != MI_F64_WEAK)
+        return fail(MI_ERR_INVALID_ARGUMENT, "actions_dtype must be MI_F32, MI_F64 or MI_F64_WEAK");
+    if (set_device(v)) return MI_ERR_HIP;
+    return mi_lookahead_unit::launch(v, io->actions, box ? io->actions_dtype : (int)MI_F32, io->horizon, io->candidates, io->gamma, io->returns, io->steps, io->terminated,
+                                io->truncated, static_cast<float *>(io->final_obs));
+}
+
 int mi_action_sample(mi_vecenv *v, int T, void *out, int loc) {
     if (!v) return fail(MI_ERR_INVALID_ARGUMENT, "null env");
     if (T < 0 || (T > 0 && !out)) return fail(MI_ERR_INVALID_ARGUMENT, "mi_action_sample: T >= 0 batches into a non-null array");

@@ -1,4 +1,4 @@
-// engine_types.h -- what the engine's units (engine.hip, classic.hip, mjx_model.hip and mjx_mass_model.hip) agree on: the
+// engine_types.h -- what the engine's units (engine.hip, classic.hip, lookahead.hip, mjx_model.hip and mjx_mass_model.hip) agree on: the
 // constants of the lane's flag word, the plain structs that ride in kernel arguments and in mi_vecenv, the handle itself, the launch functions one
 // unit defines and another calls, and the error helpers of the host side.  No kernel and no device function lives here.
 #ifndef MI355ENV_ENGINE_TYPES_H
@@ -189,6 +189,13 @@ int shared_step(mi_vecenv *v, const mi_internal::StepPtrs &p);
 int shared_rollout(mi_vecenv *v, const mi_internal::RolloutPtrs &p, const mi_internal::ActionStream &as, int T, bool sample, const mi_internal::RolloutExtra *ex = nullptr);
 int shared_recount(mi_vecenv *v);
 }  // namespace mi_classic
+// mi_lookahead's kernels behind a plain launch function (defined in lookahead.hip, called from engine.hip once the arguments are validated):
+// lookahead_kernel<E> of the env's kind, its per-lane type when the env is on those, and the element type of the action rows.  Device pointers;
+// every output nullable.  (mi_lookahead_unit: `mi_lookahead` itself is the C entry point's name.)
+namespace mi_lookahead_unit {
+int launch(mi_vecenv *v, const void *actions, int act_kind, int horizon, int candidates, double gamma, double *returns, int32_t *steps, uint8_t *terminated,
+           uint8_t *truncated, float *final_obs);
+}  // namespace mi_lookahead_unit
 // The one-lane MuJoCo kernels of an env with per-sub-environment model fields (mi_set_model_field) -- mj_step_kernel and mj_rollout_kernel over
 // mjx::LaneModel env types -- behind plain launch functions: they are instantiated in a translation unit of their own (mjx_model.hip),
 // which compiles side by side with the others.  `mj_step_ptrs` is an MjStepPtrs -- a type of the unnamed namespace, whose name is

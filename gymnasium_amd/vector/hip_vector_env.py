@@ -936,6 +936,92 @@ class HipVectorEnv(VectorEnv):
                 self._episode_count_t.add_(dones.sum())
         return infos
 
+    # -- lookahead: candidate action sequences scored from the present state (mi_lookahead) --------------------------------------------------
+    _CLASSIC_KINDS = ("cartpole", "pendulum", "acrobot", "mountain_car", "mountain_car_continuous")
+
+    def _lookahead_refusal(self) -> str | None:
+        if self.output != "torch":
+            return "lookahead() takes and returns device tensors; create the env with output='torch'"
+        if self.KIND not in self._CLASSIC_KINDS:
+            return (f"{type(self).__name__}: lookahead exists for CartPole-v1, Pendulum-v1, Acrobot-v1, MountainCar-v0 and MountainCarContinuous-v0 "
+                    "only (the MuJoCo and ToyText kernels have no such loop)")
+        if getattr(self, "_shared_rng", False):
+            return "rng='shared' is the reference's NumPy CartPoleVectorEnv: it has no sub-environment generators that a candidate could copy"
+        if getattr(self, "fast_math", False):
+            return "lookahead runs the exact kernels only: not with fast_math=True"
+        if self._step_wrappers != (0, 0.0, 0):
+            return "this env runs RepeatAction / StickyAction inside its step (set_step_wrappers): lookahead steps the plain env"
+        if self._max_and_skip:
+            return "this env runs MaxAndSkipObservation inside its step (set_max_and_skip): lookahead steps the plain env"
+        st = self.__dict__.get("_fused")
+        if st is not None and st["chain"]:
+            return "vector wrappers are fused into this env's step kernel: lookahead returns the plain env's rewards and observations"
+        return None
+
+    def lookahead(self, actions, gamma: float = 1.0, *, final_obs: bool = False) -> dict:
+        """Score ``K`` candidate action sequences of length ``H`` for every sub-environment from its PRESENT state, in one kernel launch, without
+        touching the env: what a sampling planner (random shooting, CEM, MPPI) asks of a model.
+
+        ``actions``: ``[H, K, N]`` int64 for the Discrete ids, ``[H, K, N, act_dim]`` float32 or float64 for the Box ids (a trailing
+        ``act_dim`` of 1 may be omitted; float64 rows go in un-rounded, as in ``step()``).  Candidate ``k`` of sub-environment ``i`` steps a private
+        copy of that sub-environment -- state, elapsed steps, ``set_attr`` values, generator -- with ``actions[t, k, i]`` for ``t = 0 .. H - 1`` and stops
+        after the first step that terminates or truncates (``max_episode_steps`` counts from the sub-environment's elapsed steps).
+
+        Returns a dict of device tensors: ``returns`` ``[K, N]`` float64 (``G = 0; disc = 1``; per step ``G = G + disc * r; disc = disc * gamma``,
+        in float64 in that order), ``steps`` ``[K, N]`` int32 (steps taken), ``terminated`` / ``truncated`` ``[K, N]`` bool (of the last step
+        taken) and, with ``final_obs=True``, ``final_obs`` ``[K, N, obs_dim]`` float32 (the observation after the last step taken).  A
+        sub-environment that waits for its autoreset gives return 0, 0 steps, both flags False and its present observation.
+
+        Nothing synchronises.  An action outside a Discrete space is reported like ``step()``'s with device tensors: by a later synchronising call.
+        """
+        self._check_open()
+        self._check_not_pending("lookahead")
+        refusal = self._lookahead_refusal()
+        if refusal:
+            raise error.Error(refusal)
+        if not self._has_reset:
+            raise AssertionError("Call reset before using lookahead.")
+        t, eng, N = self._torch, self._engine, self.num_envs
+        if isinstance(gamma, bool) or not isinstance(gamma, (int, float, np.integer, np.floating)):
+            raise TypeError(f"gamma must be a number, got {type(gamma).__name__}")
+        gamma = float(gamma)
+        if not 0.0 <= gamma <= 1.0:
+            raise ValueError(f"gamma must be in [0, 1], got {gamma}")
+        if isinstance(actions, np.ndarray):
+            actions = t.from_numpy(actions)
+        if not isinstance(actions, t.Tensor):
+            raise TypeError(f"actions must be a tensor, got {type(actions).__name__}")
+        if self._discrete:
+            if actions.dtype != t.int64:
+                raise TypeError(f"actions of {type(self).__name__} must be int64, got {actions.dtype}")
+            want = "[H, K, N]"
+            ok = actions.dim() == 3
+        else:
+            if actions.dtype not in (t.float32, t.float64):
+                raise TypeError(f"actions of {type(self).__name__} must be float32 or float64, got {actions.dtype}")
+            want = f"[H, K, N, {eng.act_dim}]" + (" or [H, K, N]" if eng.act_dim == 1 else "")
+            ok = (actions.dim() == 4 and actions.shape[3] == eng.act_dim) or (actions.dim() == 3 and eng.act_dim == 1)
+        if not ok or actions.shape[2] != N:
+            raise ValueError(f"actions must have shape {want} with N = {N}, got {tuple(actions.shape)}")
+        H, K = int(actions.shape[0]), int(actions.shape[1])
+        if H < 1 or K < 1:
+            raise ValueError(f"lookahead needs H >= 1 and K >= 1, got H = {H}, K = {K}")
+        if K * N >= 2 ** 31:
+            raise ValueError(f"lookahead needs K * N < 2**31, got K = {K}, N = {N}")
+        if not hasattr(getattr(eng, "lib", None), "lookahead"):
+            raise error.Error("lookahead needs the device engine (mi_lookahead): the engine behind this env has no such entry point")
+        self._bind_stream()
+        dev = self._tdev
+        in_dtype = _native.MI_F64 if actions.dtype == t.float64 else _native.MI_F32
+        a = actions.to(device=dev).contiguous()
+        out = {"returns": t.empty((K, N), dtype=t.float64, device=dev), "steps": t.empty((K, N), dtype=t.int32, device=dev),
+               "terminated": t.empty((K, N), dtype=t.bool, device=dev), "truncated": t.empty((K, N), dtype=t.bool, device=dev)}
+        if final_obs:
+            out["final_obs"] = t.empty((K, N) + tuple(self._obs_shape[1:]), dtype=self._obs_tdtype, device=dev)
+        eng.lookahead(a.data_ptr(), H, K, gamma, out["returns"].data_ptr(), out["steps"].data_ptr(), out["terminated"].data_ptr(),
+                      out["truncated"].data_ptr(), out["final_obs"].data_ptr() if final_obs else None, actions_dtype=in_dtype)
+        return out  # (a converted copy `a` is the caching allocator's on torch's stream, which the launch is on: reused in stream order)
+
     # -- HIP graphs ------------------------------------------------------------------------------------
     def capture_steps(self, actions=None, steps: int = 1, policy=None):
         """Capture ``steps`` consecutive ``step()`` calls -- and, with ``policy``, the policy between them -- into ONE HIP graph

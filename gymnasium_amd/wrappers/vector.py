@@ -158,6 +158,11 @@ class VectorWrapper:
         """``num_steps`` consecutive ``step()`` calls through this wrapper at once (HipVectorEnv.rollout): here, the wrapped env's own."""
         return self.env.rollout(num_steps, actions, **kwargs)
 
+    def lookahead(self, actions, gamma=1.0, **kwargs):
+        """Not through a wrapper: the engine scores candidates with the plain env's actions, rewards and observations, which are not this wrapper's."""
+        raise error.Error(f"{type(self).__name__}: lookahead() is not offered through wrappers -- forwarding it would hand back the unwrapped env's rewards "
+                          "and observations as if they were this wrapper's; call env.unwrapped.lookahead(...) if those are what you want")
+
     def _workspace(self, steps, rows, dim):
         """Scratch of the whole-trajectory passes: a tensor from the caching allocator, so that the library neither allocates nor synchronises."""
         lib = _native.load_library()

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-/* Entry points that were only ADDED since (mi_action_sample_masked and its three companions, mi_set_step_wrappers, mi_set_max_and_skip) leave the number where it is: nothing an ABI 10
+/* Entry points that were only ADDED since (mi_action_sample_masked and its three companions, mi_set_step_wrappers, mi_set_max_and_skip, mi_lookahead) leave the number where it is: nothing an ABI 10
  * caller uses changed, and a caller that needs them finds out by looking the symbol up. */
 #define MI355ENV_ABI_VERSION 10
 
@@ -540,6 +540,49 @@ int mi_set_step_wrappers(mi_vecenv *env, int num_repeats, double sticky_probabil
  */
 int mi_set_max_and_skip(mi_vecenv *env, int skip);
 int mi_get_max_and_skip_frames(mi_vecenv *env, float *dst, int on_device);
+
+/*
+ * Lookahead: the discounted return of `candidates` action sequences of length `horizon` for every sub-environment, each started from the
+ * sub-environment's present state, with the env itself left untouched -- what a sampling planner (random shooting, CEM, MPPI) asks of a model.  Added
+ * to ABI 10, which it leaves as it is; the reference has no counterpart: it is K * N copies of the env, set_state, `horizon` steps and a reduction.
+ * The five classic-control kinds on the exact kernels, in every autoreset mode, with or without mi_set_env_attr (each candidate uses the attributes of
+ * its own sub-environment).  Device pointers only; the call enqueues one launch on the env's stream and does not synchronise.
+ *   Candidate k of sub-environment i works on a private copy of the lane -- state, elapsed steps, flags, attributes, generator.  For
+ *   t = 0 .. horizon - 1 it applies actions[t][k][i] with the sequence of mi_step: the validity check, the env's step, elapsed += 1,
+ *   truncated = max_episode_steps > 0 && elapsed >= max_episode_steps.  It stops after the first step that terminates or truncates; later actions
+ *   are ignored.
+ *   actions     in   [horizon][candidates][N][act_dim]  i64 for the Discrete kinds; Box kinds: actions_dtype = MI_F32 rows, or MI_F64 / MI_F64_WEAK
+ *                                                        rows taken un-rounded (mi_step_io.actions_dtype)
+ *   returns     out  [candidates][N] f64     G = 0, disc = 1; per step taken: G = G + disc * reward, disc = disc * gamma -- the product rounded
+ *                                            before the sum, every operation in float64 in that order
+ *   steps       out  [candidates][N] i32     steps taken
+ *   terminated  out  [candidates][N] u8 0/1  of the last step taken
+ *   truncated   out  [candidates][N] u8 0/1  of the last step taken
+ *   final_obs   out  [candidates][N][obs_dim] obs_dtype   the observation after the last step taken
+ *   Every output is nullable (NULL = not wanted).
+ * A sub-environment that waits for its reset (NEXT_STEP after a finished episode, DISABLED likewise) gives returns 0, steps 0, both flags 0 and its
+ * present observation.  ACROBOT with torque_noise_max != 0 draws inside its step: every candidate of sub-environment i draws from a private copy of that
+ * sub-environment's generator, so all of them see the noise the env itself would see next, and the generator does not move.
+ * Nothing of the env changes: state, elapsed steps, flags, generators, the action stream, mi_stats and the episode statistics are what they were.  An
+ * action outside a Discrete space is reported through the sticky error word like mi_step's (the candidate does not move in that step).
+ * MI_ERR_UNSUPPORTED: another kind, MI_CFG_SHARED_RNG, MI_CFG_FAST_MATH, mi_set_step_wrappers / mi_set_max_and_skip on, a step epilogue attached.
+ * MI_ERR_INVALID_ARGUMENT: horizon or candidates < 1, candidates * N >= 2^31, gamma outside [0, 1], actions NULL, a wrong struct_size or actions_dtype.
+ * MI_ERR_STATE: before the first reset, or with an asynchronous step pending.
+ */
+typedef struct mi_lookahead_io {
+    int32_t struct_size;      /* = sizeof(mi_lookahead_io) */
+    int32_t actions_dtype;    /* Box kinds: MI_F32 (0, default), MI_F64 or MI_F64_WEAK; ignored by the Discrete kinds */
+    const void *actions;
+    double *returns;
+    int32_t *steps;
+    uint8_t *terminated;
+    uint8_t *truncated;
+    void *final_obs;
+    int32_t horizon;
+    int32_t candidates;
+    double gamma;
+} mi_lookahead_io;
+int mi_lookahead(mi_vecenv *env, const mi_lookahead_io *io);
 
 /*
  * Stateful vector wrappers as device epilogues of the step path.  All array arguments are DEVICE
