@@ -4,6 +4,7 @@
 // Included by classic.hip only, which instantiates and launches them.
 #ifndef MI355ENV_CLASSIC_KERNELS_H
 #define MI355ENV_CLASSIC_KERNELS_H
+#include "episode_word.h"
 #include "lane_step.h"
 #include "wrappers_internal.h"
 
@@ -588,6 +589,23 @@ struct HasRareHook : std::false_type {};
 template <class E>
 struct HasRareHook<E, std::void_t<decltype(E::RARE_HOOK)>> : std::integral_constant<bool, E::RARE_HOOK> {};
 
+// The env role's bookkeeping cuts, measured per environment like DUO_ACT_AHEAD (envs_classic.h CartPoleT; an env type that does not name one keeps the
+// parent's code): E::DUO_EPISODE_WORD, E::DUO_RAW_FLAGS, E::DUO_ENV_UNROLL
+template <class E, class = void>
+struct DuoEpisodeWord : std::false_type {};
+template <class E>
+struct DuoEpisodeWord<E, std::void_t<decltype(E::DUO_EPISODE_WORD)>> : std::integral_constant<bool, E::DUO_EPISODE_WORD> {};
+template <class E, class = void>
+struct DuoRawFlags : std::false_type {};
+template <class E>
+struct DuoRawFlags<E, std::void_t<decltype(E::DUO_RAW_FLAGS)>> : std::integral_constant<bool, E::DUO_RAW_FLAGS> {};
+template <class E, class = void>
+struct DuoEnvUnroll : std::integral_constant<int, 1> {};
+template <class E>
+struct DuoEnvUnroll<E, std::void_t<decltype(E::DUO_ENV_UNROLL)>> : std::integral_constant<int, E::DUO_ENV_UNROLL> {};
+static_assert(mi_episode_word::kMetaFlagShift == kFlagShift && mi_episode_word::kMetaElapsedMask == kElapsedMask && mi_episode_word::kMetaNeedsReset == kNeedsReset,
+              "episode_word.h restates the layout of `meta`");
+
 // env role: lane_step_fused<E, false> without the episode statistics; `bits`: 1 terminated, 2 truncated, 4 this was the autoreset step
 template <class E>
 MI_DEV void duo_env_step(const DevEnv &d, Lane<E> &L, typename E::Act a, ResetQueue<E> &q, float obs[E::OBS], double &reward, uint32_t &bits) {
@@ -633,6 +651,41 @@ MI_DEV void duo_env_step(const DevEnv &d, Lane<E> &L, typename E::Act a, ResetQu
     bits = (resetting ? 4u : 0u) | ((!resetting && te) ? 1u : 0u) | ((!resetting && tr) ? 2u : 0u);
 }
 
+// ... with the pending-autoreset flag, the TimeLimit counter and the queue's `have` in ONE word (E::DUO_EPISODE_WORD, episode_word.h): `ew` replaces
+// L.flags' kNeedsReset (stripped by the caller for the launch), L.elapsed and q.have; `thr` is mi_episode_word::truncation_threshold(d.max_steps),
+// computed once per launch.  The same decisions from the same integers: every test is one compare of the word (a TimeLimit that is off needs no
+// `max_steps > 0` per step, and `truncated` needs no mask -- the word of an autoreset step is negative).  RAW (E::DUO_RAW_FLAGS): `bits` is the
+// step's own terminated | truncated << 1, and the aux role masks an autoreset step's flags with the pending bit it carries itself.
+template <class E, bool RAW>
+MI_DEV void duo_env_step_word(const DevEnv &d, Lane<E> &L, typename E::Act a, ResetQueue<E> &q, uint32_t &ew, const int32_t thr, float obs[E::OBS], double &reward, uint32_t &bits) {
+    namespace W = mi_episode_word;
+    static_assert(!E::SPLIT_TERMINAL && !E::AUX_REWARD && !E::AUX_DERIVES_FLAGS, "measured for the plain env role only (CartPole)");
+    const bool resetting = W::resetting(ew);
+    const bool refill = W::refill(ew);  // (its `have` needs no update: the autoreset step that refills also empties the queue, step() below)
+    constexpr bool HOOK = HasRareHook<E>::value;
+    if (!HOOK && __builtin_expect(refill, 0)) q.refill();
+    const double (&rs)[E::S] = q.rs;
+    const uint32_t rflags = ResetQueue<E>::reset_flags(L.flags);
+    double rew;
+    bool te;
+    uint32_t sflags = L.flags;
+    if constexpr (HOOK) {
+        E::step_hooked(L.s, sflags, a, d.P, rew, te, L.trig, refill, [&]() __attribute__((always_inline)) {
+            if (refill) q.refill();
+        });
+    } else {
+        E::step(L.s, sflags, a, d.P, rew, te, L.trig);
+    }
+    const bool tr = W::truncated(ew, thr);  // (ONE compare for the flag and for the word: W::raw_flags and W::step, with their common term shared)
+#pragma unroll
+    for (int k = 0; k < E::S; k++) L.s[k] = resetting ? rs[k] : L.s[k];
+    L.flags = resetting ? rflags : sflags;
+    ew = W::advance(ew, te || tr);
+    E::obs(L.s, L.flags, obs, L.trig);
+    reward = resetting ? 0.0 : rew;
+    bits = RAW ? W::flag_bits(te, tr) : ((resetting ? 4u : 0u) | W::flag_bits(!resetting && te, tr));
+}
+
 // ... and the env role of an environment whose aux role derives the observation row and the flags from the state (E::AUX_DERIVES_FLAGS): the same
 // step and autoreset select, then only the state words go over (E::aux_pack) -- no observation conversion, no flag word
 template <class E>
@@ -666,6 +719,8 @@ __global__ __launch_bounds__(kDuoBlock) void rollout_duo_kernel(DevEnv d, Rollou
     constexpr int C = DuoTraits<E>::CHUNK;
     typedef Act ActLds;  // (a byte per Discrete action would save 28 KB of LDS at chunk 8 and costs 1 %: the widening on the env role)
     constexpr bool ACT_AHEAD = E::DUO_ACT_AHEAD;  // the env role requests step k + 1's action while step k runs (measured per environment, envs_classic.h)
+    constexpr bool WORD = DuoEpisodeWord<E>::value, RAW = DuoRawFlags<E>::value;  // the env role's bookkeeping in one word; its flags unmasked (duo_env_step_word)
+    static_assert(!RAW || WORD, "the unmasked flags are duo_env_step_word's");
     __shared__ ActLds sh_act[2][C + (ACT_AHEAD ? 1 : 0)][kBlock];  // (+ one row nobody writes: the env role's request for "the next step's action" after a chunk's last step)
     // what goes from the env role to the aux role: the observation row and a flag word -- or, for the environments whose aux role derives both from
     // the state (E::AUX_DERIVES_FLAGS, envs_classic.h), the state words
@@ -701,18 +756,26 @@ __global__ __launch_bounds__(kDuoBlock) void rollout_duo_kernel(DevEnv d, Rollou
     // env role
     Lane<E> L;
     ResetQueue<E> q;
+    // WORD: pending | elapsed | have (episode_word.h) and the word's truncation threshold.  (Nothing of either for the other environments, not even a dead
+    // `max_steps > 0`: it merges with the live ones of their step and moves them -- their kernels are the parent's, instruction for instruction.)
+    uint32_t ew = 0u;
+    const int32_t ew_thr = WORD ? mi_episode_word::truncation_threshold(d.max_steps) : 0;
     // aux role
     u128 astate = 0;
     double ep_ret = 0.0;
     int32_t ep_len = 0, ep_len_start = 0;  // (ep_len_start: 0 for a sub-environment whose first step is its autoreset step -- that episode was counted when it finished)
     uint32_t n_term = 0;
     uint32_t start_flags = 0;
-    uint32_t aux_elapsed = 0, aux_needs_reset = 0;  // DERIVE: the aux role's own copy of the TimeLimit counter and of the pending-autoreset flag
+    uint32_t aux_elapsed = 0, aux_needs_reset = 0;  // DERIVE: the aux role's own copy of the TimeLimit counter and of the pending-autoreset flag (RAW: of the flag)
     if (active) {
         if (is_env) {
             load_lane<E>(d, i, L);
             q.have = 0u;
             q.rng = load_rng(d, i);
+            if constexpr (WORD) {  // (the flag word's other bits do not change during the launch: they rejoin when `meta` is stored)
+                ew = mi_episode_word::encode((L.elapsed & kElapsedMask) | (L.flags << kFlagShift), 0u);
+                L.flags &= ~kNeedsReset;
+            }
         }
         if (is_book) {
             ep_ret = d.ep_ret[i], ep_len = d.ep_len[i];
@@ -755,17 +818,25 @@ __global__ __launch_bounds__(kDuoBlock) void rollout_duo_kernel(DevEnv d, Rollou
                     //  of the step body -- libm slow paths included -- are 30 KB of instruction cache: measured +5 % against the unrolled form)
                     // (the queue's periodic refill, rollout_kernel's `t % kRefillPeriod == 0`: with chunks that divide the period the test leaves the step loop)
                     constexpr bool REFILL_PER_CHUNK = kRefillPeriod % C == 0;
-                    if (REFILL_PER_CHUNK && ((c * C) & (kRefillPeriod - 1)) == 0 && !q.have) q.refill();
+                    if constexpr (WORD) {
+                        if (REFILL_PER_CHUNK && ((c * C) & (kRefillPeriod - 1)) == 0 && !mi_episode_word::have(ew)) q.refill(), ew = mi_episode_word::with_have(ew);
+                    } else {
+                        if (REFILL_PER_CHUNK && ((c * C) & (kRefillPeriod - 1)) == 0 && !q.have) q.refill();
+                    }
                     // ACT_AHEAD: the action of step k + 1 is requested while step k runs -- the rolled loop otherwise starts every step with an LDS round trip
                     ActLds a_next = sh_act[buf][0][slot];
 #ifdef MI_DUO_ENV_UNROLL  // (A/B builds: scripts/build_variant.py ... -DMI_DUO_ENV_UNROLL=2)
 #pragma unroll MI_DUO_ENV_UNROLL
 #else
-#pragma unroll 1
+#pragma unroll(DuoEnvUnroll<E>::value)  // (1 unless the environment measured otherwise, E::DUO_ENV_UNROLL: CartPole's 131-instruction step, whose rare paths are out of line, takes all 8)
 #endif
                     for (int k = 0; k < C; k++) {
                         const int t = c * C + k;
-                        if (!REFILL_PER_CHUNK && (t & (kRefillPeriod - 1)) == 0 && !q.have) q.refill();
+                        if constexpr (WORD) {
+                            if (!REFILL_PER_CHUNK && (t & (kRefillPeriod - 1)) == 0 && !mi_episode_word::have(ew)) q.refill(), ew = mi_episode_word::with_have(ew);
+                        } else {
+                            if (!REFILL_PER_CHUNK && (t & (kRefillPeriod - 1)) == 0 && !q.have) q.refill();
+                        }
                         const Act a_k = ACT_AHEAD ? (Act)a_next : (Act)sh_act[buf][k][slot];
                         if (ACT_AHEAD) a_next = sh_act[buf][k + 1][slot];
                         if constexpr (DERIVE) {
@@ -787,7 +858,10 @@ __global__ __launch_bounds__(kDuoBlock) void rollout_duo_kernel(DevEnv d, Rollou
 #pragma unroll
                                 for (int j = 0; j < E::AUX_PRE; j++) sh_pre[buf][k][slot][j] = pre[j];
                             }
-                            duo_env_step<E>(d, L, a_k, q, o, rew, bits);
+                            if constexpr (WORD)
+                                duo_env_step_word<E, RAW>(d, L, a_k, q, ew, ew_thr, o, rew, bits);
+                            else
+                                duo_env_step<E>(d, L, a_k, q, o, rew, bits);
                             if constexpr (AUXREW && E::AUX_PRE_SQUARES > 0) bits |= pre_pending << 3;
 #pragma unroll
                             for (int j = 0; j < E::OBS; j++) sh_obs[buf][k][slot][j] = o[j];
@@ -866,7 +940,17 @@ __global__ __launch_bounds__(kDuoBlock) void rollout_duo_kernel(DevEnv d, Rollou
 #pragma unroll
                             for (int j = 0; j < E::OBS; j++) o[j] = sh_obs[buf][k][slot][j];
                             const uint32_t bits = sh_bits[buf][k][slot];
-                            resetting = (bits & 4u) != 0, te = (bits & 1u) != 0, tr = (bits & 2u) != 0;
+                            if constexpr (RAW) {
+                                // the env role's flags as its step raised them (terminated | truncated << 1; truncated is never raised in an autoreset
+                                // step, terminated is the test of a state the reset replaced): this role's own pending bit masks them, and what is
+                                // left is the next step's pending bit -- sync_vector_env.py:277-329 on the flags alone
+                                resetting = aux_needs_reset != 0;
+                                const uint32_t eff = mi_episode_word::effective_flags(aux_needs_reset, bits);
+                                te = (eff & 1u) != 0, tr = (eff & 2u) != 0;
+                                aux_needs_reset = eff;
+                            } else {
+                                resetting = (bits & 4u) != 0, te = (bits & 1u) != 0, tr = (bits & 2u) != 0;
+                            }
                         }
                         double rew;
                         const bool done = te || tr;
@@ -956,7 +1040,8 @@ __global__ __launch_bounds__(kDuoBlock) void rollout_duo_kernel(DevEnv d, Rollou
             // (ep_ret / ep_len belong to the aux role: store_lane without them)
 #pragma unroll
             for (int k = 0; k < E::S; k++) d.state[(size_t)k * d.N + i] = L.s[k];
-            d.meta[i] = (L.elapsed & kElapsedMask) | (L.flags << kFlagShift);
+            if constexpr (WORD) d.meta[i] = mi_episode_word::decode_meta(ew, L.flags), q.have = mi_episode_word::have(ew);
+            else d.meta[i] = (L.elapsed & kElapsedMask) | (L.flags << kFlagShift);
             if (q.have) {  // hand the unconsumed draws back to the env's generator
 #pragma unroll
                 for (int k = 0; k < E::NDRAWS; k++) q.rng.unstep();
@@ -983,7 +1068,8 @@ __global__ __launch_bounds__(kDuoBlock) void rollout_duo_kernel(DevEnv d, Rollou
                     E::aux_unpack(w64, w32, d.P, o, t0);
                     last_done = aux_needs_reset != 0, last_te = last_done && t0;
                 } else {
-                    const uint32_t last_bits = chunks > 0 ? (uint32_t)sh_bits[(chunks - 1) & 1][C - 1][slot] : ((start_flags & kNeedsReset) ? 2u : 0u);
+                    // (RAW: the ring holds the unmasked flags; the masked ones of the last step are this role's pending word)
+                    const uint32_t last_bits = chunks > 0 ? (RAW ? aux_needs_reset : (uint32_t)sh_bits[(chunks - 1) & 1][C - 1][slot]) : ((start_flags & kNeedsReset) ? 2u : 0u);
                     last_done = (last_bits & 3u) != 0, last_te = (last_bits & 1u) != 0;
                 }
                 // DERIVE: the running episode's length is the TimeLimit counter once an autoreset step has zeroed both (they advance together from

@@ -45,6 +45,20 @@ struct TwoPi {
 #ifndef MI_HOT_TRIG
 #define MI_HOT_TRIG true
 #endif
+// The cuts to the two-role CartPole rollout's env role, each with a switch of its own for A/B builds (scripts/build_variant.py ... -DMI_CP_EPISODE_WORD=0);
+// what each is, and what each measured: docs/classic_kernels.md, profiles/duo_env_bookkeeping_ab.txt.
+#ifndef MI_MAIN_RANGE_FABS
+#define MI_MAIN_RANGE_FABS 1  // ExactMathT::in_main_range as one float64 compare
+#endif
+#ifndef MI_CP_EPISODE_WORD
+#define MI_CP_EPISODE_WORD 1  // CartPoleT::DUO_EPISODE_WORD
+#endif
+#ifndef MI_CP_RAW_FLAGS
+#define MI_CP_RAW_FLAGS 0  // CartPoleT::DUO_RAW_FLAGS (measured: no gain over the word alone, off)
+#endif
+#ifndef MI_CP_ENV_UNROLL
+#define MI_CP_ENV_UNROLL 8  // CartPoleT::DUO_ENV_UNROLL (= DUO_CHUNK: no loop left)
+#endif
 
 // Several IEEE quotients by ONE divisor.  The compiler's float64 division is v_div_scale x 2, v_rcp_f64, two Newton steps on the reciprocal (4 FMAs),
 // q0 = a r, e = fma(-b, q0, a), v_div_fmas (= fma(e, r, q0) when nothing was scaled) and v_div_fixup: 11 instructions, one of them a 17-tick
@@ -98,7 +112,13 @@ struct ExactMathT {
     // the two halves of sincos() for a caller that defers the rare case: the short routine of |x| < 0.855469 evaluated unconditionally (its result
     // is only meaningful when in_main_range(x); an index outside the table reads zeros from LDS, no fault), and the test
     static MI_DEV void sincos_main_unchecked(double x, double &s, double &c) { mi_sincos::sincos_main<KASM>(g_trig6, x, s, c); }
+#if MI_MAIN_RANGE_FABS
+    // (0.85546875 is the double whose high word is 0x3feb6000 and whose low word is 0: the same predicate as the integer test of the high word below, a NaN
+    //  fails both -- ONE v_cmp_lt_f64 with |x| as a source modifier instead of v_and + v_mov + a 64-bit integer compare)
+    static MI_DEV bool in_main_range(double x) { return __builtin_fabs(x) < 0.85546875; }
+#else
     static MI_DEV bool in_main_range(double x) { return ((uint32_t)(mi_sincos::bits(x) >> 32) & 0x7fffffffu) < 0x3feb6000u; }
+#endif
     static MI_DEV void sincos_spread(double x, double &s, double &c) { mi_sincos::sincos_bf<false, false, KASM, HOT>(g_trig6, x, s, c); }  // any range, no small-angle short cut
     // for angles the environment wraps or clips (|x| far below 1e8): no hand-over to the platform's huge-argument routine, and lanes
     // spread over all ranges (no wavefront-uniform short cut)
@@ -262,6 +282,16 @@ struct CartPoleT {
     static constexpr bool DUO_ROLLOUT = true;  // engine.hip rollout_duo_kernel (env + aux wavefront per 64 sub-environments): measured +13 %
     static constexpr int DUO_CHUNK = 8;  // steps per phase of the two-role kernel (round 6, after the phase overhead left the wavefronts: +3.0 % over 4; round 4 measured -2.4 %)
     static constexpr bool DUO_ACT_AHEAD = false;  // (profiles/r06_act_prefetch_ab.txt)
+    // The env role's episode bookkeeping (classic_kernels.h duo_env_step_word): pending autoreset, TimeLimit counter and the reset queue's `have` in ONE
+    // word (episode_word.h) instead of three registers ...
+    static constexpr bool DUO_EPISODE_WORD = MI_CP_EPISODE_WORD;
+    // ... whose flag word for the aux role could then be the step's own `terminated | truncated << 1`, the aux role carrying the pending bit itself and
+    // masking an autoreset step's flags (the recurrence AUX_DERIVES_FLAGS uses for MountainCar): measured, no gain over the word alone -- off
+    // (docs/rejected_experiments.md)
+    static constexpr bool DUO_RAW_FLAGS = DUO_EPISODE_WORD && MI_CP_RAW_FLAGS;
+    // copies of the step in the env role's chunk loop; DUO_CHUNK: no loop, no ring pointers to advance (with the shorter step measured a gain, where round 7's
+    // unroll by 2 of the longer one had lost 0.3 %: docs/classic_kernels.md)
+    static constexpr int DUO_ENV_UNROLL = MI_CP_ENV_UNROLL;
     // the reward of a (non-reset) step is a function of its terminated flag (step(), below): the aux role recomputes it instead of receiving it
     static constexpr bool REWARD_FROM_TERMINATED = true;
     static MI_DEV double reward_from_terminated(bool terminated, const EnvParams &P) {
