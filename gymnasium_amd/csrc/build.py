@@ -13,8 +13,8 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 # The translation units, each compiled on its own and linked into one library; what a unit is and why it is one stands at its head.  A unit's
 # dependencies are the quoted includes it reaches (includes()), so there is no header list to keep.
-SOURCES = ["engine.hip", "physics16.hip", "physics32.hip", "wrappers.hip", "classic.hip", "mjx_model.hip", "mjx_mass_model.hip", "action_mask.hip", "action_wrappers.hip",
-           "observation_wrappers.hip", "per_env_normalize.hip", "stateful_observation.hip", "discretize.hip", "lookahead.hip"]
+SOURCES = ["engine.hip", "physics16.hip", "physics32.hip", "wrappers.hip", "classic.hip", "mujoco.hip", "tabular.hip", "mjx_model.hip", "mjx_mass_model.hip", "action_mask.hip",
+           "action_wrappers.hip", "observation_wrappers.hip", "per_env_normalize.hip", "stateful_observation.hip", "discretize.hip", "lookahead.hip"]
 OUT = os.path.join(HERE, "libmi355env.so")
 ARCH = "gfx950"
 # Per translation unit, on top of FLAGS: LLVM's iterative GCN scheduler for the cooperative physics kernels.  With ONE wavefront per SIMD it
@@ -23,7 +23,8 @@ ARCH = "gfx950"
 # env-steps, every bit of the state) -- PROVIDED the RK4 stage update stays out of line (mjx_coop.h rk4_stage): inlined, the 16-lane Ant instantiation is
 # miscompiled (round 2: wrong results under the iterative scheduler; round 3: a memory fault under the DEFAULT scheduler; stand-alone reproducer and the
 # mechanism -- SGPR spills into VGPR lanes -- in scripts/repro/README.md, profiles/r03_rk4_inline.txt).
-# engine.hip stays on the default scheduler: built with iterative-maxocc its one-lane Humanoid kernel diverged.
+# mujoco.hip (the one-lane kernels over the stock models, engine.hip's until they became a unit) stays on the default scheduler: built with
+# iterative-maxocc its one-lane Humanoid kernel diverged.
 ITERATIVE = ["-mllvm", "-amdgpu-sched-strategy=iterative-maxocc"]
 # ... and MachineLICM told to sink loop invariants back next to their uses when that avoids a spill: these 9 - 21 k-instruction kernels hoist
 # hundreds of literal / address materialisations out of the sub-step loop, whose live ranges then cost more than they save (round 2, Ant: 51 -> 4
@@ -40,7 +41,7 @@ NO_MLICM = ["-mllvm", "-disable-machine-licm"]
 # classic.hip (round 4): the five classic-control kinds' kernels under LLVM's max-ILP machine scheduler -- one wavefront per SIMD at 65 536 sub-environments,
 # so a dependent instruction's latency is hidden by the wavefront's OWN independent instructions or not at all.  A/B on one box (whole engine.hip
 # rebuilt with the flag, scripts/ab_bench.py, profiles/r04_maxilp_classic.txt): CartPole +6.4 %, Pendulum +5.8 %, MountainCarContinuous +2.7 %, Acrobot -0.3 %;
-# Taxi -1.3 %, Hopper (one-lane) -2.0 % -- hence only the classic kernels moved.  Results are bit-identical by construction (no re-association; every
+# Taxi -1.3 %, Hopper (one-lane) -2.0 % -- hence only the classic kernels moved (and tabular.hip and mujoco.hip, units since, have no entry below).  Results are bit-identical by construction (no re-association; every
 # classic parity test is array_equal) and the two-build comparison of tests/test_gpu_scheduler_guard.py covers this unit as well.
 # (`iterative-ilp` crashes clang-22 on engine.hip, `iterative-maxocc` stops with "Illegal instruction detected: Operand has incorrect register class".)
 MAXILP = ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]

@@ -5,7 +5,7 @@
 // hides a dependent instruction's latency but the wavefront's own independent instructions: max-ILP scheduling
 // measured +6.4 % (CartPole), +5.8 % (Pendulum), +2.7 % (MountainCarContinuous) against the default max-occupancy scheduler, with every result bit
 // unchanged (scheduling reorders, it does not re-associate; tests/test_gpu_parity.py compares array_equal) -- and -1 ... -2 % on the ToyText and
-// one-lane MuJoCo kernels, which therefore stay in engine.o on the default scheduler (profiles/r04_maxilp_classic.txt).
+// one-lane MuJoCo kernels, which therefore stay on the default scheduler (tabular.hip, mujoco.hip) (profiles/r04_maxilp_classic.txt).
 //
 // Here: the dispatchers from the env's kind to its type (envs_classic.h), the host ends of the step epilogue, the launch_step* / launch_rollout*
 // templates and namespace mi_classic.  No MuJoCo or ToyText code, and no part of the C ABI.

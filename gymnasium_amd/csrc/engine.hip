@@ -1,9 +1,10 @@
-// engine.hip -- libmi355env.so: the host side and the C ABI of include/mi355env.h for the lockstep vector-environment kernels for MI355X (gfx950).
-// The ToyText kernels (tabular_kernels.h), the per-lane MuJoCo kernels over the stock models (mj_glue_kernels.h, and mj_wrapped_kernels.h for their step
-// under RepeatAction / StickyAction; mjx_model.hip and mjx_mass_model.hip instantiate both over the per-sub-environment model fields) and the small
-// family-independent kernels (seeding, the action stream, transposes) are
-// instantiated here; the classic-control kernels are classic.hip's, behind the launch functions of namespace mi_classic.  What the units of the library
-// share is in engine_types.h (structs, mi_vecenv, cross-unit launch functions) and lane_common.h (device helpers).
+// engine.hip -- libmi355env.so: the host side and the C ABI of include/mi355env.h for the lockstep vector-environment kernels for MI355X (gfx950):
+// argument checking, the buffers, the action stream's bookkeeping, and the six family-independent kernels (seed_words_kernel, seed_sequence_kernel,
+// sticky_clear_kernel, act_init_kernel, act_sample_kernel, model_transpose_kernel).  No environment family's kernels are instantiated or chosen here:
+// the classic-control kinds are classic.hip's (namespace mi_classic), the MuJoCo kinds mujoco.hip's (mi_mujoco, with mjx_model.hip and
+// mjx_mass_model.hip behind it), the ToyText kinds tabular.hip's (mi_tabular) -- plain functions that take the env once its arguments are validated and
+// its buffers chosen.  So this unit includes none of their kernel headers and compiles in seconds.  What the units of the library share is in
+// engine_types.h (structs, mi_vecenv, cross-unit launch functions) and lane_common.h (device helpers).
 //
 // Execution model: one sub-environment per lane, 256-thread workgroups (4 wavefronts of 64, one per SIMD of a CU);
 // at num_envs = 65536 the grid is 256 workgroups = one per CU.  Sub-environment state is struct-of-arrays in HBM
@@ -12,7 +13,7 @@
 // segments.  TimeLimit, the autoreset state machine, the per-env PCG64 streams and the episode-return bookkeeping
 // all live on device; a step() is ONE kernel launch, a rollout(T) is ONE launch for T steps with the state held
 // in registers in between (the MuJoCo kinds: physics + glue per step for the cooperative robots, and a series of such trips per step while
-// RepeatAction / StickyAction are on, launch_mj_step_wrapped).  There is no CPU fallback anywhere in this file.
+// RepeatAction / StickyAction are on, mujoco.hip launch_mj_step_wrapped).  There is no CPU fallback anywhere in this library.
 //
 // Reference semantics reproduced (paths relative to the reference tree):
 //   vector/sync_vector_env.py:187-337  SyncVectorEnv.reset/step incl. NEXT_STEP / SAME_STEP / DISABLED autoreset
@@ -22,7 +23,6 @@
 //   utils/seeding.py:10-42             per-env Generator(PCG64(SeedSequence(seed + i))) (pcg64_dev.h)
 //   spaces/multi_discrete.py:176-178, spaces/box.py:463-465   action_space.sample() (rollout with on-device policy)
 #include <hip/hip_runtime.h>
-#include <type_traits>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -36,20 +36,12 @@
 #include "engine_types.h"
 #include "lane_common.h"
 #include "wrappers_internal.h"
-#include "mj_glue_kernels.h"
-#include "mj_wrapped_kernels.h"
-#include "mjx_physics.h"
-#include "tabular_kernels.h"
 
 namespace {
 
 // ---------------------------------------------------------------------------------------------------------
 // kernels
 // ---------------------------------------------------------------------------------------------------------
-
-// ---- cooperative physics (mjx_coop.h): G lanes per sub-environment, 64 / G sub-environments per wavefront --------------
-// mj_physics_kernel lives in mjx_physics.h and is instantiated in physics16.hip / physics32.hip (their own compiler settings); here it
-// is only launched: mi_phys::launch16 / launch32.
 
 __global__ void seed_words_kernel(DevEnv d, const uint64_t *words, const uint8_t *mask) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -153,39 +145,6 @@ const mi_layout kLayouts[kClassicKinds] = {
 };
 const int kNumActions[MI_ENV_KIND_COUNT] = {2, 0, 3, 3, 0, 0, 0, 0, 0};
 
-}  // namespace
-
-namespace {
-
-typedef mjx::MjEnv<mjx::HalfCheetahModel, mjx::kHalfCheetah> HalfCheetahEnv;
-typedef mjx::MjEnv<mjx::AntModel, mjx::kAnt> AntEnv;
-typedef mjx::MjEnv<mjx::HumanoidModel, mjx::kHumanoid> HumanoidEnv;
-typedef mjx::MjEnv<mjx::HopperModel, mjx::kHopper> HopperEnv;
-typedef mjx::MjEnv<mjx::Walker2dModel, mjx::kWalker2d> Walker2dEnv;
-typedef mjx::MjEnv<mjx::InvertedPendulumModel, mjx::kInvertedPendulum> InvertedPendulumEnv;
-typedef mjx::MjEnv<mjx::InvertedDoublePendulumModel, mjx::kInvertedDoublePendulum> InvertedDoublePendulumEnv;
-typedef mjx::MjEnv<mjx::ReacherModel, mjx::kReacher> ReacherEnv;
-typedef mjx::MjEnv<mjx::HumanoidStandupModel, mjx::kHumanoidStandup> HumanoidStandupEnv;
-typedef mjx::MjEnv<mjx::SwimmerModel, mjx::kSwimmer> SwimmerEnv;
-typedef mjx::MjEnv<mjx::PusherModel, mjx::kPusher> PusherEnv;
-template <class F>
-int dispatch_mj(int kind, F &&f) {
-    switch (kind) {
-    case MI_ENV_HALF_CHEETAH: return f(HalfCheetahEnv());
-    case MI_ENV_ANT: return f(AntEnv());
-    case MI_ENV_HUMANOID: return f(HumanoidEnv());
-    case MI_ENV_HOPPER: return f(HopperEnv());
-    case MI_ENV_WALKER2D: return f(Walker2dEnv());
-    case MI_ENV_INVERTED_PENDULUM: return f(InvertedPendulumEnv());
-    case MI_ENV_INVERTED_DOUBLE_PENDULUM: return f(InvertedDoublePendulumEnv());
-    case MI_ENV_REACHER: return f(ReacherEnv());
-    case MI_ENV_HUMANOID_STANDUP: return f(HumanoidStandupEnv());
-    case MI_ENV_SWIMMER: return f(SwimmerEnv());
-    case MI_ENV_PUSHER: return f(PusherEnv());
-    }
-    return fail(MI_ERR_UNSUPPORTED, "this MuJoCo kind is not built into the HIP engine yet");
-}
-
 // The sticky device error word lives in page-locked host memory (the kernels write it through its device address on the rare error): after
 // a stream synchronisation it is simply read, no copy.
 int raise_device_error(mi_vecenv *v) {  // precondition: the stream is idle (a kernel in flight could set the word again right after the clear)
@@ -204,140 +163,6 @@ int raise_device_error(mi_vecenv *v) {  // precondition: the stream is idle (a k
 int check_device_error(mi_vecenv *v) {
     HIP_TRY(hipStreamSynchronize(v->stream));
     return raise_device_error(v);
-}
-
-}  // namespace
-
-namespace {
-
-// One vector step of a MuJoCo env with RepeatAction / StickyAction on (mi_set_step_wrappers; mj_wrapped_kernels.h): the opening kernel, then per trip
-// what the plain step launches -- [cooperative physics ->] glue, the wrapped instantiation -- all on the env's stream, nothing synchronised.  The physics
-// launch of a trip takes the inner-step words as its meta (their skip bit as the mask: rows that finished inside the repeat, or that reset instead of
-// stepping, retire) and the effective action rows as its actions.
-template <class E>
-int launch_mj_step_wrapped(mi_vecenv *v, MjStepPtrs mp) {
-    const dim3 g(v->grid), b(kBlock);
-    const int mode = v->cfg.autoreset_mode;
-    const MjWrapDev w = {v->wrap.repeats, v->wrap.sticky_duration, v->wrap.sticky_p, v->wrap.last_action, v->wrap.sticky_word, v->d_wrap_acc, v->d_wrap_inner};
-    hipLaunchKernelGGL(mj_wrap_open_kernel, g, b, 0, v->stream, v->d, w, mp.actions, (int)E::NU, mp.act_f64, mode);
-    if (w.sticky_duration) mp.actions = w.last_action;
-    mp.extras = nullptr;
-    const int trips = w.repeats > 0 ? w.repeats : 1;
-    for (int trip = 0; trip < trips; trip++) {
-        if (v->d_model) {  // per-sub-environment model fields: the one-lane simulator with the lane's view
-            const bool mass = (v->model_mask & (1u << MI_MODEL_BODY_MASS_SCALE)) != 0;
-            if (!(mass ? mi_mjmass::step_wrapped : mi_mjmodel::step_wrapped)(v->cfg.kind, mode, trip, v->grid, v->stream, v->d, &mp, w))
-                return fail(MI_ERR_UNSUPPORTED, "no per-lane-model kernel for this env kind");
-            continue;
-        }
-        if constexpr (E::HAS_COOP) {
-            if (v->mj_coop) {
-                mi_phys::Args pa;
-                pa.state = v->d.state, pa.meta = w.inner, pa.needs_reset_mask = kMjInnerSkip, pa.N = v->d.N, pa.frame_skip = (int)v->d.P.p[4];
-                pa.newton = v->d.solver_newton, pa.act_f64 = mp.act_f64;
-                const bool ok = E::COOP_G == 16 ? mi_phys::launch16(v->cfg.kind, pa, true, mp.actions, v->d_extras, v->stream)
-                                                : mi_phys::launch32(v->cfg.kind, pa, true, mp.actions, v->d_extras, v->stream);
-                if (!ok) return fail(MI_ERR_UNSUPPORTED, "no cooperative physics kernel for this env kind");
-                mp.extras = v->d_extras;
-                hipLaunchKernelGGL((mj_trip_kernel<E, true>), g, b, 0, v->stream, v->d, mp, w, mode, trip);
-                continue;
-            }
-        }
-        hipLaunchKernelGGL((mj_trip_kernel<E, false>), g, b, 0, v->stream, v->d, mp, w, mode, trip);
-    }
-    HIP_TRY(hipGetLastError());
-    return MI_OK;
-}
-
-// One vector step of a MuJoCo env: [cooperative physics ->] per-lane glue (autoreset state machine, reward, observation, stats)
-template <class E>
-int launch_mj_step(mi_vecenv *v, MjStepPtrs mp) {
-    if (v->wrap_on) return launch_mj_step_wrapped<E>(v, mp);
-    const dim3 g(v->grid), b(kBlock);
-    const int mode = v->cfg.autoreset_mode;
-    mp.extras = nullptr;
-    if (v->d_model) {  // per-sub-environment model fields: the one-lane simulator with the lane's view
-        const bool mass = (v->model_mask & (1u << MI_MODEL_BODY_MASS_SCALE)) != 0;  // a body mass scale is held: the kernels with the mass rows in their view
-        if (!(mass ? mi_mjmass::step : mi_mjmodel::step)(v->cfg.kind, mode, v->grid, v->stream, v->d, &mp)) return fail(MI_ERR_UNSUPPORTED, "no per-lane-model kernel for this env kind");
-        HIP_TRY(hipGetLastError());
-        return MI_OK;
-    }
-    if constexpr (!E::HAS_COOP) {
-        switch (mode) {
-        case MI_AUTORESET_NEXT_STEP: hipLaunchKernelGGL((mj_step_kernel<E, MI_AUTORESET_NEXT_STEP, false>), g, b, 0, v->stream, v->d, mp); break;
-        case MI_AUTORESET_SAME_STEP: hipLaunchKernelGGL((mj_step_kernel<E, MI_AUTORESET_SAME_STEP, false>), g, b, 0, v->stream, v->d, mp); break;
-        default: hipLaunchKernelGGL((mj_step_kernel<E, MI_AUTORESET_DISABLED, false>), g, b, 0, v->stream, v->d, mp); break;
-        }
-        HIP_TRY(hipGetLastError());
-        return MI_OK;
-    } else {
-    if (v->mj_coop) {
-        mi_phys::Args pa;
-        pa.state = v->d.state, pa.meta = v->d.meta, pa.needs_reset_mask = kNeedsReset << kFlagShift, pa.N = v->d.N, pa.frame_skip = (int)v->d.P.p[4];
-        pa.newton = v->d.solver_newton, pa.act_f64 = mp.act_f64;
-        const bool skip_resetting = mode != MI_AUTORESET_SAME_STEP;  // SAME_STEP: every sub-environment steps
-        const bool ok = E::COOP_G == 16 ? mi_phys::launch16(v->cfg.kind, pa, skip_resetting, mp.actions, v->d_extras, v->stream)
-                                        : mi_phys::launch32(v->cfg.kind, pa, skip_resetting, mp.actions, v->d_extras, v->stream);
-        if (!ok) return fail(MI_ERR_UNSUPPORTED, "no cooperative physics kernel for this env kind");
-        mp.extras = v->d_extras;
-    }
-    if (v->mj_coop) {
-        switch (mode) {
-        case MI_AUTORESET_NEXT_STEP: hipLaunchKernelGGL((mj_step_kernel<E, MI_AUTORESET_NEXT_STEP, true>), g, b, 0, v->stream, v->d, mp); break;
-        case MI_AUTORESET_SAME_STEP: hipLaunchKernelGGL((mj_step_kernel<E, MI_AUTORESET_SAME_STEP, true>), g, b, 0, v->stream, v->d, mp); break;
-        default: hipLaunchKernelGGL((mj_step_kernel<E, MI_AUTORESET_DISABLED, true>), g, b, 0, v->stream, v->d, mp); break;
-        }
-    } else {
-        switch (mode) {
-        case MI_AUTORESET_NEXT_STEP: hipLaunchKernelGGL((mj_step_kernel<E, MI_AUTORESET_NEXT_STEP, false>), g, b, 0, v->stream, v->d, mp); break;
-        case MI_AUTORESET_SAME_STEP: hipLaunchKernelGGL((mj_step_kernel<E, MI_AUTORESET_SAME_STEP, false>), g, b, 0, v->stream, v->d, mp); break;
-        default: hipLaunchKernelGGL((mj_step_kernel<E, MI_AUTORESET_DISABLED, false>), g, b, 0, v->stream, v->d, mp); break;
-        }
-    }
-    HIP_TRY(hipGetLastError());
-    return MI_OK;
-    }
-}
-
-// T vector steps with the cooperative physics: per step [sample actions ->] physics -> glue, all on the env's stream.  Every MuJoCo kind's rollout
-// takes this form while RepeatAction / StickyAction are on (launch_mj_step_wrapped): a sticky action then replaces the drawn one, whose draws are
-// consumed either way.
-template <class E>
-int launch_mj_rollout_coop(mi_vecenv *v, const RolloutPtrs &p, const ActionStream &as, int T, bool sample, int in_f64, const RolloutExtra &ex) {
-    const size_t N = (size_t)v->cfg.num_envs;
-    const dim3 g(v->grid), b(kBlock);
-    // the glue kernel writes a final_obs / final_info row only where an episode ended (mi_step's contract): the other rows are zeros (mi_rollout_extra)
-    if (ex.final_obs) HIP_TRY(hipMemsetAsync(ex.final_obs, 0, (size_t)T * N * v->lay.obs_dim * sizeof(double), v->stream));
-    if (ex.final_info) HIP_TRY(hipMemsetAsync(ex.final_info, 0, (size_t)T * N * E::INFO * sizeof(double), v->stream));
-    for (int t = 0; t < T; t++) {
-        const void *act;
-        if (sample) {
-            float *dst = p.actions_out ? static_cast<float *>(p.actions_out) + (size_t)t * N * E::NU : v->d_act_scratch;
-            hipLaunchKernelGGL((mj_sample_kernel<E>), g, b, 0, v->stream, v->d, as, t, dst);
-            act = dst;
-        } else if (in_f64) {
-            act = static_cast<const double *>(p.actions_in) + (size_t)t * N * E::NU;
-        } else {
-            act = static_cast<const float *>(p.actions_in) + (size_t)t * N * E::NU;
-        }
-        MjStepPtrs mp;
-        memset(&mp, 0, sizeof mp);
-        mp.actions = act, mp.act_f64 = !sample && in_f64;
-        mp.obs = p.obs ? static_cast<double *>(p.obs) + (size_t)t * N * v->lay.obs_dim : static_cast<double *>(v->d_obs_scratch);
-        mp.reward = p.reward ? p.reward + (size_t)t * N : nullptr;
-        mp.terminated = p.terminated ? p.terminated + (size_t)t * N : nullptr;
-        mp.truncated = p.truncated ? p.truncated + (size_t)t * N : nullptr;
-        mp.obs_dim = v->lay.obs_dim;
-        mp.final_obs = ex.final_obs ? static_cast<double *>(ex.final_obs) + (size_t)t * N * v->lay.obs_dim : nullptr;
-        mp.ep_ret = ex.ep_ret ? ex.ep_ret + (size_t)t * N : nullptr;
-        mp.ep_len = ex.ep_len ? ex.ep_len + (size_t)t * N : nullptr;
-        // (the finishing step's info reaches final_info through the info row: without a caller's array the env's own staging row serves)
-        mp.info = ex.info ? ex.info + (size_t)t * N * E::INFO : (ex.final_info ? v->d_info : nullptr);
-        mp.final_info = ex.final_info ? ex.final_info + (size_t)t * N * E::INFO : nullptr;
-        const int rc = launch_mj_step<E>(v, mp);
-        if (rc) return rc;
-    }
-    return MI_OK;
 }
 
 int set_device(const mi_vecenv *v) {
@@ -392,26 +217,7 @@ int mi_create(const mi_config *cfg, int device, mi_vecenv **out) {
 
 static int create_buffers(mi_vecenv *v, const mi_config *cfg, int device) {
     if (is_mj(cfg->kind)) {
-        mi::EnvParams P;
-        for (int k = 0; k < 16; k++) P.p[k] = cfg->params[k];
-        dispatch_mj(cfg->kind, [&](auto env) -> int {
-            using E = decltype(env);
-            const mi_layout l = {E::obs_dim_host(P), MI_F64, E::NU, MI_F32, E::S, E::INFO, {0, 0}};
-            v->lay = l;
-            v->extras_dim = mjx::coop::Sim<typename E::Model, E::COOP_G>::EX_TOTAL;
-            return (int)MI_OK;
-        });
-        // Which physics kernel: the cooperative one (mjx_coop.h) wins where the robot fills its 16 / 32 lanes (Ant 2.4M vs 1.4M
-        // env-steps/s, Humanoid 0.76M vs 0.23M); HalfCheetah (9 dofs, 7 bodies, one forward pass per sub-step) is faster on the
-        // one-lane kernel (16.4M vs 12.9M).  MI355ENV_MJ_SERIAL=1 / MI355ENV_MJ_COOP=1 force either one (cross-check tests).
-        const char *serial = getenv("MI355ENV_MJ_SERIAL"), *coop = getenv("MI355ENV_MJ_COOP");
-        // the faster kernel per robot: HalfCheetah 22.0 M (cooperative) vs 18.8 M (one-lane) env-steps/s at 65536 envs
-        const bool has_coop = cfg->kind == MI_ENV_HALF_CHEETAH || cfg->kind == MI_ENV_ANT || cfg->kind == MI_ENV_HUMANOID || cfg->kind == MI_ENV_HUMANOID_STANDUP ||
-                              cfg->kind == MI_ENV_HOPPER || cfg->kind == MI_ENV_WALKER2D;  // (round 2: the planar walkers joined -- Walker2d 6.6 M one-lane)
-        v->mj_coop = has_coop && cfg->kind != MI_ENV_HOPPER;  // measured @65536: Walker2d 8.4 M cooperative vs 6.6 M one-lane; Hopper 9.7 M vs 17.2 M
-        if (serial && serial[0] == '1') v->mj_coop = false;
-        if (coop && coop[0] == '1') v->mj_coop = true;
-        if (!has_coop) v->mj_coop = false;  // the other small robots: one-lane kernel only (cylinder geoms, fluid forces, two-dof arms)
+        mi_mujoco::configure(v);  // the robot's layout, and which physics kernel it runs
     } else if (cfg->kind == MI_ENV_BLACKJACK) {
         const mi_layout l = {3, MI_I64, 1, MI_I64, 2, 0, {0, 0}};
         v->lay = l;
@@ -628,29 +434,7 @@ int mi_get_env_attr(mi_vecenv *v, int attr, double *host_out) {
 
 // Per-sub-environment model fields of the MuJoCo kinds (include/mi355env.h MI_MODEL_*; device side: mjx::LaneModel).  As everywhere on this path the
 // parity with `mujoco` is UNPINNED; the CPU oracle, which takes the same fields as data, is the reference.
-struct ModelFieldInfo {
-    int width[MI_MODEL_FIELD_COUNT], offset[MI_MODEL_FIELD_COUNT], total;
-    const double *defaults[MI_MODEL_FIELD_COUNT];
-    // the rows derived from the body mass scale (MI_MODEL_DERIVED_*) and the compiled model's values of them
-    int dwidth[MI_MODEL_DERIVED_COUNT], doffset[MI_MODEL_DERIVED_COUNT];
-    const double *dcompiled[MI_MODEL_DERIVED_COUNT];
-};
-static const double kUnitMassScale[32] = {1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1};
-static bool model_field_info(const mi_vecenv *v, ModelFieldInfo &out) {
-    if (!v || !is_mj(v->cfg.kind)) return false;
-    return dispatch_mj(v->cfg.kind, [&](auto env) -> int {
-               typedef typename decltype(env)::Model M;
-               typedef mjx::MassLaneFields<M> V;
-               static_assert(M::NBODY <= 32, "kUnitMassScale");
-               static const double kMeanInertia = M::MEANINERTIA;  // (one per robot: the lambda is instantiated per env type)
-               const ModelFieldInfo f = {{3, M::NU, M::NV, M::NPAIR, M::NBODY}, {V::OFF_GRAVITY, V::OFF_GEAR, V::OFF_DAMPING, V::OFF_FRICTION, V::OFF_MASS_SCALE}, V::WIDTH,
-                                         {M::gravity, M::actuator_gear, M::dof_damping, M::pair_friction, kUnitMassScale},
-                                         {M::NV, 2 * M::NBODY, 1}, {V::OFF_DOF_INVWEIGHT, V::OFF_BODY_INVWEIGHT, V::OFF_MEANINERTIA},
-                                         {M::dof_invweight0, &M::body_invweight0[0][0], &kMeanInertia}};
-               out = f;
-               return (int)MI_OK;
-           }) == MI_OK;
-}
+static bool model_field_info(const mi_vecenv *v, ModelFieldInfo &out) { return v && mi_mujoco::model_field_info(v->cfg.kind, out); }
 static int model_field_check(mi_vecenv *v, int field, ModelFieldInfo &f) {
     if (!v) return fail(MI_ERR_INVALID_ARGUMENT, "null env");
     if (!model_field_info(v, f)) return fail(MI_ERR_UNSUPPORTED, "per-sub-environment model fields: the MuJoCo kinds only");
@@ -780,7 +564,7 @@ int mi_get_model_derived(mi_vecenv *v, int which, double *host_out) {
 // RepeatAction / StickyAction of the sub-environments (include/mi355env.h mi_set_step_wrappers; device side: lane_step_wrapped).
 int mi_set_step_wrappers(mi_vecenv *v, int num_repeats, double sticky_probability, int sticky_duration) {
     if (!v) return fail(MI_ERR_INVALID_ARGUMENT, "null env");
-    const bool mj = is_mj(v->cfg.kind);  // the MuJoCo kinds: trips of the plain step's launches (launch_mj_step_wrapped)
+    const bool mj = is_mj(v->cfg.kind);  // the MuJoCo kinds: trips of the plain step's launches (mujoco.hip launch_mj_step_wrapped)
     if (!mj && (v->cfg.kind < 0 || v->cfg.kind >= kClassicKinds))
         return fail(MI_ERR_UNSUPPORTED, "mi_set_step_wrappers: the five classic-control kinds and the eleven MuJoCo kinds only");
     if (v->shared_rng) return fail(MI_ERR_UNSUPPORTED, "mi_set_step_wrappers: not with MI_CFG_SHARED_RNG (CartPoleVectorEnv has no sub-environments to wrap)");
@@ -1010,29 +794,11 @@ int mi_reset(mi_vecenv *v, const uint8_t *mask, const double *bounds, void *obs,
     }
     const int has_bounds = bounds != nullptr;
     const double b0 = has_bounds ? bounds[0] : 0.0, b1 = has_bounds ? bounds[1] : 0.0;
-    if (is_tab(v->cfg.kind)) {
-        if (!v->tab_loaded) return fail(MI_ERR_STATE, "tabular environment without a table: call mi_tabular_load first");
-        hipLaunchKernelGGL(tab_reset_kernel, dim3(v->grid), dim3(kBlock), 0, v->stream, v->d, dm, (int64_t *)dobs);
-        HIP_TRY(hipGetLastError());
-        v->was_reset = true;
-        if (loc == MI_HOST) {
-            HIP_TRY(hipStreamSynchronize(v->stream));
-            if (obs && obs != v->h_io.obs) memcpy(obs, v->h_io.obs, v->obs_bytes);
-        }
-        return MI_OK;
-    }
-    int rc = is_mj(v->cfg.kind) ? dispatch_mj(v->cfg.kind, [&](auto env) -> int {
-        using E = decltype(env);
-        // a body mass scale was set: the Humanoids' reset reads the lane's body masses (an env that never set one keeps the stock reset kernel, bit for bit)
-        if (v->d_model && (v->model_mask & (1u << MI_MODEL_BODY_MASS_SCALE))) {
-            if (!mi_mjmass::reset(v->cfg.kind, v->grid, v->stream, v->d, dm, (double *)dobs, v->lay.obs_dim)) return fail(MI_ERR_UNSUPPORTED, "no per-lane-model kernel for this env kind");
-            HIP_TRY(hipGetLastError());
-            return (int)MI_OK;
-        }
-        hipLaunchKernelGGL((mj_reset_kernel<E>), dim3(v->grid), dim3(kBlock), 0, v->stream, v->d, dm, (double *)dobs, v->lay.obs_dim);
-        HIP_TRY(hipGetLastError());
-        return (int)MI_OK;
-    }) : v->shared_rng ? MI_OK : mi_classic::reset(v, dm, has_bounds, b0, b1, (float *)dobs);
+    if (is_tab(v->cfg.kind) && !v->tab_loaded) return fail(MI_ERR_STATE, "tabular environment without a table: call mi_tabular_load first");
+    int rc = is_tab(v->cfg.kind)  ? mi_tabular::reset(v, dm, (int64_t *)dobs)
+             : is_mj(v->cfg.kind) ? mi_mujoco::reset(v, dm, (double *)dobs)
+             : v->shared_rng      ? (int)MI_OK
+                                  : mi_classic::reset(v, dm, has_bounds, b0, b1, (float *)dobs);
     if (v->shared_rng) {  // CartPoleVectorEnv.reset (cartpole.py:481-503): every sub-environment, bounds kept for the autoresets
         if (mask) return fail(MI_ERR_UNSUPPORTED, "MI_CFG_SHARED_RNG: CartPoleVectorEnv.reset resets every sub-environment (no reset_mask)");
         v->shared.low = has_bounds ? b0 : -0.05, v->shared.high = has_bounds ? b1 : 0.05;
@@ -1109,15 +875,8 @@ static int action_spec(const mi_vecenv *v, ActSpec *sp) {
         sp->lo[0] = -2.0, sp->range[0] = 2.0 - (-2.0);  // Box(-max_torque, max_torque) (pendulum.py:112-114)
     else if (kind == MI_ENV_MOUNTAIN_CAR_CONTINUOUS)
         sp->lo[0] = -1.0, sp->range[0] = 1.0 - (-1.0);  // Box(min_action, max_action) (continuous_mountain_car.py:137-139)
-    else
-        return dispatch_mj(kind, [&](auto env) -> int {  // Box(low, high, (nu,), float32) from the float32 ctrlrange (mujoco_env.py:113-117)
-            using E = decltype(env);
-            for (int u = 0; u < E::NU; u++) {
-                const double lo = (double)(float)E::Model::actuator_ctrlrange[u][0], hi = (double)(float)E::Model::actuator_ctrlrange[u][1];
-                sp->lo[u] = lo, sp->range[u] = hi - lo;
-            }
-            return (int)MI_OK;
-        });
+    else if (!mi_mujoco::action_bounds(kind, sp->lo, sp->range))
+        return fail(MI_ERR_UNSUPPORTED, "this MuJoCo kind is not built into the HIP engine yet");
     return MI_OK;
 }
 // T batches of action_space.sample() into `dst` (device), from the lane states
@@ -1221,28 +980,9 @@ static int step_enqueue(mi_vecenv *v, const mi_step_io *io, int loc) {
     if (zc) dinfo = dinfo ? (double *)pinned(v, dinfo) : nullptr, dfinfo = dfinfo ? (double *)pinned(v, dfinfo) : nullptr;
     int rc;
     if (is_tab(v->cfg.kind)) {
-        const TabStepPtrs tp = {(const int64_t *)p.actions, (int64_t *)p.obs, p.reward, p.terminated, p.truncated, (int64_t *)p.final_obs,
-                                p.ep_ret, p.ep_len, dinfo, dfinfo, p.act_lane, (int64_t *)p.actions_out, p.act_jump};
-        const dim3 g(v->grid), b(kBlock);
-        if (fused_sample) {
-            switch (v->cfg.autoreset_mode) {
-            case MI_AUTORESET_NEXT_STEP: hipLaunchKernelGGL((tab_step_kernel<MI_AUTORESET_NEXT_STEP, true>), g, b, 0, v->stream, v->d, tp); break;
-            case MI_AUTORESET_SAME_STEP: hipLaunchKernelGGL((tab_step_kernel<MI_AUTORESET_SAME_STEP, true>), g, b, 0, v->stream, v->d, tp); break;
-            default: hipLaunchKernelGGL((tab_step_kernel<MI_AUTORESET_DISABLED, true>), g, b, 0, v->stream, v->d, tp); break;
-            }
-        } else
-        switch (v->cfg.autoreset_mode) {
-        case MI_AUTORESET_NEXT_STEP: hipLaunchKernelGGL((tab_step_kernel<MI_AUTORESET_NEXT_STEP>), g, b, 0, v->stream, v->d, tp); break;
-        case MI_AUTORESET_SAME_STEP: hipLaunchKernelGGL((tab_step_kernel<MI_AUTORESET_SAME_STEP>), g, b, 0, v->stream, v->d, tp); break;
-        default: hipLaunchKernelGGL((tab_step_kernel<MI_AUTORESET_DISABLED>), g, b, 0, v->stream, v->d, tp); break;
-        }
-        HIP_TRY(hipGetLastError());
-        rc = MI_OK;
+        rc = mi_tabular::step(v, p, dinfo, dfinfo, fused_sample);
     } else if (is_mj(v->cfg.kind)) {
-        const MjStepPtrs mp = {p.actions, (double *)p.obs, p.reward, p.terminated, p.truncated, (double *)p.final_obs,
-                               p.ep_ret, p.ep_len, dinfo, dfinfo, v->lay.obs_dim, nullptr, act_kind != MI_F32};
-        if (!mp.obs) return fail(MI_ERR_INVALID_ARGUMENT, "obs is NULL");
-        rc = dispatch_mj(v->cfg.kind, [&](auto env) -> int { return launch_mj_step<decltype(env)>(v, mp); });
+        rc = mi_mujoco::step(v, p, dinfo, dfinfo, act_kind);
     } else if (v->shared_rng) {
         if (p.final_obs) return fail(MI_ERR_INVALID_ARGUMENT, "MI_CFG_SHARED_RNG is NEXT_STEP only: no final_obs");
         rc = mi_classic::shared_step(v, p);
@@ -1399,131 +1139,14 @@ static int rollout_impl(mi_vecenv *v, int T, const mi_rollout_io *io, const Roll
     ActionStream as;
     memset(&as, 0, sizeof as);
     if (sample) {
-        as.state_hi = (uint64_t)(v->act_rng.state >> 64), as.state_lo = (uint64_t)v->act_rng.state;
-        as.inc_hi = (uint64_t)(v->act_rng.inc >> 64), as.inc_lo = (uint64_t)v->act_rng.inc;
-        as.pow2 = v->d_pow2, as.jump_n = v->jump_n;
+        as = action_stream(v);
         if (keep_lanes) as.lane = v->d_act_lane, as.lane_valid = v->act_lane_valid ? 1 : 0;
     }
     int rc;
     if (is_tab(v->cfg.kind)) {
-        const dim3 g(v->grid), b(kBlock);
-        const bool next = v->cfg.autoreset_mode == MI_AUTORESET_NEXT_STEP;
-        // table in LDS when it fits next to the 160 KB of a CU and the copy is amortised over enough steps (Blackjack has no table)
-        size_t lds = 0;
-        if (v->d.tab.nS > 0 && T >= 8 && !v->d.tab.env_table) {  // (per-sub-environment tables stay in HBM / L2)
-            const size_t cells = (size_t)v->d.tab.nS * v->d.tab.nA, rows = cells * v->d.tab.K;
-            lds = (3 * rows + v->d.tab.nS) * sizeof(double) + (rows + cells) * sizeof(int32_t) + rows;
-            lds = (lds + 15) & ~(size_t)15;
-            if (lds > 150 * 1024) lds = 0;
-        }
-        const int lb = (int)lds;
-        const int tk = v->d.tab.nS < 0 ? kTabBlackjack : (v->d.tab_fickle_rows ? kTabFickle : kTabPlain);
-        auto launch_ex = [&](auto mode, auto smp, auto with_extras) {
-            constexpr int M = decltype(mode)::value;
-            constexpr bool S = decltype(smp)::value, X = decltype(with_extras)::value;
-            RolloutExtra e = {};
-            if constexpr (X) e = *ex;
-            if (tk == kTabBlackjack)  // (no table)
-                hipLaunchKernelGGL((tab_rollout_kernel<M, S, false, kTabBlackjack, X>), g, b, 0, v->stream, v->d, p, as, T, lb, e);
-            else if (tk == kTabFickle && lds)
-                hipLaunchKernelGGL((tab_rollout_kernel<M, S, true, kTabFickle, X>), g, b, lds, v->stream, v->d, p, as, T, lb, e);
-            else if (tk == kTabFickle)
-                hipLaunchKernelGGL((tab_rollout_kernel<M, S, false, kTabFickle, X>), g, b, 0, v->stream, v->d, p, as, T, lb, e);
-            else if (lds)
-                hipLaunchKernelGGL((tab_rollout_kernel<M, S, true, kTabPlain, X>), g, b, lds, v->stream, v->d, p, as, T, lb, e);
-            else
-                hipLaunchKernelGGL((tab_rollout_kernel<M, S, false, kTabPlain, X>), g, b, 0, v->stream, v->d, p, as, T, lb, e);
-        };
-        auto launch = [&](auto mode, auto smp) { launch_ex(mode, smp, std::false_type()); };
-        typedef std::integral_constant<int, MI_AUTORESET_NEXT_STEP> NextT;
-        typedef std::integral_constant<int, MI_AUTORESET_SAME_STEP> SameT;
-        // the branch-free kernel for the collector's case: one plain table of <= 3 outcomes per (state, action) that fits into LDS in its packed form
-        static const bool lean_on = !(getenv("MI355ENV_TAB_LEAN") && getenv("MI355ENV_TAB_LEAN")[0] == '0');  // "0": tab_rollout_kernel (A/B, tests)
-        const int kl = v->d.tab.K == 1 ? 1 : 3;
-        const size_t lean_lds = tk == kTabPlain && v->d.tab.nS > 0 ? (tab_lean_lds_bytes(v->d.tab.nS, v->d.tab.nA, kl) + 15) & ~(size_t)15 : 0;
-        if (ex) {  // the general kernel stores the extras; the branch-free kernels below have no such outputs
-            if (next && sample)
-                launch_ex(NextT(), std::true_type(), std::true_type());
-            else if (next)
-                launch_ex(NextT(), std::false_type(), std::true_type());
-            else if (sample)
-                launch_ex(SameT(), std::true_type(), std::true_type());
-            else
-                launch_ex(SameT(), std::false_type(), std::true_type());
-        } else if (next && sample && lean_on && tk == kTabPlain && !v->d.tab.env_table && v->d.tab.K <= 3 && lean_lds <= 150 * 1024) {
-            const bool full = p.actions_out && p.obs && p.reward && p.terminated && p.truncated;
-            const int nA = v->d.tab.nA, start = v->tab_start_state;
-            const bool apow2 = nA >= 2 && (nA & (nA - 1)) == 0;
-            int shift = 64;
-            for (int x = nA; apow2 && x > 1; x >>= 1) shift--;
-            auto lean = [&](auto kl_c, auto full_c, auto one_c, auto pow_c) {
-                hipLaunchKernelGGL((tab_rollout_lean_kernel<decltype(kl_c)::value, decltype(full_c)::value, decltype(one_c)::value, decltype(pow_c)::value>), g, b,
-                                   lean_lds, v->stream, v->d, p, as, T, start, shift);
-            };
-            auto pick_pow = [&](auto kl_c, auto full_c, auto one_c) {
-                if (apow2)
-                    lean(kl_c, full_c, one_c, std::true_type());
-                else
-                    lean(kl_c, full_c, one_c, std::false_type());
-            };
-            auto pick_one = [&](auto kl_c, auto full_c) {
-                if (start >= 0)
-                    pick_pow(kl_c, full_c, std::true_type());
-                else
-                    pick_pow(kl_c, full_c, std::false_type());
-            };
-            auto pick_full = [&](auto kl_c) {
-                if (full)
-                    pick_one(kl_c, std::true_type());
-                else
-                    pick_one(kl_c, std::false_type());
-            };
-            if (kl == 1)
-                pick_full(std::integral_constant<int, 1>());
-            else
-                pick_full(std::integral_constant<int, 3>());
-        } else if (next && sample && lean_on && tk == kTabBlackjack) {
-            const char *fs = getenv("MI355ENV_BJ_FORCE_SLOW");  // tests: every k-th lane-step through the general routines
-            const int force_slow = fs ? atoi(fs) : 0;
-            if (p.actions_out && p.obs && p.reward && p.terminated && p.truncated)
-                hipLaunchKernelGGL((bj_rollout_lean_kernel<true>), g, b, 0, v->stream, v->d, p, as, T, force_slow);
-            else
-                hipLaunchKernelGGL((bj_rollout_lean_kernel<false>), g, b, 0, v->stream, v->d, p, as, T, force_slow);
-        } else if (next && sample)
-            launch(NextT(), std::true_type());
-        else if (next)
-            launch(NextT(), std::false_type());
-        else if (sample)
-            launch(SameT(), std::true_type());
-        else
-            launch(SameT(), std::false_type());
-        HIP_TRY(hipGetLastError());
-        rc = MI_OK;
+        rc = mi_tabular::rollout(v, p, as, T, sample, ex);
     } else if (is_mj(v->cfg.kind)) {
-        rc = dispatch_mj(v->cfg.kind, [&](auto env) -> int {
-            using E = decltype(env);
-            const RolloutExtra e = ex ? *ex : RolloutExtra{};
-            if (v->wrap_on) return launch_mj_rollout_coop<E>(v, p, as, T, sample, in_f64, e);
-            if (v->d_model) {
-                if (!((v->model_mask & (1u << MI_MODEL_BODY_MASS_SCALE)) ? mi_mjmass::rollout : mi_mjmodel::rollout)(v->cfg.kind, v->cfg.autoreset_mode, sample, v->grid, v->stream, v->d, p, as, T, v->lay.obs_dim, in_f64, e))
-                    return fail(MI_ERR_UNSUPPORTED, "no per-lane-model kernel for this env kind");
-                HIP_TRY(hipGetLastError());
-                return (int)MI_OK;
-            }
-            if (v->mj_coop) return launch_mj_rollout_coop<E>(v, p, as, T, sample, in_f64, e);
-            const dim3 g(v->grid), b(kBlock);
-            const bool next = v->cfg.autoreset_mode == MI_AUTORESET_NEXT_STEP;
-            if (next && sample)
-                hipLaunchKernelGGL((mj_rollout_kernel<E, MI_AUTORESET_NEXT_STEP, true>), g, b, 0, v->stream, v->d, p, as, T, v->lay.obs_dim, in_f64, e);
-            else if (next)
-                hipLaunchKernelGGL((mj_rollout_kernel<E, MI_AUTORESET_NEXT_STEP, false>), g, b, 0, v->stream, v->d, p, as, T, v->lay.obs_dim, in_f64, e);
-            else if (sample)
-                hipLaunchKernelGGL((mj_rollout_kernel<E, MI_AUTORESET_SAME_STEP, true>), g, b, 0, v->stream, v->d, p, as, T, v->lay.obs_dim, in_f64, e);
-            else
-                hipLaunchKernelGGL((mj_rollout_kernel<E, MI_AUTORESET_SAME_STEP, false>), g, b, 0, v->stream, v->d, p, as, T, v->lay.obs_dim, in_f64, e);
-            HIP_TRY(hipGetLastError());
-            return (int)MI_OK;
-        });
+        rc = mi_mujoco::rollout(v, p, as, T, sample, in_f64, ex);
     } else if (v->shared_rng) {
         rc = mi_classic::shared_rollout(v, p, as, T, sample, ex);  // (T step launches: the step kernel's own outputs, row t of the caller's arrays)
     } else if (ex) {

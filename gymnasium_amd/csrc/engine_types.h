@@ -1,4 +1,4 @@
-// engine_types.h -- what the engine's units (engine.hip, classic.hip, lookahead.hip, mjx_model.hip and mjx_mass_model.hip) agree on: the
+// engine_types.h -- what the engine's units (engine.hip, classic.hip, mujoco.hip, tabular.hip, lookahead.hip, mjx_model.hip and mjx_mass_model.hip) agree on: the
 // constants of the lane's flag word, the plain structs that ride in kernel arguments and in mi_vecenv, the handle itself, the launch functions one
 // unit defines and another calls, and the error helpers of the host side.  No kernel and no device function lives here.
 #ifndef MI355ENV_ENGINE_TYPES_H
@@ -172,6 +172,15 @@ struct SharedRng {
     uint32_t *blk_prefix;  // [grid] exclusive scan of blk_done (shared_scan_kernel)
     double low, high;      // self.low / self.high (cartpole.py:489-491): the bounds of the last reset() serve the autoresets
 };
+// Per-sub-environment model fields of a MuJoCo kind (include/mi355env.h MI_MODEL_*; device side: mjx::LaneModel): where each field lies in the env's
+// rows and the compiled-in values it starts from (mi_mujoco::model_field_info).
+struct ModelFieldInfo {
+    int width[MI_MODEL_FIELD_COUNT], offset[MI_MODEL_FIELD_COUNT], total;
+    const double *defaults[MI_MODEL_FIELD_COUNT];
+    // the rows derived from the body mass scale (MI_MODEL_DERIVED_*) and the compiled model's values of them
+    int dwidth[MI_MODEL_DERIVED_COUNT], doffset[MI_MODEL_DERIVED_COUNT];
+    const double *dcompiled[MI_MODEL_DERIVED_COUNT];
+};
 }  // namespace mi_internal
 // The classic-control kernels behind plain launch functions (defined in classic.hip, called from engine.hip): what mi_step / mi_reset /
 // mi_rollout do for the kinds CARTPOLE ... MOUNTAIN_CAR_CONTINUOUS once the arguments are validated and the buffers chosen.
@@ -189,6 +198,23 @@ int shared_step(mi_vecenv *v, const mi_internal::StepPtrs &p);
 int shared_rollout(mi_vecenv *v, const mi_internal::RolloutPtrs &p, const mi_internal::ActionStream &as, int T, bool sample, const mi_internal::RolloutExtra *ex = nullptr);
 int shared_recount(mi_vecenv *v);
 }  // namespace mi_classic
+// The MuJoCo family behind plain functions (defined in mujoco.hip, called from engine.hip): likewise for the eleven MuJoCo kinds -- over the stock models, the
+// per-sub-environment model fields or the cooperative physics, as the env stands -- and what the host side needs to know about a robot (bool: false for another kind).
+namespace mi_mujoco {
+bool configure(mi_vecenv *v);  // mi_create: v->lay, v->extras_dim and the v->mj_coop default of v->cfg's robot
+bool model_field_info(int kind, mi_internal::ModelFieldInfo &out);
+bool action_bounds(int kind, double *lo, double *range);  // Box(low, high, (nu,), float32) from the float32 ctrlrange (mujoco_env.py:113-117): low, high - low
+int reset(mi_vecenv *v, const uint8_t *device_mask, double *device_obs);
+int step(mi_vecenv *v, const mi_internal::StepPtrs &p, double *info, double *final_info, int act_kind);  // (obs / final_obs are float64 rows here)
+int rollout(mi_vecenv *v, const mi_internal::RolloutPtrs &p, const mi_internal::ActionStream &as, int T, bool sample, int in_f64, const mi_internal::RolloutExtra *ex);
+}  // namespace mi_mujoco
+// The ToyText kernels behind plain launch functions (defined in tabular.hip, called from engine.hip) for MI_ENV_TABULAR and MI_ENV_BLACKJACK; rollout
+// chooses among the general, the branch-free and the Blackjack kernels.  The table is v->d.tab (mi_tabular_load).
+namespace mi_tabular {
+int reset(mi_vecenv *v, const uint8_t *device_mask, int64_t *device_obs);
+int step(mi_vecenv *v, const mi_internal::StepPtrs &p, double *info, double *final_info, bool fused_sample);  // (obs / final_obs / actions are int64 rows here)
+int rollout(mi_vecenv *v, const mi_internal::RolloutPtrs &p, const mi_internal::ActionStream &as, int T, bool sample, const mi_internal::RolloutExtra *ex);
+}  // namespace mi_tabular
 // mi_lookahead's kernels behind a plain launch function (defined in lookahead.hip, called from engine.hip once the arguments are validated):
 // lookahead_kernel<E> of the env's kind, its per-lane type when the env is on those, and the element type of the action rows.  Device pointers;
 // every output nullable.  (mi_lookahead_unit: `mi_lookahead` itself is the C entry point's name.)
@@ -198,8 +224,9 @@ int launch(mi_vecenv *v, const void *actions, int act_kind, int horizon, int can
 }  // namespace mi_lookahead_unit
 // The one-lane MuJoCo kernels of an env with per-sub-environment model fields (mi_set_model_field) -- mj_step_kernel and mj_rollout_kernel over
 // mjx::LaneModel env types -- behind plain launch functions: they are instantiated in a translation unit of their own (mjx_model.hip),
-// which compiles side by side with the others.  `mj_step_ptrs` is an MjStepPtrs -- a type of the unnamed namespace, whose name is
-// part of the stock kernels' symbols and therefore stays there; both units compile the one definition below.  d.mj.rows are the env's rows.
+// which compiles side by side with the others.  mujoco.hip launches through them (its lane_launchers; engine.hip calls preload and
+// derive_constants only).  `mj_step_ptrs` is an MjStepPtrs -- a type of the unnamed namespace, whose name is
+// part of the stock kernels' symbols and therefore stays there; every unit compiles the one definition below.  d.mj.rows are the env's rows.
 // false: a kind the unit does not hold.
 namespace mi_mjmodel {
 bool step(int kind, int autoreset_mode, int grid, hipStream_t stream, const mi_internal::DevEnv &d, const void *mj_step_ptrs);

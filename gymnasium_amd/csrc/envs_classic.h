@@ -132,7 +132,7 @@ struct ExactMathT {
     // three / two np.float64 ** 2 at once: the table routine runs once per group for the lanes whose square is not provably the plain product (pow_exact.h)
     static MI_DEV void sq3(double a, double b, double c, double &ra, double &rb, double &rc) { mi_pow::square3<KASM>(g_pow_log, g_pow_exp, a, b, c, ra, rb, rc); }
     static MI_DEV void sq2(double a, double b, double &ra, double &rb) { mi_pow::square2<KASM>(g_pow_log, g_pow_exp, a, b, ra, rb); }
-    // the test alone, for a caller that collects the arguments which need the table routine (the two-role Pendulum rollout, engine.hip): true = `hi` IS x ** 2
+    // the test alone, for a caller that collects the arguments which need the table routine (the two-role Pendulum rollout, classic_kernels.h): true = `hi` IS x ** 2
     static MI_DEV bool sq_is_plain(double x, double &hi) { return mi_pow::square_is_plain(x, hi); }
     static MI_DEV bool sqf_is_plain(float x, float &hi) { return mi_pow::squaref_is_plain(x, hi); }  // ... and for np.float32 ** 2
 };
@@ -278,8 +278,8 @@ struct CartPoleT {
     static constexpr int S = 4, OBS = 4, N_ACTIONS = 2;
     static constexpr bool DISCRETE = true;
     static constexpr int ACT_KIND = MI_I64;
-    static constexpr int ROLLOUT_UNROLL = 1;  // engine.hip rollout_kernel: steps per unrolled loop body
-    static constexpr bool DUO_ROLLOUT = true;  // engine.hip rollout_duo_kernel (env + aux wavefront per 64 sub-environments): measured +13 %
+    static constexpr int ROLLOUT_UNROLL = 1;  // classic_kernels.h rollout_kernel: steps per unrolled loop body
+    static constexpr bool DUO_ROLLOUT = true;  // classic_kernels.h rollout_duo_kernel (env + aux wavefront per 64 sub-environments): measured +13 %
     static constexpr int DUO_CHUNK = 8;  // steps per phase of the two-role kernel (round 6, after the phase overhead left the wavefronts: +3.0 % over 4; round 4 measured -2.4 %)
     static constexpr bool DUO_ACT_AHEAD = false;  // (profiles/r06_act_prefetch_ab.txt)
     // The env role's episode bookkeeping (classic_kernels.h duo_env_step_word): pending autoreset, TimeLimit counter and the reset queue's `have` in ONE
@@ -375,7 +375,7 @@ struct CartPoleT {
         step_hooked(s, f, action, P, reward, terminated, t, false, [] {});
     }
     // ... with a caller's own rare work behind the step's one rare branch: `rare()` runs (in the out-of-line block, for the lanes with `extra` among
-    // those that enter it) after the accelerations.  engine.hip duo_env_step: the reset queue's refill, which only feeds the reset select after the step.
+    // those that enter it) after the accelerations.  classic_kernels.h duo_env_step: the reset queue's refill, which only feeds the reset select after the step.
     static constexpr bool RARE_HOOK = true;
     template <class F>
     static MI_DEV void step_hooked(double s[S], uint32_t &, Act action, const EnvParams &P, double &reward, bool &terminated, Trig &, bool extra, F &&rare) {
@@ -448,7 +448,7 @@ struct PendulumT {
     static constexpr int S = 2, OBS = 3;
     static constexpr bool DISCRETE = false;
     static constexpr int ROLLOUT_UNROLL = 1;
-    // engine.hip rollout_duo_kernel (env + aux wavefront per 64 sub-environments).  Round 4 measured -0.5 % (and +-0 with the reward on the aux role) and
+    // classic_kernels.h rollout_duo_kernel (env + aux wavefront per 64 sub-environments).  Round 4 measured -0.5 % (and +-0 with the reward on the aux role) and
     // concluded that the instruction count is the limit; it was the kernel's own phase overhead (round 6: lane masks carried through the role branches).
     // Now the step is cut in two balanced halves: the env role advances the state and takes the observation (one exact sincos) plus ONE of the reward's
     // three exact pow() calls and the angle's normalisation (the exact fmod), the aux role evaluates the rest of the reward -- two pow and the sums, from
@@ -550,7 +550,7 @@ struct PendulumT {
     }
     // (round 6, fourth cut: the float32 `u ** 2`.  powf's square is provably the plain product for 31 of 32 floats too -- pow_exact.h squaref_is_plain, checked
     //  over all 2^32 of them -- so the aux role tests a chunk's clipped actions first, runs the table routine once per PENDING action, all lanes side by side,
-    //  and reads the squares back in the step loop: engine.hip rollout_duo_kernel.)
+    //  and reads the squares back in the step loop: classic_kernels.h rollout_duo_kernel.)
     static constexpr bool AUX_ACT_SQUARE = M::EXACT && ACT_KIND == MI_F32;
     static MI_DEV float act_square_arg(Act action) { return (float)clip_torque(action); }
     static MI_DEV double aux_reward_squared(const double pre[AUX_PRE], float u_squared) {  // aux_reward with powf(u, 2) already evaluated
@@ -592,17 +592,17 @@ template <class M>
 struct AcrobotT {
     typedef M Math;
     // This environment's kernels need ~290 live registers: the compiler parks the overflow in AGPRs (v_accvgpr_read / write in the loop).  They
-    // are instantiated with ExactMathBuiltinFma (engine.hip AcrobotMath): no inline-asm Horner steps next to AGPR traffic (sincos_exact.h fma_k).
+    // are instantiated with ExactMathBuiltinFma (classic.hip AcrobotMath): no inline-asm Horner steps next to AGPR traffic (sincos_exact.h fma_k).
 #ifndef MI_ACROBOT_SPLIT_TERMINAL
 #define MI_ACROBOT_SPLIT_TERMINAL 1
 #endif
-    static constexpr bool SPLIT_TERMINAL = MI_ACROBOT_SPLIT_TERMINAL != 0;  // fused rollouts: integrate(), obs(), terminal_after_obs() (engine.hip lane_step_fused)
+    static constexpr bool SPLIT_TERMINAL = MI_ACROBOT_SPLIT_TERMINAL != 0;  // fused rollouts: integrate(), obs(), terminal_after_obs() (lane_step.h lane_step_fused)
     static constexpr bool USES_POW = true, USES_POWF = false;
     static constexpr int S = 4, OBS = 6, N_ACTIONS = 3;
     static constexpr bool DISCRETE = true;
     static constexpr int ACT_KIND = MI_I64;
-    static constexpr int ROLLOUT_UNROLL = 2;  // engine.hip rollout_kernel: steps per unrolled loop body
-    static constexpr bool DUO_ROLLOUT = false;  // engine.hip rollout_duo_kernel (env + aux wavefront per 64 sub-environments): measured +-0: 256 registers
+    static constexpr int ROLLOUT_UNROLL = 2;  // classic_kernels.h rollout_kernel: steps per unrolled loop body
+    static constexpr bool DUO_ROLLOUT = false;  // classic_kernels.h rollout_duo_kernel (env + aux wavefront per 64 sub-environments): measured +-0: 256 registers
     typedef int64_t Act;
 
     static MI_DEV void default_bounds(double &b0, double &b1) { b0 = -0.1, b1 = 0.1; }
@@ -719,8 +719,8 @@ struct MountainCarT {
     static constexpr int S = 2, OBS = 2, N_ACTIONS = 3;
     static constexpr bool DISCRETE = true;
     static constexpr int ACT_KIND = MI_I64;
-    static constexpr int ROLLOUT_UNROLL = 1;  // engine.hip rollout_kernel: steps per unrolled loop body
-    static constexpr bool DUO_ROLLOUT = true;  // engine.hip rollout_duo_kernel (env + aux wavefront per 64 sub-environments): measured +15 %
+    static constexpr int ROLLOUT_UNROLL = 1;  // classic_kernels.h rollout_kernel: steps per unrolled loop body
+    static constexpr bool DUO_ROLLOUT = true;  // classic_kernels.h rollout_duo_kernel (env + aux wavefront per 64 sub-environments): measured +15 %
     static constexpr int DUO_CHUNK = 8;  // steps per phase of the two-role kernel (+2.6 % over 4)
     static constexpr bool DUO_ACT_AHEAD = true;   // +3.5 % here; CartPole -0.7 %, Pendulum -1 %, MountainCarContinuous -3.4 %
     static constexpr bool REWARD_FROM_TERMINATED = true;  // -1.0 every step (step(), below)
@@ -791,7 +791,7 @@ struct MountainCarContinuousT {
     static constexpr int S = 2, OBS = 2;
     static constexpr bool DISCRETE = false;
     static constexpr int ROLLOUT_UNROLL = 1;
-    static constexpr bool DUO_ROLLOUT = true;  // engine.hip rollout_duo_kernel (env + aux wavefront per 64 sub-environments): measured +8 %
+    static constexpr bool DUO_ROLLOUT = true;  // classic_kernels.h rollout_duo_kernel (env + aux wavefront per 64 sub-environments): measured +8 %
     static constexpr int DUO_CHUNK = 8;  // steps per phase of the two-role kernel (+4.2 % over 4)
     static constexpr bool DUO_ACT_AHEAD = false;  // (profiles/r06_act_prefetch_ab.txt)
     static constexpr bool REWARD_FROM_TERMINATED = false;
@@ -936,7 +936,7 @@ struct MountainCarContinuousT {
 // Per-sub-environment physics: SyncVectorEnv.set_attr (vector/sync_vector_env.py:343-398) on the attributes the reference's step() reads.
 //
 // The *AttrT types are the environments above with every such attribute a per-lane value instead of a literal; everything else (reset, obs,
-// sampling) is inherited.  engine.hip loads the values once per launch (step_kernel: with the state, in the same trip to memory; rollout_kernel:
+// sampling) is inherited.  classic_kernels.h loads the values once per launch (step_kernel: with the state, in the same trip to memory; rollout_kernel:
 // before the step loop) from AttrDev -- an attribute whose bit is set in the wave-uniform mask comes from its row of [A][N] float64, the others
 // are the construction values (attr_default) -- and hands them to attrs_arrive(), which keeps them, plus what is invariant per lane, in the
 // lane's register struct Trig (derived from the base type's, so obs() and trig_invalidate() see what they always saw).  Reset reads no attribute.
@@ -1180,7 +1180,7 @@ struct AcrobotAttrs : AcrobotTrig {
     double dt, dt2, dt6; // rk4 over [0, dt] (acrobot.py:451-459): dt - 0, dt / 2.0, dt / 6.0
     double max_vel_1, max_vel_2;
     double noise;        // torque_noise_max
-    double u;            // the step's draw from the sub-environment's generator (engine.hip: STEP_DRAWS), read only where noise > 0
+    double u;            // the step's draw from the sub-environment's generator (lane_step.h: STEP_DRAWS), read only where noise > 0
     bool nips;           // book_or_nips == "nips"
 };
 template <class M>
@@ -1216,7 +1216,7 @@ struct AcrobotAttrT : AcrobotT<M> {
         t.noise = v[9], t.u = 0.0;
         t.nips = v[10] != 0.0;
     }
-    // The one classic step that draws from the sub-environment's own generator (acrobot.py:207-211): engine.hip takes one next_double for a lane
+    // The one classic step that draws from the sub-environment's own generator (acrobot.py:207-211): lane_step.h takes one next_double for a lane
     // that is about to step and says so here, and hands it over before the dynamics (lane_step / lane_step_fused: HasStepDraws).
     static constexpr bool STEP_DRAWS = true;
     static MI_DEV bool step_draws(const Trig &t) { return t.noise > 0; }  // (false for a NaN, like the reference's `if`)

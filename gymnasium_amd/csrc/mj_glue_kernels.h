@@ -1,5 +1,5 @@
 // mj_glue_kernels.h -- the per-lane kernels of the MuJoCo family around the simulator of mjx_kernels.h: the vectoriser's state machine, reward,
-// observation and statistics of one sub-environment per lane.  engine.hip instantiates them over the stock models, mjx_model.hip over the
+// observation and statistics of one sub-environment per lane.  mujoco.hip instantiates them over the stock models, mjx_model.hip over the
 // mjx::LaneModel env types, mjx_mass_model.hip over the mjx::MassLaneModel ones.
 #ifndef MI355ENV_MJ_GLUE_KERNELS_H
 #define MI355ENV_MJ_GLUE_KERNELS_H

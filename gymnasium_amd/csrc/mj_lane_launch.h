@@ -1,6 +1,6 @@
 // mj_lane_launch.h -- the launchers of the one-lane MuJoCo kernels (mj_glue_kernels.h, mj_wrapped_kernels.h) over the env types of one per-lane model template:
-// mjx::LaneModel (mjx_model.hip, namespace mi_mjmodel) or mjx::MassLaneModel (mjx_mass_model.hip, namespace mi_mjmass).  Each of the two units
-// instantiates the kernels it launches; engine_types.h declares the plain functions engine.hip calls.
+// the stock model itself (mujoco.hip), mjx::LaneModel (mjx_model.hip, namespace mi_mjmodel) or mjx::MassLaneModel (mjx_mass_model.hip, namespace mi_mjmass).  Each of the three units
+// instantiates the kernels it launches; engine_types.h declares the plain functions mujoco.hip calls for the other two.
 #ifndef MI355ENV_MJ_LANE_LAUNCH_H
 #define MI355ENV_MJ_LANE_LAUNCH_H
 #include "mj_glue_kernels.h"

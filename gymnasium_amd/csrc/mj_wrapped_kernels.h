@@ -9,7 +9,7 @@
 // last trip: that trip FINALISES it -- outputs, episode bookkeeping, LaneStats, a SAME_STEP autoreset, the kNeedsReset flag -- and sets the skip bit of
 // its inner-step word, which the cooperative physics kernel takes as its `meta` (mjx_physics.h Args: a row whose masked bit is set retires its lanes)
 // and the later trips' glue tests first.  The flag word of the state (DevEnv::meta) carries nothing new.
-// engine.hip instantiates mj_trip_kernel over the stock models, mjx_model.hip and mjx_mass_model.hip over the per-lane-model env types; the plain kernels
+// mujoco.hip instantiates mj_trip_kernel over the stock models, mjx_model.hip and mjx_mass_model.hip over the per-lane-model env types; the plain kernels
 // of mj_glue_kernels.h are not touched.
 #ifndef MI355ENV_MJ_WRAPPED_KERNELS_H
 #define MI355ENV_MJ_WRAPPED_KERNELS_H

@@ -339,7 +339,7 @@ struct Sim {
         const int b = lane + 1;
         const bool isbody = b < NB;
         const int bi = isbody ? b : 1;
-        const int depth = M::body_depth[bi], p = M::body_parentid[bi], ja = M::body_jntadr[bi], jn = jnum(bi);
+        const int jn = jnum(bi);
         // (round 3) The joints of a body act in the body's own static frame F0 (parent pose o body_pos / body_quat): with pose = F0 o (pl, ql),
         //   anchor_j = F0 (pl + R(ql) jnt_pos_j),  axis_j = F0 R(ql) jnt_axis_j,  hinge: ql <- ql o q(axis_j, theta_j), pl <- anchor_j^loc - R(ql) jnt_pos_j,
         //   slide: pl += axis_j^loc theta_j
@@ -354,7 +354,6 @@ struct Sim {
 #pragma unroll
             for (int jj = 0; jj < M::MAXJPB; jj++) {
                 if (jj < jn) {
-                    const int j = ja + jj;
                     double Rm[9], qq[4], t[3];
                     quat_to_mat(Rm, ql);
                     rot_vec(t, Rm, jpos(bi, jj));
@@ -523,7 +522,7 @@ struct Sim {
         const int b = lane + 1;
         const bool isbody = b < NB;
         const int bi = isbody ? b : 1;
-        const int depth = M::body_depth[bi], p = M::body_parentid[bi], ja = M::body_jntadr[bi], jn = jnum(bi);
+        const int p = M::body_parentid[bi], jn = jnum(bi);
         // cvel and cacc live in ONE frame (the com-based world frame), so a body's value is its parent's plus the contributions of its own
         // joints: two prefix sums over the tree, done by pointer jumping (see kinematics()) -- first the velocities (a joint's cdof_dot needs the
         // velocity just before it), then the accelerations.  Each body walks its own joint chain ONCE instead of the wavefront walking the

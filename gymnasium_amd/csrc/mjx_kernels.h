@@ -1,4 +1,4 @@
-// mjx_kernels.h -- the MuJoCo-family environments as lockstep kernels (included through mj_glue_kernels.h by engine.hip, which owns the C ABI, and by mjx_model.hip).
+// mjx_kernels.h -- the MuJoCo-family environments as lockstep kernels (included through mj_glue_kernels.h by mujoco.hip, mjx_model.hip and mjx_mass_model.hip).
 //
 // Per-env glue restated from the reference's Python (one lane = one scalar env):
 //   gymnasium/envs/mujoco/mujoco_env.py:132-155,172-187   set_state / do_simulation / reset

@@ -1,7 +1,7 @@
 // mjx_model.hip -- the one-lane MuJoCo kernels of an env with per-sub-environment model fields (mi_set_model_field) as a translation unit of their
 // own: namespace mi_mjmodel, the launchers of mj_step_kernel / mj_rollout_kernel (mj_glue_kernels.h, through mj_lane_launch.h) over the mjx::LaneModel
-// env types; engine_types.h declares them and says why.  A unit of its own so that its 77 kernels compile beside engine.o instead of after it.  Default
-// flag set, like engine.hip's own one-lane kernels.  (An env with a body mass scale runs the kernels of mjx_mass_model.hip instead.)
+// env types; engine_types.h declares them and says why.  A unit of its own so that its 77 kernels compile beside the stock models' (mujoco.hip) instead of after them.  Default
+// flag set, like mujoco.hip's one-lane kernels.  (An env with a body mass scale runs the kernels of mjx_mass_model.hip instead.)
 // As everywhere on this path the parity with `mujoco` is unpinned; the CPU oracle is the reference for these fields.
 #include "mj_lane_launch.h"
 

@@ -1,6 +1,6 @@
 // mjx_physics.h -- the cooperative physics kernel (mjx_coop.h) behind a plain launch function, so that it can live in its own
 // translation units: physics16.hip (16-lane groups: Ant, HalfCheetah) and physics32.hip (32-lane groups: Humanoid, HumanoidStandup) are
-// compiled with different instruction-scheduler settings than engine.hip (gymnasium_amd/csrc/build.py TU_FLAGS).
+// compiled with different instruction-scheduler settings than mujoco.hip, which launches them (gymnasium_amd/csrc/build.py TU_FLAGS).
 //
 // Reference call sites replaced: gymnasium/envs/mujoco/mujoco_env.py:150 (mj_step(nstep = frame_skip)) and :155 (mj_rnePostConstraint),
 // for every sub-environment that takes a real step in this vector step.

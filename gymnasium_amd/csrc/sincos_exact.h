@@ -190,7 +190,7 @@ MI_SC_DEV double do_sincos(const double *T, double a, double da, int n) {
     return (n & 2) ? -r : r;
 }
 
-// T: the table (kTable, or a copy of it in faster memory: the kernels of engine.hip keep one in LDS)
+// T: the table (kTable, or a copy of it in faster memory: the kernels of classic_kernels.h keep one in LDS)
 MI_SC_DEV double sin_exact(const double *T, double x) {
     const uint32_t k = (uint32_t)(bits(x) >> 32) & 0x7fffffffu;
     if (k < 0x3e500000u) return x;                                           // |x| < 2^-26

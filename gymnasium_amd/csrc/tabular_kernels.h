@@ -1,7 +1,7 @@
 // tabular_kernels.h -- the ToyText family's device code: the finite MDPs (FrozenLake, CliffWalking, Taxi with and without the fickle passenger) and
 // Blackjack, which rides on the same kernels.  The per-step kernels (tab_step_kernel, tab_reset_kernel), the fused rollouts (tab_rollout_kernel per
 // kind, tab_rollout_lean_kernel with the table in LDS, bj_rollout_lean_kernel) and what their launch sites need (TabStepPtrs, TabLeanCell,
-// tab_lean_lds_bytes).  Included by engine.hip only, which holds the host code that launches them: they run on the default scheduler (max-ILP cost
+// tab_lean_lds_bytes).  Included by tabular.hip only, which holds the host code that launches them: they run on the default scheduler (max-ILP cost
 // them 1 - 2 %, profiles/r04_maxilp_classic.txt).
 #ifndef MI355ENV_TABULAR_KERNELS_H
 #define MI355ENV_TABULAR_KERNELS_H

@@ -365,7 +365,7 @@ bool steps_layout(int T, int rows, int dim, StepsLayout *l) {
     l->bytes = (at + 255) & ~(size_t)255;
     return true;
 }
-void swap_sets(mi_running_stats *s) {  // steps_scan wrote the second buffer set (as the step epilogue does, engine.hip epilogue_swap)
+void swap_sets(mi_running_stats *s) {  // steps_scan wrote the second buffer set (as the step epilogue does, classic.hip epilogue_swap)
     double *t;
     t = s->mean, s->mean = s->mean2, s->mean2 = t;
     t = s->var, s->var = s->var2, s->var2 = t;

@@ -8,7 +8,7 @@ struct mi_running_stats {
     int device, dim, dtype;  // dtype of the running mean / var: MI_F32 or MI_F64 (what NumPy's promotion gives in the reference)
     double *mean, *var;      // [dim] device, values always representable in `dtype`
     double *count;           // [1] device
-    double *mean2, *var2, *count2;  // a second buffer set: the step epilogue (engine.hip) writes the updated statistics there while the
+    double *mean2, *var2, *count2;  // a second buffer set: the step epilogue (classic_kernels.h) writes the updated statistics there while the
                                     // other workgroups still read the first, then the host swaps the two sets
     double *partial;         // [2][kPartials] device scratch
     int *flag;               // [1] device: number of rows of the last update (0 = the update was skipped)

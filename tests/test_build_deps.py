@@ -18,11 +18,26 @@ def closure(unit):  # (generated/mjx_models.h is a committed file: nothing to ge
 
 def test_closure_of_engine():
     deps = closure("engine.hip")
-    for name in ("engine_types.h", "mj_glue_kernels.h", "ziggurat_tables.h", os.path.join("generated", "mjx_models.h"),
-                 os.path.join("..", "..", "include", "mi355env.h")):
+    for name in ("engine_types.h", os.path.join("..", "..", "include", "mi355env.h")):
         assert name in deps, name
     assert not any(f.endswith(".hip") for f in deps)
-    assert "tabular_kernels.h" in deps and "classic_kernels.h" not in deps and "lane_step.h" not in deps
+    # the C ABI holds no environment family's kernels: those are mujoco.hip's, tabular.hip's and classic.hip's
+    for name in ("tabular_kernels.h", "mj_glue_kernels.h", "mj_wrapped_kernels.h", "mjx_physics.h", "mjx_coop.h", "mjx_core.h",
+                 os.path.join("generated", "mjx_models.h"), "classic_kernels.h", "lane_step.h"):
+        assert name not in deps, name
+
+
+def test_closure_of_mujoco():
+    deps = closure("mujoco.hip")
+    for name in ("mj_glue_kernels.h", "mj_wrapped_kernels.h", "mjx_physics.h", "mj_lane_launch.h", os.path.join("generated", "mjx_models.h")):
+        assert name in deps, name
+    assert "tabular_kernels.h" not in deps and "classic_kernels.h" not in deps and not any(f.endswith(".hip") for f in deps)
+
+
+def test_closure_of_tabular():
+    deps = closure("tabular.hip")
+    assert "tabular_kernels.h" in deps and "classic_kernels.h" not in deps
+    assert not any(os.path.basename(f).startswith(("mjx_", "mj_")) for f in deps), deps
 
 
 def test_closure_of_classic():
@@ -81,7 +96,9 @@ def test_touching_a_header_makes_its_includers_stale(copied_tree, header):
     expected = {unit for unit in B.SOURCES if os.path.normpath(header) in closure(unit)}  # (closure() reads the tree itself: computed once per unit)
     assert expected, header
     assert stale_units(copied_tree) == expected
-    if header in ("mj_glue_kernels.h", "lane_common.h"):
+    if header == "mj_glue_kernels.h":
+        assert {"mujoco.hip", "mjx_model.hip", "mjx_mass_model.hip"} <= expected and "engine.hip" not in expected
+    if header == "lane_common.h":
         assert {"engine.hip", "mjx_model.hip"} <= expected
     if header == "wrappers_internal.h":
         assert {"wrappers.hip"} <= expected and "mjx_model.hip" not in expected
@@ -90,7 +107,7 @@ def test_touching_a_header_makes_its_includers_stale(copied_tree, header):
     if header in ("classic_kernels.h", "lane_step.h"):
         assert "classic.hip" in expected and "engine.hip" not in expected
     if header == "tabular_kernels.h":
-        assert "engine.hip" in expected and "classic.hip" not in expected
+        assert expected == {"tabular.hip"}
 
 
 def test_touching_a_unit_or_the_build_script(copied_tree):

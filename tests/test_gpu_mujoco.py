@@ -422,3 +422,21 @@ def test_non_default_constructor_kwargs_vs_oracle(env_id, k, oracle_factory):
         if t % 4 == 3:  # re-synchronise (contact dynamics amplify last-bit differences, like the windowed parity test does)
             gpu.set_state(*cpu.get_state())
     gpu.close(), cpu.close()
+
+
+@pytest.mark.parametrize("env_id", ["Hopper-v5", "Ant-v5"], ids=["one_lane", "cooperative"])
+def test_disabled_autoreset_steps_like_next_step_until_an_episode_ends(env_id):
+    """DISABLED has no rollout launch; its step kernel over the stock models (mujoco.hip: mj_step_kernel<E, MI_AUTORESET_DISABLED, COOP>, one-lane and behind
+    the cooperative physics) equals the NEXT_STEP one up to and including the step in which the first episode ends.  300 sub-environments: two
+    workgroups, the second partial; max_episode_steps = 2: every row truncates in the second step."""
+    kw = dict(num_envs=300, max_episode_steps=2)
+    a = gymnasium_amd.make_vec(env_id, autoreset_mode="Disabled", **kw)
+    b = gymnasium_amd.make_vec(env_id, autoreset_mode="NextStep", **kw)
+    a.reset(seed=5), b.reset(seed=5)
+    b.action_space.seed(3)
+    for t in range(2):
+        act = b.action_space.sample()
+        ra, rb = a.step(act), b.step(act)
+        assert all(np.array_equal(x, y) for x, y in zip(ra[:4], rb[:4])), t
+    assert ra[3].all() and not ra[2].all()
+    a.close(), b.close()

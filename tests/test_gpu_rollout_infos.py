@@ -176,6 +176,80 @@ def test_one_lane_simulator_rollout_infos_equal_stacked_steps(mode, monkeypatch)
     _rollout_equals_steps("HalfCheetah-v5", 5, 6, 3, mode, False, True)
 
 
+# -- mi_rollout_infos == T x mi_step on the test's own device buffers ---------------------------------------------------------------------------
+def _raw_rollout_equals_raw_steps(env_id, mode, sample, extras, T, n=300, max_episode_steps=2, **kw):
+    """One mi_rollout_infos on one env against T mi_step calls on a second, below the Python env: the trajectory and the rows of `extras`
+    (a rollout writes zeros where a step leaves the row alone, so the steps' arrays start as zeros), then state, generators and statistics.  300
+    sub-environments: two workgroups, the second partial; max_episode_steps = 2: a truncation and an autoreset inside three steps."""
+    import torch
+
+    a, b = (gymnasium_amd.make_vec(env_id, num_envs=n, max_episode_steps=max_episode_steps, autoreset_mode=mode, output="torch", **kw) for _ in range(2))
+    a.reset(seed=cases.RESET_SEED), b.reset(seed=cases.RESET_SEED)
+    ea, eb = a._engine, b._engine
+    discrete = ea.act_dtype is np.int64
+    acts = None if sample else cases.caller_actions(a, T)
+    if sample:
+        words = _native.pcg_words(np.random.default_rng(cases.ACTION_SEED))
+        ea.action_seed(words), eb.action_seed(words)
+
+    def buffers():
+        def z(shape, dtype):
+            return torch.zeros((T,) + tuple(shape), dtype=dtype, device="cuda")
+
+        info = (n, max(ea.info_dim, 1))
+        traj = {"obs": z(a._obs_shape, a._obs_tdtype), "reward": z((n,), torch.float64), "terminated": z((n,), torch.bool), "truncated": z((n,), torch.bool),
+                "actions_out": z((n,) if discrete else (n, ea.act_dim), torch.int64 if discrete else torch.float32)}
+        ex = {"final_obs": z(a._obs_shape, a._obs_tdtype), "episode_return": z((n,), torch.float64), "episode_length": z((n,), torch.int32),
+              "info": z(info, torch.float64), "final_info": z(info, torch.float64)}
+        return traj, {k: ex[k] for k in extras}
+
+    (ta, xa), (tb, xb) = buffers(), buffers()
+    a._bind_stream(), b._bind_stream()
+    ea.rollout(T, None if sample else acts.data_ptr(), ta["actions_out"].data_ptr() if sample else None, ta["obs"].data_ptr(), ta["reward"].data_ptr(),
+               ta["terminated"].data_ptr(), ta["truncated"].data_ptr(), extra={k: v.data_ptr() for k, v in xa.items()})
+    info_row = torch.zeros((n, max(ea.info_dim, 1)), dtype=torch.float64, device="cuda")
+    for t in range(T):
+        row = {k: v[t].data_ptr() for k, v in xb.items()}
+        if "final_info" in row:  # (a step's final_info is its info row of the finishing transition: a step that asks for one has an info row)
+            row.setdefault("info", info_row.data_ptr())
+        eb.step(None if sample else acts[t].data_ptr(), tb["obs"][t].data_ptr(), tb["reward"][t].data_ptr(), tb["terminated"][t].data_ptr(),
+                tb["truncated"][t].data_ptr(), loc=_native.MI_DEVICE, actions_out=tb["actions_out"][t].data_ptr() if sample else None, **row)
+    a.synchronize(), b.synchronize()
+    for name in ta:
+        assert torch.equal(ta[name], tb[name]), name
+    for name in xa:
+        assert torch.equal(xa[name], xb[name]), name
+    done = _np(ta["terminated"] | ta["truncated"])
+    assert done.any() and not done.all()
+    if "final_obs" in xa or "final_info" in xa:
+        assert any(xa[k].any() for k in ("final_obs", "final_info") if k in xa), "no finished episode left a final row"
+    assert all(np.array_equal(x, y) for x, y in zip(a.get_state(), b.get_state())) and np.array_equal(a.get_rng_state(), b.get_rng_state())
+    assert a.statistics() == b.statistics()
+    a.close(), b.close()
+
+
+# the five forms of tab_rollout_kernel (tabular.hip mi_tabular::rollout): Blackjack; the fickle Taxi and a plain table, each read from HBM (T < 8) and from LDS
+TABULAR_FORMS = [("Blackjack-v1", {}, 3), ("Taxi-v4", {"fickle_passenger": True}, 3), ("Taxi-v4", {"fickle_passenger": True}, 8), ("FrozenLake-v1", {}, 3),
+                 ("FrozenLake-v1", {}, 8)]
+
+
+@pytest.mark.parametrize("sample", [False, True], ids=["caller_actions", "device_policy"])
+@pytest.mark.parametrize("mode", cases.MODES)
+@pytest.mark.parametrize("form", TABULAR_FORMS, ids=["blackjack", "fickle", "fickle_lds", "plain", "plain_lds"])
+def test_toytext_rollout_extras_equal_stacked_steps(form, mode, sample):
+    env_id, kw, T = form
+    extras = ["episode_return", "episode_length"] + ([] if env_id.startswith("Blackjack") else ["info"])  # (Blackjack has no info columns)
+    if mode == "SameStep":
+        extras += ["final_obs"] + ([] if env_id.startswith("Blackjack") else ["final_info"])
+    _raw_rollout_equals_raw_steps(env_id, mode, sample, extras, T, **kw)
+
+
+def test_cooperative_rollout_with_final_info_but_no_info_array():
+    """The T-launch rollout of the cooperative robots (mujoco.hip launch_mj_rollout_coop): the finishing step's info reaches final_info through the env's own
+    staging row when the caller keeps no info array."""
+    _raw_rollout_equals_raw_steps("Ant-v5", "SameStep", False, ["final_info"], 3)
+
+
 # -- scoping ---------------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("mode", cases.MODES)
 def test_default_rollout_is_unchanged_also_after_a_rollout_with_infos(mode):

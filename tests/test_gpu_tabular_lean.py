@@ -10,11 +10,14 @@ Taxi with rain (three outcomes x 3 000 cells do not fit into LDS) exercises the 
 Blackjack-v1 has its own branch-free rollout (bj_rollout_lean_kernel): the same checks for the three rule sets, and once more with every third
 lane-step forced through the kernel's general routines (MI355ENV_BJ_FORCE_SLOW: the path a rejected draw or a dealer's seventh card takes).
 """
+import functools
+
 import numpy as np
 import pytest
 
 import gymnasium_amd
 import parity_suite as ps
+from gymnasium_amd.envs.toy_text import TabularVectorEnv
 
 pytestmark = pytest.mark.gpu
 
@@ -41,8 +44,9 @@ def _run(key, n, T, oracle_factory, max_episode_steps=None, return_actions=True,
     eid, kw = (key, {}) if isinstance(key, str) and key.startswith("Blackjack") else (key if isinstance(key, tuple) else ps.toytext_spec(key))
     if max_episode_steps is not None:
         kw = dict(kw, max_episode_steps=max_episode_steps)
-    gpu = gymnasium_amd.make_vec(eid, num_envs=n, output="torch", **kw)
-    cpu = gymnasium_amd.make_vec(eid, num_envs=n, _engine_factory=oracle_factory, **kw)
+    make = eid if callable(eid) else functools.partial(gymnasium_amd.make_vec, eid)  # (a vector env class of the test's own: _SmallMdp)
+    gpu = make(num_envs=n, output="torch", **kw)
+    cpu = make(num_envs=n, _engine_factory=oracle_factory, **kw)
     og, _ = gpu.reset(seed=11)
     oc, _ = cpu.reset(seed=11)
     assert _eq(og, oc)
@@ -94,6 +98,39 @@ def test_lean_rollout_short_time_limit(key, oracle_factory):
 @pytest.mark.parametrize("key", ["frozenlake8x8", "taxi"])
 def test_lean_rollout_without_action_array_and_twice(key, oracle_factory):
     _run(key, 500, 16, oracle_factory, return_actions=False, rollouts=2)
+
+
+class _SmallMdp(TabularVectorEnv):
+    """A 7-state table of the test's own, so that every template argument of tab_rollout_lean_kernel<KL, FULL, ONE_START, APOW2> is reached in both
+    values (tabular.hip mi_tabular::rollout; the stock envs never pair three outcomes or one start state with a number of actions that is no power of
+    two): `outcomes` outcomes per (state, action) with the exactly representable probabilities 1, or 1/2, 1/4, 1/4; every episode starts in state 2,
+    or in one of three states; state 6 terminates."""
+
+    def __init__(self, actions, outcomes, starts, **kw):
+        self._shape = (actions, outcomes, starts)
+        super().__init__(**kw)
+
+    def _build(self):
+        nA, K, starts = self._shape
+        nS, probs = 7, ((1.0,) if K == 1 else (0.5, 0.25, 0.25))
+        nxt = lambda s, a, k: (3 * s + a + 2 * k + 1) % nS
+        P = [[[(p, nxt(s, a, k), float(a + k), nxt(s, a, k) == nS - 1) for k, p in enumerate(probs)] for a in range(nA)] for s in range(nS)]
+        isd = np.zeros(nS)
+        if starts == 1:
+            isd[2] = 1.0
+        else:
+            isd[[1, 3, 5]] = (0.25, 0.5, 0.25)
+        return P, isd
+
+
+@pytest.mark.parametrize("full", [True, False], ids=["all_arrays", "no_action_array"])
+@pytest.mark.parametrize("starts", [1, 3])
+@pytest.mark.parametrize("actions", [4, 3])
+@pytest.mark.parametrize("outcomes", [1, 3])
+def test_every_lean_rollout_form_vs_oracle(outcomes, actions, starts, full, oracle_factory):
+    """2 x 2 x 2 x 2 = the 16 instantiations.  300 sub-environments: two workgroups, the second partial; T = 3 with max_episode_steps = 2: a truncation
+    and an autoreset inside the rollout."""
+    _run((functools.partial(_SmallMdp, actions, outcomes, starts), {}), 300, 3, oracle_factory, max_episode_steps=2, return_actions=full)
 
 
 BLACKJACK = [("Blackjack-v1", {}), ("Blackjack-v1", {"natural": True}), ("Blackjack-v1", {"sab": True})]

@@ -87,7 +87,7 @@ def test_cooperative_mujoco_kernels_keep_their_lds_and_register_budget():
 
 
 def test_two_role_rollout_kernels_fit_two_wavefronts_per_simd():
-    """rollout_duo_kernel runs an env and an aux wavefront of the same 64 sub-environments on one SIMD (engine.hip): a workgroup is 8 wavefronts on the 4
+    """rollout_duo_kernel runs an env and an aux wavefront of the same 64 sub-environments on one SIMD (classic.hip): a workgroup is 8 wavefronts on the 4
     SIMDs of a CU, so each wavefront may use at most half the register file, nothing may spill, and the rings must fit the CU's LDS."""
     from kernel_resources import resources
 
@@ -102,7 +102,7 @@ def test_two_role_rollout_kernels_fit_two_wavefronts_per_simd():
 
 def test_branch_free_tabular_rollouts_are_instantiated_and_stay_in_registers(kernels):
     """tab_rollout_lean_kernel<KL, FULL, ONE_START, APOW2> (16 instantiations) and bj_rollout_lean_kernel<FULL> (2): what mi_rollout launches for the collector's
-    ToyText configurations (engine.hip).  None may spill, and all stay within 128 VGPRs (four wavefronts per SIMD at the batch sizes beyond the benchmark's)."""
+    ToyText configurations (tabular.hip mi_tabular::rollout).  None may spill, and all stay within 128 VGPRs (four wavefronts per SIMD at the batch sizes beyond the benchmark's)."""
     from kernel_resources import resources
 
     lean = [n for n in kernels if "tab_rollout_lean_kernel<" in n]
@@ -112,6 +112,24 @@ def test_branch_free_tabular_rollouts_are_instantiated_and_stay_in_registers(ker
         if "rollout_lean_kernel" in r["name"]:
             assert r.get("vgpr_spill_count", 0) == 0 and r.get("private_segment_fixed_size", 0) == 0, r["name"]
             assert r["vgpr_count"] <= 128, f"{r['name']}: {r['vgpr_count']} VGPRs"
+
+
+def test_engine_unit_holds_only_the_family_independent_kernels():
+    """engine.hip is the C ABI: its code object (the one with seed_words_kernel, which no header defines) holds the six family-independent kernels and no
+    environment family's -- those are instantiated in classic.hip, mujoco.hip (mjx_model.hip, mjx_mass_model.hip) and tabular.hip."""
+    from kernel_resources import READELF, extract_all
+
+    units = []
+    for co in extract_all(LIB):  # (one code object per translation unit)
+        with tempfile.NamedTemporaryFile(suffix=".co") as f:
+            f.write(co), f.flush()
+            table = subprocess.run([READELF, "--symbols", "--wide", f.name], capture_output=True, text=True, check=True).stdout
+        descriptors = [line.split()[-1][:-3] for line in table.splitlines() if line.rstrip().endswith(".kd")]  # a kernel's descriptor: <symbol>.kd
+        names = subprocess.run(["c++filt"], input="\n".join(descriptors), capture_output=True, text=True).stdout.splitlines()
+        units.append({re.sub(r"\(.*", "", n.replace("(anonymous namespace)::", "")).split()[-1] for n in names})
+    engine = [u for u in units if "seed_words_kernel" in u]
+    assert len(engine) == 1, [sorted(u)[:3] for u in engine]
+    assert engine[0] == {"seed_words_kernel", "seed_sequence_kernel", "sticky_clear_kernel", "act_init_kernel", "act_sample_kernel", "model_transpose_kernel"}, sorted(engine[0])
 
 
 def test_acrobot_rollout_kernels_fit_two_wavefronts_per_simd_and_keep_their_constants_in_registers(kernels):
