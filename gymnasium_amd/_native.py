@@ -63,6 +63,8 @@ HOST_SYMBOLS += ["get_model_derived"]
 # The return of K candidate action sequences from every sub-environment's present state (mi_lookahead; added to ABI 10, which it leaves as it is): product
 # library only -- HipVectorEnv.lookahead tells the backends apart by whether the entry point is bound.
 HOST_SYMBOLS += ["lookahead"]
+# ... and of K candidate POLICIES evaluated in the lane (mi_lookahead_policy; added to ABI 10 likewise): product library only, told apart the same way.
+HOST_SYMBOLS += ["lookahead_policy"]
 MODEL_BODY_MASS_SCALE = 4
 MODEL_DERIVED_DOF_INVWEIGHT0, MODEL_DERIVED_BODY_INVWEIGHT0, MODEL_DERIVED_MEANINERTIA = 0, 1, 2  # MI_MODEL_DERIVED_*
 WRAPPER_SYMBOLS = ["rms_create", "rms_destroy", "rms_get", "rms_set", "normalize_observation", "normalize_reward", "clip_reward", "set_step_epilogue"]
@@ -117,6 +119,13 @@ class MiLookaheadIO(C.Structure):
     """mi_lookahead_io (include/mi355env.h): device pointers; every output nullable."""
     _fields_ = [("struct_size", C.c_int32), ("actions_dtype", C.c_int32), ("actions", C.c_void_p), ("returns", C.c_void_p), ("steps", C.c_void_p),
                 ("terminated", C.c_void_p), ("truncated", C.c_void_p), ("final_obs", C.c_void_p), ("horizon", C.c_int32), ("candidates", C.c_int32),
+                ("gamma", C.c_double)]
+
+
+class MiLookaheadPolicyIO(C.Structure):
+    """mi_lookahead_policy_io (include/mi355env.h): device pointers; every output nullable."""
+    _fields_ = [("struct_size", C.c_int32), ("params", C.c_void_p), ("returns", C.c_void_p), ("steps", C.c_void_p), ("terminated", C.c_void_p),
+                ("truncated", C.c_void_p), ("final_obs", C.c_void_p), ("horizon", C.c_int32), ("candidates", C.c_int32), ("hidden", C.c_int32),
                 ("gamma", C.c_double)]
 
 
@@ -260,6 +269,10 @@ class NativeLib:
             try:
                 self.lookahead = f("lookahead", [vp, C.POINTER(MiLookaheadIO)], i32)
             except ImportError:  # (likewise: HipVectorEnv.lookahead refuses)
+                pass
+            try:
+                self.lookahead_policy = f("lookahead_policy", [vp, C.POINTER(MiLookaheadPolicyIO)], i32)
+            except ImportError:  # (likewise: HipVectorEnv.lookahead_policy refuses)
                 pass
 
     def _fn(self, name, argtypes, restype):
@@ -512,6 +525,15 @@ class Engine:
         io.returns, io.steps, io.terminated, io.truncated, io.final_obs = _ptr(returns), _ptr(steps), _ptr(terminated), _ptr(truncated), _ptr(final_obs)
         io.horizon, io.candidates, io.gamma = int(horizon), int(candidates), float(gamma)
         self.lib.check(self.lib.lookahead(self.handle, C.byref(io)))
+
+    def lookahead_policy(self, params, hidden: int, horizon: int, candidates: int, gamma: float, returns=None, steps=None, terminated=None, truncated=None,
+                         final_obs=None):
+        """mi_lookahead_policy: device addresses; params [candidates][P] float32, every output [candidates][num_envs][...] or None."""
+        io = MiLookaheadPolicyIO()
+        io.struct_size, io.params, io.hidden = C.sizeof(MiLookaheadPolicyIO), _ptr(params), int(hidden)
+        io.returns, io.steps, io.terminated, io.truncated, io.final_obs = _ptr(returns), _ptr(steps), _ptr(terminated), _ptr(truncated), _ptr(final_obs)
+        io.horizon, io.candidates, io.gamma = int(horizon), int(candidates), float(gamma)
+        self.lib.check(self.lib.lookahead_policy(self.handle, C.byref(io)))
 
     def stats(self) -> dict:
         st = MiStats()

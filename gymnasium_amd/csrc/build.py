@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # The translation units, each compiled on its own and linked into one library; what a unit is and why it is one stands at its head.  A unit's
 # dependencies are the quoted includes it reaches (includes()), so there is no header list to keep.
 SOURCES = ["engine.hip", "physics16.hip", "physics32.hip", "wrappers.hip", "classic.hip", "mujoco.hip", "tabular.hip", "mjx_model.hip", "mjx_mass_model.hip", "action_mask.hip",
-           "action_wrappers.hip", "observation_wrappers.hip", "per_env_normalize.hip", "stateful_observation.hip", "discretize.hip", "lookahead.hip"]
+           "action_wrappers.hip", "observation_wrappers.hip", "per_env_normalize.hip", "stateful_observation.hip", "discretize.hip", "lookahead.hip", "lookahead_policy.hip"]
 OUT = os.path.join(HERE, "libmi355env.so")
 ARCH = "gfx950"
 # Per translation unit, on top of FLAGS: LLVM's iterative GCN scheduler for the cooperative physics kernels.  With ONE wavefront per SIMD it
@@ -47,7 +47,8 @@ NO_MLICM = ["-mllvm", "-disable-machine-licm"]
 MAXILP = ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]
 # Every unit not named here builds with FLAGS alone (the default flag set its head refers to).
 # lookahead.hip: the same per-lane step in a loop of its own (mi_lookahead), one wavefront per SIMD at 65 536 candidates: classic.hip's flags.
-TU_FLAGS = {"physics16.hip": ITERATIVE + SINK, "physics32.hip": ITERATIVE + SINK, "classic.hip": MAXILP, "lookahead.hip": MAXILP}
+# lookahead_policy.hip: that loop with the policy evaluated in the lane (mi_lookahead_policy): lookahead.hip's reason.
+TU_FLAGS = {"physics16.hip": ITERATIVE + SINK, "physics32.hip": ITERATIVE + SINK, "classic.hip": MAXILP, "lookahead.hip": MAXILP, "lookahead_policy.hip": MAXILP}
 FLAGS = ["-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-fvisibility=hidden", "-Wall", "-Wno-unused-function", "-Wno-missing-braces"]
 
 

@@ -1194,6 +1194,30 @@ int mi_lookahead(mi_vecenv *v, const mi_lookahead_io *io) {
                                 io->truncated, static_cast<float *>(io->final_obs));
 }
 
+// ... and of K candidate POLICIES, evaluated in the lane from the observation of every step (include/mi355env.h mi_lookahead_policy; device side:
+// lookahead_policy.hip).  mi_lookahead's refusals and state errors, in its order.
+int mi_lookahead_policy(mi_vecenv *v, const mi_lookahead_policy_io *io) {
+    if (!v || !io) return fail(MI_ERR_INVALID_ARGUMENT, "null argument");
+    if (io->struct_size != (int32_t)sizeof(mi_lookahead_policy_io))
+        return fail(MI_ERR_INVALID_ARGUMENT, "mi_lookahead_policy: struct_size != sizeof(mi_lookahead_policy_io)");
+    if (v->cfg.kind < 0 || v->cfg.kind >= kClassicKinds) return fail(MI_ERR_UNSUPPORTED, "mi_lookahead_policy: the five classic-control kinds only");
+    if (v->shared_rng) return fail(MI_ERR_UNSUPPORTED, "mi_lookahead_policy: not with MI_CFG_SHARED_RNG (CartPoleVectorEnv has no sub-environment generators to copy)");
+    if (v->cfg.reserved[0] & MI_CFG_FAST_MATH) return fail(MI_ERR_UNSUPPORTED, "mi_lookahead_policy: not with MI_CFG_FAST_MATH");
+    if (v->wrap_on) return fail(MI_ERR_UNSUPPORTED, "mi_lookahead_policy: not with mi_set_step_wrappers / mi_set_max_and_skip on");
+    if (v->has_epi) return fail(MI_ERR_UNSUPPORTED, "mi_lookahead_policy: not with a step epilogue attached (mi_set_step_epilogue)");
+    if (v->has_pending) return fail(MI_ERR_STATE, "an asynchronous step is pending (mi_step_wait)");
+    if (!v->was_reset) return fail(MI_ERR_STATE, "lookahead_policy before reset");
+    if (!io->params) return fail(MI_ERR_INVALID_ARGUMENT, "mi_lookahead_policy: params must not be NULL");
+    if (io->hidden < 0 || io->hidden > 256) return fail(MI_ERR_INVALID_ARGUMENT, "mi_lookahead_policy: hidden must be in [0, 256]");
+    if (io->horizon < 1 || io->candidates < 1) return fail(MI_ERR_INVALID_ARGUMENT, "mi_lookahead_policy: horizon and candidates must be >= 1");
+    if ((int64_t)io->candidates * (int64_t)v->cfg.num_envs >= ((int64_t)1 << 31))
+        return fail(MI_ERR_INVALID_ARGUMENT, "mi_lookahead_policy: candidates * num_envs must be < 2^31");
+    if (!(io->gamma >= 0.0 && io->gamma <= 1.0)) return fail(MI_ERR_INVALID_ARGUMENT, "mi_lookahead_policy: gamma must be in [0, 1]");
+    if (set_device(v)) return MI_ERR_HIP;
+    return mi_lookahead_policy_unit::launch(v, io->params, io->hidden, io->horizon, io->candidates, io->gamma, io->returns, io->steps, io->terminated, io->truncated,
+                                            static_cast<float *>(io->final_obs));
+}
+
 int mi_action_sample(mi_vecenv *v, int T, void *out, int loc) {
     if (!v) return fail(MI_ERR_INVALID_ARGUMENT, "null env");
     if (T < 0 || (T > 0 && !out)) return fail(MI_ERR_INVALID_ARGUMENT, "mi_action_sample: T >= 0 batches into a non-null array");

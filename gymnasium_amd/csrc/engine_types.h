@@ -1,4 +1,4 @@
-// engine_types.h -- what the engine's units (engine.hip, classic.hip, mujoco.hip, tabular.hip, lookahead.hip, mjx_model.hip and mjx_mass_model.hip) agree on: the
+// engine_types.h -- what the engine's units (engine.hip, classic.hip, mujoco.hip, tabular.hip, lookahead.hip, lookahead_policy.hip, mjx_model.hip and mjx_mass_model.hip) agree on: the
 // constants of the lane's flag word, the plain structs that ride in kernel arguments and in mi_vecenv, the handle itself, the launch functions one
 // unit defines and another calls, and the error helpers of the host side.  No kernel and no device function lives here.
 #ifndef MI355ENV_ENGINE_TYPES_H
@@ -222,6 +222,13 @@ namespace mi_lookahead_unit {
 int launch(mi_vecenv *v, const void *actions, int act_kind, int horizon, int candidates, double gamma, double *returns, int32_t *steps, uint8_t *terminated,
            uint8_t *truncated, float *final_obs);
 }  // namespace mi_lookahead_unit
+// mi_lookahead_policy's kernels likewise (defined in lookahead_policy.hip): lookahead_policy_kernel<E, LDS> of the env's kind, its per-lane type when the
+// env is on those, and the parameter path the launch function chooses.  params_per_candidate: P of a kind and a hidden width (0 for another kind).
+namespace mi_lookahead_policy_unit {
+int params_per_candidate(int kind, int hidden);
+int launch(mi_vecenv *v, const float *params, int hidden, int horizon, int candidates, double gamma, double *returns, int32_t *steps, uint8_t *terminated,
+           uint8_t *truncated, float *final_obs);
+}  // namespace mi_lookahead_policy_unit
 // The one-lane MuJoCo kernels of an env with per-sub-environment model fields (mi_set_model_field) -- mj_step_kernel and mj_rollout_kernel over
 // mjx::LaneModel env types -- behind plain launch functions: they are instantiated in a translation unit of their own (mjx_model.hip),
 // which compiles side by side with the others.  mujoco.hip launches through them (its lane_launchers; engine.hip calls preload and

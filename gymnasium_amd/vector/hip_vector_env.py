@@ -1022,6 +1022,92 @@ class HipVectorEnv(VectorEnv):
                       out["truncated"].data_ptr(), out["final_obs"].data_ptr() if final_obs else None, actions_dtype=in_dtype)
         return out  # (a converted copy `a` is the caching allocator's on torch's stream, which the launch is on: reused in stream order)
 
+    # -- lookahead over policies: candidate parameter vectors scored from the present state (mi_lookahead_policy) ------------------------------
+    def policy_param_layout(self, hidden: int = 0) -> dict:
+        """Where the parts of one candidate's parameter vector lie for ``lookahead_policy(..., hidden=hidden)``: ``{"W": (slice, shape), "b": ...,
+        "size": P}`` for ``hidden == 0``, ``{"W1": ..., "b1": ..., "W2": ..., "b2": ..., "size": P}`` otherwise (row-major; ``W`` / ``W2`` have one row per
+        action of a Discrete space or per component of a Box action, ``W`` / ``W1`` one column per observation component):
+        ``row[sl].reshape(shape)`` reads a part, ``row[sl] = part.ravel()`` writes it."""
+        if self.KIND not in self._CLASSIC_KINDS:
+            raise error.Error(f"{type(self).__name__}: lookahead_policy exists for CartPole-v1, Pendulum-v1, Acrobot-v1, MountainCar-v0 and "
+                              "MountainCarContinuous-v0 only")
+        if isinstance(hidden, bool) or not isinstance(hidden, (int, np.integer)):
+            raise TypeError(f"hidden must be an int, got {type(hidden).__name__}")
+        hidden = int(hidden)
+        if not 0 <= hidden <= 256:
+            raise ValueError(f"hidden must be in [0, 256], got {hidden}")
+        obs = int(self._engine.obs_dim)
+        A = int(self.single_action_space.n) if self._discrete else int(self._engine.act_dim)
+        parts = [("W", (A, obs)), ("b", (A,))] if hidden == 0 else [("W1", (hidden, obs)), ("b1", (hidden,)), ("W2", (A, hidden)), ("b2", (A,))]
+        out, at = {}, 0
+        for name, shape in parts:
+            n = int(np.prod(shape))
+            out[name] = (slice(at, at + n), shape)
+            at += n
+        out["size"] = at
+        return out
+
+    def lookahead_policy(self, params, horizon: int, gamma: float = 1.0, *, hidden: int = 0, final_obs: bool = False) -> dict:
+        """Score ``K`` candidate POLICIES for every sub-environment from its PRESENT state, closed loop, in one kernel launch, without touching the
+        env: what evolution strategies, ARS, CEM over parameters and population-based search ask of a model.  ``lookahead()`` with the action of every
+        step computed on the device from the observation the candidate's private copy would have returned.
+
+        ``params``: ``[K, P]`` float32 (tensor or ndarray; nothing is cast), candidate ``k`` using row ``k`` for all ``N`` sub-environments;
+        ``policy_param_layout(hidden)`` gives ``P`` and the parts.  ``hidden == 0``: ``y = b + W @ obs``.  ``1 <= hidden <= 256``:
+        ``y = b2 + W2 @ relu(b1 + W1 @ obs)``.  All in float32, every product and every sum rounded on its own, accumulated in ascending index order
+        (``include/mi355env.h`` states the order operation by operation; NumPy reproduces it bit for bit).  Discrete ids take the first largest
+        ``y[o]`` by a strict ``>`` scan from ``o = 0`` -- no comparison with a NaN holds, which is NOT ``np.argmax``'s rule --; Box ids take ``y[0]`` as the float32
+        action, clipped by the env as every action is.  There is no tanh or sigmoid.
+
+        ``horizon``, ``gamma``, ``final_obs`` and the returned dict of device tensors are ``lookahead()``'s.  Nothing synchronises."""
+        self._check_open()
+        self._check_not_pending("lookahead_policy")
+        refusal = self._lookahead_refusal()
+        if refusal:
+            raise error.Error(refusal)
+        if not self._has_reset:
+            raise AssertionError("Call reset before using lookahead_policy.")
+        t, eng, N = self._torch, self._engine, self.num_envs
+        if isinstance(gamma, bool) or not isinstance(gamma, (int, float, np.integer, np.floating)):
+            raise TypeError(f"gamma must be a number, got {type(gamma).__name__}")
+        gamma = float(gamma)
+        if not 0.0 <= gamma <= 1.0:
+            raise ValueError(f"gamma must be in [0, 1], got {gamma}")
+        P = self.policy_param_layout(hidden)["size"]
+        hidden = int(hidden)
+        if isinstance(horizon, bool) or not isinstance(horizon, (int, np.integer)):
+            raise TypeError(f"horizon must be an int, got {type(horizon).__name__}")
+        H = int(horizon)
+        if H < 1:
+            raise ValueError(f"horizon must be >= 1, got {H}")
+        if isinstance(params, np.ndarray):
+            if params.dtype != np.float32:
+                raise TypeError(f"params must be float32, got {params.dtype}")
+            params = t.from_numpy(params)
+        if not isinstance(params, t.Tensor):
+            raise TypeError(f"params must be a tensor, got {type(params).__name__}")
+        if params.dtype != t.float32:
+            raise TypeError(f"params must be float32, got {params.dtype}")
+        if params.dim() != 2 or params.shape[1] != P:
+            raise ValueError(f"params must have shape [K, P] with P = {P} for hidden = {hidden}, got {tuple(params.shape)}")
+        K = int(params.shape[0])
+        if K < 1:
+            raise ValueError(f"lookahead_policy needs K >= 1, got K = {K}")
+        if K * N >= 2 ** 31:
+            raise ValueError(f"lookahead_policy needs K * N < 2**31, got K = {K}, N = {N}")
+        if not hasattr(getattr(eng, "lib", None), "lookahead_policy"):
+            raise error.Error("lookahead_policy needs the device engine (mi_lookahead_policy): the engine behind this env has no such entry point")
+        self._bind_stream()
+        dev = self._tdev
+        p = params.to(device=dev).contiguous()
+        out = {"returns": t.empty((K, N), dtype=t.float64, device=dev), "steps": t.empty((K, N), dtype=t.int32, device=dev),
+               "terminated": t.empty((K, N), dtype=t.bool, device=dev), "truncated": t.empty((K, N), dtype=t.bool, device=dev)}
+        if final_obs:
+            out["final_obs"] = t.empty((K, N) + tuple(self._obs_shape[1:]), dtype=self._obs_tdtype, device=dev)
+        eng.lookahead_policy(p.data_ptr(), hidden, H, K, gamma, out["returns"].data_ptr(), out["steps"].data_ptr(), out["terminated"].data_ptr(),
+                             out["truncated"].data_ptr(), out["final_obs"].data_ptr() if final_obs else None)
+        return out  # (a converted copy `p`: lookahead()'s note)
+
     # -- HIP graphs ------------------------------------------------------------------------------------
     def capture_steps(self, actions=None, steps: int = 1, policy=None):
         """Capture ``steps`` consecutive ``step()`` calls -- and, with ``policy``, the policy between them -- into ONE HIP graph

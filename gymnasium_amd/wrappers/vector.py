@@ -163,6 +163,12 @@ class VectorWrapper:
         raise error.Error(f"{type(self).__name__}: lookahead() is not offered through wrappers -- forwarding it would hand back the unwrapped env's rewards "
                           "and observations as if they were this wrapper's; call env.unwrapped.lookahead(...) if those are what you want")
 
+    def lookahead_policy(self, params, horizon, gamma=1.0, **kwargs):
+        """Not through a wrapper, for lookahead()'s reason: the candidates see, and are scored by, the plain env's observations and rewards."""
+        raise error.Error(f"{type(self).__name__}: lookahead_policy() is not offered through wrappers -- the candidate policies would be fed the unwrapped "
+                          "env's observations and scored by its rewards as if they were this wrapper's; call env.unwrapped.lookahead_policy(...) if those "
+                          "are what you want")
+
     def _workspace(self, steps, rows, dim):
         """Scratch of the whole-trajectory passes: a tensor from the caching allocator, so that the library neither allocates nor synchronises."""
         lib = _native.load_library()

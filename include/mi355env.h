@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-/* Entry points that were only ADDED since (mi_action_sample_masked and its three companions, mi_set_step_wrappers, mi_set_max_and_skip, mi_lookahead) leave the number where it is: nothing an ABI 10
+/* Entry points that were only ADDED since (mi_action_sample_masked and its three companions, mi_set_step_wrappers, mi_set_max_and_skip, mi_lookahead, mi_lookahead_policy) leave the number where it is: nothing an ABI 10
  * caller uses changed, and a caller that needs them finds out by looking the symbol up. */
 #define MI355ENV_ABI_VERSION 10
 
@@ -583,6 +583,44 @@ typedef struct mi_lookahead_io {
     double gamma;
 } mi_lookahead_io;
 int mi_lookahead(mi_vecenv *env, const mi_lookahead_io *io);
+
+/*
+ * Lookahead over POLICIES: mi_lookahead with the action of every step computed in the lane from the observation, by a small network whose parameters
+ * are the candidate -- what evolution strategies, ARS, CEM over parameters and population-based search ask of a model.  Added to ABI 10, which it
+ * leaves as it is.  Everything is mi_lookahead's -- the private copy of the lane (state, elapsed steps, flags, attributes, generator), mi_step's
+ * sequence per step, the stop after the first step that terminates or truncates, the outputs and their nullability, the return recurrence, the
+ * sub-environment that waits for its reset, the untouched env, the kinds, one launch on the env's stream and no synchronisation -- except where the
+ * actions come from:
+ *   params      in   [candidates][P] f32, row-major.  Candidate k uses row k for all N sub-environments.
+ *   The action of step t is computed from the float32 observation of the candidate's current state (the values mi_step would have returned; first: of
+ *   the present state).  OBS = obs_dim, A = the number of actions (Discrete kinds) or act_dim (Box kinds: 1), h = hidden:
+ *     h == 0        row = W[A][OBS], b[A]; P = A (OBS + 1).  y[o] = b[o]; then for j = 0 .. OBS - 1 in that order: y[o] = y[o] + W[o][j] * obs[j].
+ *     1 <= h <= 256 row = W1[h][OBS], b1[h], W2[A][h], b2[A]; P = h (OBS + 1) + A (h + 1).  y[o] = b2[o]; then for u = 0 .. h - 1 in that order:
+ *                   z = b1[u]; for j ascending: z = z + W1[u][j] * obs[j];  a = z > 0 ? z : 0 (a NaN gives 0);  for every o: y[o] = y[o] + W2[o][u] * a.
+ *   Every product and every sum is a float32 operation rounded on its own: no FMA, no re-association, subnormals kept.  That order IS the contract;
+ *   NumPy reproduces it bit for bit.
+ *     Discrete kinds: best = 0; for o = 1 .. A - 1: if y[o] > y[best], best = o.  Strict: the first maximum wins, and no comparison with a NaN holds -- a
+ *                     NaN y[o], o >= 1, is never chosen and a NaN y[0] is never displaced (NOT np.argmax's rule, which returns the first NaN).  The
+ *                     action is `best`: always inside the space.
+ *     Box kinds:      y[0] is the float32 action row, taken as mi_lookahead takes an MI_F32 row: the env's own clip applies, nothing squashes it.
+ *   No tanh, no sigmoid: they would need an exact float32 restatement of libm's.
+ * MI_ERR_UNSUPPORTED and MI_ERR_STATE: as mi_lookahead.
+ * MI_ERR_INVALID_ARGUMENT: hidden outside [0, 256], horizon or candidates < 1, candidates * N >= 2^31, gamma outside [0, 1], params NULL, a wrong struct_size.
+ */
+typedef struct mi_lookahead_policy_io {
+    int32_t struct_size;      /* = sizeof(mi_lookahead_policy_io) */
+    const float *params;
+    double *returns;
+    int32_t *steps;
+    uint8_t *terminated;
+    uint8_t *truncated;
+    void *final_obs;
+    int32_t horizon;
+    int32_t candidates;
+    int32_t hidden;
+    double gamma;
+} mi_lookahead_policy_io;
+int mi_lookahead_policy(mi_vecenv *env, const mi_lookahead_policy_io *io);
 
 /*
  * Stateful vector wrappers as device epilogues of the step path.  All array arguments are DEVICE
