@@ -46,8 +46,8 @@ NO_MLICM = ["-mllvm", "-disable-machine-licm"]
 # (`iterative-ilp` crashes clang-22 on engine.hip, `iterative-maxocc` stops with "Illegal instruction detected: Operand has incorrect register class".)
 MAXILP = ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]
 # Every unit not named here builds with FLAGS alone (the default flag set its head refers to).
-# lookahead.hip: the same per-lane step in a loop of its own (mi_lookahead), one wavefront per SIMD at 65 536 candidates: classic.hip's flags.
-# lookahead_policy.hip: that loop with the policy evaluated in the lane (mi_lookahead_policy): lookahead.hip's reason.
+# lookahead.hip, lookahead_policy.hip: the same per-lane step in the candidate loop of candidate_lane.h (mi_lookahead; mi_lookahead_policy, with the
+# policy evaluated in the lane), one wavefront per SIMD at 65 536 candidates: classic.hip's flags.
 TU_FLAGS = {"physics16.hip": ITERATIVE + SINK, "physics32.hip": ITERATIVE + SINK, "classic.hip": MAXILP, "lookahead.hip": MAXILP, "lookahead_policy.hip": MAXILP}
 FLAGS = ["-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-fvisibility=hidden", "-Wall", "-Wno-unused-function", "-Wno-missing-braces"]
 

@@ -1171,21 +1171,32 @@ int mi_rollout_infos(mi_vecenv *v, int T, const mi_rollout_io *io, const mi_roll
     return rollout_impl(v, T, io, &ex);
 }
 
+// What mi_lookahead and mi_lookahead_policy (`who`) refuse alike, in the order both state it: the env's kind, modes and state ...
+static int lookahead_env_checks(const mi_vecenv *v, const char *who) {
+    if (v->cfg.kind < 0 || v->cfg.kind >= kClassicKinds) return fail(MI_ERR_UNSUPPORTED, "%s: the five classic-control kinds only", who);
+    if (v->shared_rng) return fail(MI_ERR_UNSUPPORTED, "%s: not with MI_CFG_SHARED_RNG (CartPoleVectorEnv has no sub-environment generators to copy)", who);
+    if (v->cfg.reserved[0] & MI_CFG_FAST_MATH) return fail(MI_ERR_UNSUPPORTED, "%s: not with MI_CFG_FAST_MATH", who);
+    if (v->wrap_on) return fail(MI_ERR_UNSUPPORTED, "%s: not with mi_set_step_wrappers / mi_set_max_and_skip on", who);
+    if (v->has_epi) return fail(MI_ERR_UNSUPPORTED, "%s: not with a step epilogue attached (mi_set_step_epilogue)", who);
+    if (v->has_pending) return fail(MI_ERR_STATE, "an asynchronous step is pending (mi_step_wait)");
+    if (!v->was_reset) return fail(MI_ERR_STATE, "%s before reset", who + 3);  // (without the "mi_")
+    return MI_OK;
+}
+// ... and, after the entry point's own check of its input, horizon, candidates and gamma.
+static int lookahead_shape_checks(const mi_vecenv *v, const char *who, int horizon, int candidates, double gamma) {
+    if (horizon < 1 || candidates < 1) return fail(MI_ERR_INVALID_ARGUMENT, "%s: horizon and candidates must be >= 1", who);
+    if ((int64_t)candidates * (int64_t)v->cfg.num_envs >= ((int64_t)1 << 31)) return fail(MI_ERR_INVALID_ARGUMENT, "%s: candidates * num_envs must be < 2^31", who);
+    if (!(gamma >= 0.0 && gamma <= 1.0)) return fail(MI_ERR_INVALID_ARGUMENT, "%s: gamma must be in [0, 1]", who);
+    return MI_OK;
+}
+
 // The return of K candidate action sequences from every sub-environment's present state (include/mi355env.h mi_lookahead; device side: lookahead.hip).
 int mi_lookahead(mi_vecenv *v, const mi_lookahead_io *io) {
     if (!v || !io) return fail(MI_ERR_INVALID_ARGUMENT, "null argument");
     if (io->struct_size != (int32_t)sizeof(mi_lookahead_io)) return fail(MI_ERR_INVALID_ARGUMENT, "mi_lookahead: struct_size != sizeof(mi_lookahead_io)");
-    if (v->cfg.kind < 0 || v->cfg.kind >= kClassicKinds) return fail(MI_ERR_UNSUPPORTED, "mi_lookahead: the five classic-control kinds only");
-    if (v->shared_rng) return fail(MI_ERR_UNSUPPORTED, "mi_lookahead: not with MI_CFG_SHARED_RNG (CartPoleVectorEnv has no sub-environment generators to copy)");
-    if (v->cfg.reserved[0] & MI_CFG_FAST_MATH) return fail(MI_ERR_UNSUPPORTED, "mi_lookahead: not with MI_CFG_FAST_MATH");
-    if (v->wrap_on) return fail(MI_ERR_UNSUPPORTED, "mi_lookahead: not with mi_set_step_wrappers / mi_set_max_and_skip on");
-    if (v->has_epi) return fail(MI_ERR_UNSUPPORTED, "mi_lookahead: not with a step epilogue attached (mi_set_step_epilogue)");
-    if (v->has_pending) return fail(MI_ERR_STATE, "an asynchronous step is pending (mi_step_wait)");
-    if (!v->was_reset) return fail(MI_ERR_STATE, "lookahead before reset");
+    if (int rc = lookahead_env_checks(v, "mi_lookahead")) return rc;
     if (!io->actions) return fail(MI_ERR_INVALID_ARGUMENT, "mi_lookahead: actions must not be NULL");
-    if (io->horizon < 1 || io->candidates < 1) return fail(MI_ERR_INVALID_ARGUMENT, "mi_lookahead: horizon and candidates must be >= 1");
-    if ((int64_t)io->candidates * (int64_t)v->cfg.num_envs >= ((int64_t)1 << 31)) return fail(MI_ERR_INVALID_ARGUMENT, "mi_lookahead: candidates * num_envs must be < 2^31");
-    if (!(io->gamma >= 0.0 && io->gamma <= 1.0)) return fail(MI_ERR_INVALID_ARGUMENT, "mi_lookahead: gamma must be in [0, 1]");
+    if (int rc = lookahead_shape_checks(v, "mi_lookahead", io->horizon, io->candidates, io->gamma)) return rc;
     const bool box = v->lay.act_dtype == MI_F32;
     if (box && io->actions_dtype != MI_F32 && io->actions_dtype != MI_F64 && io->actions_dtype != MI_F64_WEAK)
         return fail(MI_ERR_INVALID_ARGUMENT, "actions_dtype must be MI_F32, MI_F64 or MI_F64_WEAK");
@@ -1195,24 +1206,15 @@ int mi_lookahead(mi_vecenv *v, const mi_lookahead_io *io) {
 }
 
 // ... and of K candidate POLICIES, evaluated in the lane from the observation of every step (include/mi355env.h mi_lookahead_policy; device side:
-// lookahead_policy.hip).  mi_lookahead's refusals and state errors, in its order.
+// lookahead_policy.hip).
 int mi_lookahead_policy(mi_vecenv *v, const mi_lookahead_policy_io *io) {
     if (!v || !io) return fail(MI_ERR_INVALID_ARGUMENT, "null argument");
     if (io->struct_size != (int32_t)sizeof(mi_lookahead_policy_io))
         return fail(MI_ERR_INVALID_ARGUMENT, "mi_lookahead_policy: struct_size != sizeof(mi_lookahead_policy_io)");
-    if (v->cfg.kind < 0 || v->cfg.kind >= kClassicKinds) return fail(MI_ERR_UNSUPPORTED, "mi_lookahead_policy: the five classic-control kinds only");
-    if (v->shared_rng) return fail(MI_ERR_UNSUPPORTED, "mi_lookahead_policy: not with MI_CFG_SHARED_RNG (CartPoleVectorEnv has no sub-environment generators to copy)");
-    if (v->cfg.reserved[0] & MI_CFG_FAST_MATH) return fail(MI_ERR_UNSUPPORTED, "mi_lookahead_policy: not with MI_CFG_FAST_MATH");
-    if (v->wrap_on) return fail(MI_ERR_UNSUPPORTED, "mi_lookahead_policy: not with mi_set_step_wrappers / mi_set_max_and_skip on");
-    if (v->has_epi) return fail(MI_ERR_UNSUPPORTED, "mi_lookahead_policy: not with a step epilogue attached (mi_set_step_epilogue)");
-    if (v->has_pending) return fail(MI_ERR_STATE, "an asynchronous step is pending (mi_step_wait)");
-    if (!v->was_reset) return fail(MI_ERR_STATE, "lookahead_policy before reset");
+    if (int rc = lookahead_env_checks(v, "mi_lookahead_policy")) return rc;
     if (!io->params) return fail(MI_ERR_INVALID_ARGUMENT, "mi_lookahead_policy: params must not be NULL");
     if (io->hidden < 0 || io->hidden > 256) return fail(MI_ERR_INVALID_ARGUMENT, "mi_lookahead_policy: hidden must be in [0, 256]");
-    if (io->horizon < 1 || io->candidates < 1) return fail(MI_ERR_INVALID_ARGUMENT, "mi_lookahead_policy: horizon and candidates must be >= 1");
-    if ((int64_t)io->candidates * (int64_t)v->cfg.num_envs >= ((int64_t)1 << 31))
-        return fail(MI_ERR_INVALID_ARGUMENT, "mi_lookahead_policy: candidates * num_envs must be < 2^31");
-    if (!(io->gamma >= 0.0 && io->gamma <= 1.0)) return fail(MI_ERR_INVALID_ARGUMENT, "mi_lookahead_policy: gamma must be in [0, 1]");
+    if (int rc = lookahead_shape_checks(v, "mi_lookahead_policy", io->horizon, io->candidates, io->gamma)) return rc;
     if (set_device(v)) return MI_ERR_HIP;
     return mi_lookahead_policy_unit::launch(v, io->params, io->hidden, io->horizon, io->candidates, io->gamma, io->returns, io->steps, io->terminated, io->truncated,
                                             static_cast<float *>(io->final_obs));

@@ -216,8 +216,9 @@ int step(mi_vecenv *v, const mi_internal::StepPtrs &p, double *info, double *fin
 int rollout(mi_vecenv *v, const mi_internal::RolloutPtrs &p, const mi_internal::ActionStream &as, int T, bool sample, const mi_internal::RolloutExtra *ex);
 }  // namespace mi_tabular
 // mi_lookahead's kernels behind a plain launch function (defined in lookahead.hip, called from engine.hip once the arguments are validated):
-// lookahead_kernel<E> of the env's kind, its per-lane type when the env is on those, and the element type of the action rows.  Device pointers;
-// every output nullable.  (mi_lookahead_unit: `mi_lookahead` itself is the C entry point's name.)
+// lookahead_kernel<E> of the env's kind, its per-lane type when the env is on those, and the element type of the action rows (candidate_lane.h's
+// dispatch, as for the policy unit below; the candidate loop both units share is that header's).  Device pointers; every output nullable.
+// (mi_lookahead_unit: `mi_lookahead` itself is the C entry point's name.)
 namespace mi_lookahead_unit {
 int launch(mi_vecenv *v, const void *actions, int act_kind, int horizon, int candidates, double gamma, double *returns, int32_t *steps, uint8_t *terminated,
            uint8_t *truncated, float *final_obs);

@@ -1,18 +1,18 @@
 // lookahead_policy.hip -- mi_lookahead_policy's kernels as their own translation unit: namespace mi_lookahead_policy_unit, the launch function engine.hip
 // calls (engine_types.h declares it) and every instantiation of lookahead_policy_kernel.
 //
-// What it computes (include/mi355env.h mi_lookahead_policy): lookahead.hip's loop -- K candidates per sub-environment, each on a PRIVATE copy of lane i,
-// lane_step's sequence per step, stopped after the first step that ends the episode, the env only read -- with the action of every step computed IN
-// the lane from the float32 observation of the lane's current state: a linear map (hidden == 0) or one hidden layer of `hidden` ReLU units, candidate
-// k using row k of `params`.  The arithmetic is fixed operation by operation (the header): float32, every product and every sum rounded on its own
-// (this unit is built with -ffp-contract=off like its sibling and must stay so), hidden units in ascending order, each consumed by all outputs as
-// soon as it exists -- so the kernel holds A accumulators and never an array of activations -- and the strict-greater scan for the Discrete kinds.
+// What it computes (include/mi355env.h mi_lookahead_policy): the candidate loop candidate_lane.h describes -- K candidates per sub-environment, each on
+// a private copy of lane i, stopped after the first step that ends the episode, the env only read -- with the action of every step computed IN the lane
+// from the float32 observation of the lane's current state: a linear map (hidden == 0) or one hidden layer of `hidden` ReLU units, candidate k using
+// row k of `params`.  The arithmetic is fixed operation by operation (the header): float32, every product and every sum rounded on its own (this unit
+// is built with -ffp-contract=off like its sibling and must stay so), hidden units in ascending order, each consumed by all outputs as soon as it
+// exists -- so the kernel holds A accumulators and never an array of activations -- and the strict-greater scan for the Discrete kinds.
 //
-// How: lookahead.hip's lane mapping (lane j = k * N + i, outputs contiguous in j), load order (everything the lane reads before its first step is
-// requested before tables_init's barrier) and loop idiom (a finished candidate goes on stepping from the state it finished in, everything held by
-// selects, nothing stored inside the loop).  The observation is needed every step here, so the loop is lane_step_fused's shape: advance, select, take
-// the observation of the state the lane now holds -- which hands its sin / cos to the next step (envs_classic.h Trig) and, for Acrobot, to the
-// terminal test (terminal_after_obs): no angle is evaluated twice.  The observation after the loop IS final_obs.
+// The kernel's device text is its own, not candidate_lane.h's parts: built from them, at the same static counts, 9 of 24 measured configurations ran
+// 0.1 - 2.1 % slower (docs/results_log.md), and no part alone left the step loops' instruction sequence as it was.  It shares the output struct and
+// the host side: the dispatch to the env type, from which P comes too, and the grid.  The observation is needed every step here, so the loop is
+// lane_step_fused's shape: advance, select, take the observation of the state the lane now holds -- which hands its sin / cos to the next step
+// (envs_classic.h Trig) and, for Acrobot, to the terminal test (terminal_after_obs).  The observation after the loop IS final_obs.
 //
 // Parameters, two paths chosen on the host (policy_path, below):
 //   LDS     a workgroup's 256 lanes span candidates k_lo .. k_hi, whose rows are one contiguous range of `params`; it is staged into LDS with
@@ -27,16 +27,13 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "lane_step.h"
+#include "candidate_lane.h"
 
 namespace {
 
 struct PolicyPtrs {
     const float *params;  // [K][P]
-    double *returns;      // [K * N]
-    int32_t *steps;       // [K * N]
-    uint8_t *terminated, *truncated;
-    float *final_obs;     // [K * N][OBS]
+    CandidateOut out;
     int H, KN, hidden, P;
     double gamma;
 };
@@ -182,7 +179,7 @@ __global__ __launch_bounds__(kBlock, PolicyWaves<E>::value) void lookahead_polic
     const int i = live ? j - k * d.N : 0;
     const int k_lo = j0 / d.N;
     // everything the lane reads before its first step -- state, elapsed | flags, attributes, generator (a type whose step draws) -- and the workgroup's
-    // parameter rows are requested before the math tables are staged into LDS: one trip to memory, not two (lookahead.hip's order)
+    // parameter rows are requested before the math tables are staged into LDS: one trip to memory, not two (CandidateStart's order)
     double s[E::S];
     uint32_t meta = 0;
     uint64_t g[4] = {0, 0, 0, 0};
@@ -267,11 +264,11 @@ __global__ __launch_bounds__(kBlock, PolicyWaves<E>::value) void lookahead_polic
         tr_last = go ? (tr ? 1u : 0u) : tr_last;
         active = (go && (te || tr)) ? 0u : active;
     }
-    if (io.returns) io.returns[j] = G;
-    if (io.steps) io.steps[j] = steps;
-    if (io.terminated) io.terminated[j] = (uint8_t)te_last;
-    if (io.truncated) io.truncated[j] = (uint8_t)tr_last;
-    if (io.final_obs) store_row<E::OBS>(io.final_obs + (size_t)j * E::OBS, o);
+    if (io.out.returns) io.out.returns[j] = G;
+    if (io.out.steps) io.out.steps[j] = steps;
+    if (io.out.terminated) io.out.terminated[j] = (uint8_t)te_last;
+    if (io.out.truncated) io.out.truncated[j] = (uint8_t)tr_last;
+    if (io.out.final_obs) store_row<E::OBS>(io.out.final_obs + (size_t)j * E::OBS, o);
 }
 
 // Which path: MI355ENV_LOOKAHEAD_POLICY_PATH = "global" sends every call down the global path, "lds" refuses a call whose rows do not fit instead of
@@ -296,11 +293,11 @@ int launch_for(mi_vecenv *v, const PolicyPtrs &p, int candidates) {
     size_t bytes;
     if (int rc = policy_path(v, p, candidates, lds, bytes)) return rc;
     const AttrDev at = {v->d_attr, v->attr_mask};
-    const unsigned grid = (unsigned)(((int64_t)p.KN + kBlock - 1) / kBlock);
+    const dim3 grid(candidate_grid(p.KN));
     if (lds)
-        hipLaunchKernelGGL((lookahead_policy_kernel<E, true>), dim3(grid), dim3(kBlock), bytes, v->stream, v->d, p, at);
+        hipLaunchKernelGGL((lookahead_policy_kernel<E, true>), grid, dim3(kBlock), bytes, v->stream, v->d, p, at);
     else
-        hipLaunchKernelGGL((lookahead_policy_kernel<E, false>), dim3(grid), dim3(kBlock), 0, v->stream, v->d, p, at);
+        hipLaunchKernelGGL((lookahead_policy_kernel<E, false>), grid, dim3(kBlock), 0, v->stream, v->d, p, at);
     HIP_TRY(hipGetLastError());
     return MI_OK;
 }
@@ -309,33 +306,18 @@ int launch_for(mi_vecenv *v, const PolicyPtrs &p, int candidates) {
 
 namespace mi_lookahead_policy_unit {
 int params_per_candidate(int kind, int hidden) {
-    int obs, a;
-    switch (kind) {
-    case MI_ENV_CARTPOLE: obs = PolicyDims<CartPole>::OBS, a = PolicyDims<CartPole>::A; break;
-    case MI_ENV_PENDULUM: obs = PolicyDims<Pendulum>::OBS, a = PolicyDims<Pendulum>::A; break;
-    case MI_ENV_ACROBOT: obs = PolicyDims<Acrobot>::OBS, a = PolicyDims<Acrobot>::A; break;
-    case MI_ENV_MOUNTAIN_CAR: obs = PolicyDims<MountainCar>::OBS, a = PolicyDims<MountainCar>::A; break;
-    case MI_ENV_MOUNTAIN_CAR_CONTINUOUS: obs = PolicyDims<MountainCarContinuous>::OBS, a = PolicyDims<MountainCarContinuous>::A; break;
-    default: return 0;
-    }
-    return hidden == 0 ? a * (obs + 1) : hidden * (obs + 1) + a * (hidden + 1);
+    int P = 0;
+    for_candidate_env<false>(kind, false, MI_F32, [&](auto e) {
+        typedef PolicyDims<typename decltype(e)::type> D;
+        P = hidden == 0 ? D::A * (D::OBS + 1) : hidden * (D::OBS + 1) + D::A * (hidden + 1);
+    });
+    return P;
 }
 
 int launch(mi_vecenv *v, const float *params, int hidden, int horizon, int candidates, double gamma, double *returns, int32_t *steps, uint8_t *terminated,
            uint8_t *truncated, float *final_obs) {
-    typedef ExactMath M;
-    const PolicyPtrs p = {params, returns, steps, terminated, truncated, final_obs, horizon, candidates * v->cfg.num_envs, hidden,
+    const PolicyPtrs p = {params, {returns, steps, terminated, truncated, final_obs}, horizon, candidates * v->cfg.num_envs, hidden,
                           params_per_candidate(v->cfg.kind, hidden), gamma};
-    // an env on the per-lane types (mi_set_env_attr; once mi_set_step_wrappers was on) stays on them, as in mi_classic::step
-    const bool attr = v->attr_mask || v->per_lane;
-    switch (v->cfg.kind) {
-    case MI_ENV_CARTPOLE: return attr ? launch_for<CartPoleAttrT<M>>(v, p, candidates) : launch_for<CartPoleT<M>>(v, p, candidates);
-    case MI_ENV_PENDULUM: return attr ? launch_for<PendulumAttrT<M>>(v, p, candidates) : launch_for<PendulumT<M>>(v, p, candidates);
-    case MI_ENV_ACROBOT:  // (the math policy of Acrobot's other kernels, envs_classic.h)
-        return attr ? launch_for<AcrobotAttrT<ExactMathBuiltinFma>>(v, p, candidates) : launch_for<AcrobotT<ExactMathBuiltinFma>>(v, p, candidates);
-    case MI_ENV_MOUNTAIN_CAR: return attr ? launch_for<MountainCarAttrT<M>>(v, p, candidates) : launch_for<MountainCarT<M>>(v, p, candidates);
-    case MI_ENV_MOUNTAIN_CAR_CONTINUOUS: return attr ? launch_for<MountainCarContinuousAttrT<M>>(v, p, candidates) : launch_for<MountainCarContinuousT<M>>(v, p, candidates);
-    }
-    return fail(MI_ERR_UNSUPPORTED, "mi_lookahead_policy: the five classic-control kinds only");
+    return dispatch_candidate_env<false>(v, MI_F32, "mi_lookahead_policy", [&](auto e) { return launch_for<typename decltype(e)::type>(v, p, candidates); });
 }
 }  // namespace mi_lookahead_policy_unit

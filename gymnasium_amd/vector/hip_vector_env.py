@@ -958,6 +958,38 @@ class HipVectorEnv(VectorEnv):
             return "vector wrappers are fused into this env's step kernel: lookahead returns the plain env's rewards and observations"
         return None
 
+    def _lookahead_begin(self, name: str, gamma) -> float:
+        """What ``lookahead()`` and ``lookahead_policy()`` (``name``) check before they look at their own arguments; returns gamma as a float."""
+        self._check_open()
+        self._check_not_pending(name)
+        refusal = self._lookahead_refusal()
+        if refusal:
+            raise error.Error(refusal)
+        if not self._has_reset:
+            raise AssertionError(f"Call reset before using {name}.")
+        if isinstance(gamma, bool) or not isinstance(gamma, (int, float, np.integer, np.floating)):
+            raise TypeError(f"gamma must be a number, got {type(gamma).__name__}")
+        gamma = float(gamma)
+        if not 0.0 <= gamma <= 1.0:
+            raise ValueError(f"gamma must be in [0, 1], got {gamma}")
+        return gamma
+
+    def _lookahead_outputs(self, name: str, K: int, final_obs: bool) -> dict:
+        """What both (``name``) do once their own arguments are valid and K >= 1: K against the lane index, the engine's entry point ``mi_<name>``,
+        torch's stream bound, the output tensors allocated."""
+        t, N = self._torch, self.num_envs
+        if K * N >= 2 ** 31:
+            raise ValueError(f"{name} needs K * N < 2**31, got K = {K}, N = {N}")
+        if not hasattr(getattr(self._engine, "lib", None), name):
+            raise error.Error(f"{name} needs the device engine (mi_{name}): the engine behind this env has no such entry point")
+        self._bind_stream()
+        dev = self._tdev
+        out = {"returns": t.empty((K, N), dtype=t.float64, device=dev), "steps": t.empty((K, N), dtype=t.int32, device=dev),
+               "terminated": t.empty((K, N), dtype=t.bool, device=dev), "truncated": t.empty((K, N), dtype=t.bool, device=dev)}
+        if final_obs:
+            out["final_obs"] = t.empty((K, N) + tuple(self._obs_shape[1:]), dtype=self._obs_tdtype, device=dev)
+        return out
+
     def lookahead(self, actions, gamma: float = 1.0, *, final_obs: bool = False) -> dict:
         """Score ``K`` candidate action sequences of length ``H`` for every sub-environment from its PRESENT state, in one kernel launch, without
         touching the env: what a sampling planner (random shooting, CEM, MPPI) asks of a model.
@@ -974,19 +1006,8 @@ class HipVectorEnv(VectorEnv):
 
         Nothing synchronises.  An action outside a Discrete space is reported like ``step()``'s with device tensors: by a later synchronising call.
         """
-        self._check_open()
-        self._check_not_pending("lookahead")
-        refusal = self._lookahead_refusal()
-        if refusal:
-            raise error.Error(refusal)
-        if not self._has_reset:
-            raise AssertionError("Call reset before using lookahead.")
+        gamma = self._lookahead_begin("lookahead", gamma)
         t, eng, N = self._torch, self._engine, self.num_envs
-        if isinstance(gamma, bool) or not isinstance(gamma, (int, float, np.integer, np.floating)):
-            raise TypeError(f"gamma must be a number, got {type(gamma).__name__}")
-        gamma = float(gamma)
-        if not 0.0 <= gamma <= 1.0:
-            raise ValueError(f"gamma must be in [0, 1], got {gamma}")
         if isinstance(actions, np.ndarray):
             actions = t.from_numpy(actions)
         if not isinstance(actions, t.Tensor):
@@ -1006,18 +1027,9 @@ class HipVectorEnv(VectorEnv):
         H, K = int(actions.shape[0]), int(actions.shape[1])
         if H < 1 or K < 1:
             raise ValueError(f"lookahead needs H >= 1 and K >= 1, got H = {H}, K = {K}")
-        if K * N >= 2 ** 31:
-            raise ValueError(f"lookahead needs K * N < 2**31, got K = {K}, N = {N}")
-        if not hasattr(getattr(eng, "lib", None), "lookahead"):
-            raise error.Error("lookahead needs the device engine (mi_lookahead): the engine behind this env has no such entry point")
-        self._bind_stream()
-        dev = self._tdev
+        out = self._lookahead_outputs("lookahead", K, final_obs)
         in_dtype = _native.MI_F64 if actions.dtype == t.float64 else _native.MI_F32
-        a = actions.to(device=dev).contiguous()
-        out = {"returns": t.empty((K, N), dtype=t.float64, device=dev), "steps": t.empty((K, N), dtype=t.int32, device=dev),
-               "terminated": t.empty((K, N), dtype=t.bool, device=dev), "truncated": t.empty((K, N), dtype=t.bool, device=dev)}
-        if final_obs:
-            out["final_obs"] = t.empty((K, N) + tuple(self._obs_shape[1:]), dtype=self._obs_tdtype, device=dev)
+        a = actions.to(device=self._tdev).contiguous()
         eng.lookahead(a.data_ptr(), H, K, gamma, out["returns"].data_ptr(), out["steps"].data_ptr(), out["terminated"].data_ptr(),
                       out["truncated"].data_ptr(), out["final_obs"].data_ptr() if final_obs else None, actions_dtype=in_dtype)
         return out  # (a converted copy `a` is the caching allocator's on torch's stream, which the launch is on: reused in stream order)
@@ -1060,19 +1072,8 @@ class HipVectorEnv(VectorEnv):
         action, clipped by the env as every action is.  There is no tanh or sigmoid.
 
         ``horizon``, ``gamma``, ``final_obs`` and the returned dict of device tensors are ``lookahead()``'s.  Nothing synchronises."""
-        self._check_open()
-        self._check_not_pending("lookahead_policy")
-        refusal = self._lookahead_refusal()
-        if refusal:
-            raise error.Error(refusal)
-        if not self._has_reset:
-            raise AssertionError("Call reset before using lookahead_policy.")
-        t, eng, N = self._torch, self._engine, self.num_envs
-        if isinstance(gamma, bool) or not isinstance(gamma, (int, float, np.integer, np.floating)):
-            raise TypeError(f"gamma must be a number, got {type(gamma).__name__}")
-        gamma = float(gamma)
-        if not 0.0 <= gamma <= 1.0:
-            raise ValueError(f"gamma must be in [0, 1], got {gamma}")
+        gamma = self._lookahead_begin("lookahead_policy", gamma)
+        t, eng = self._torch, self._engine
         P = self.policy_param_layout(hidden)["size"]
         hidden = int(hidden)
         if isinstance(horizon, bool) or not isinstance(horizon, (int, np.integer)):
@@ -1093,17 +1094,8 @@ class HipVectorEnv(VectorEnv):
         K = int(params.shape[0])
         if K < 1:
             raise ValueError(f"lookahead_policy needs K >= 1, got K = {K}")
-        if K * N >= 2 ** 31:
-            raise ValueError(f"lookahead_policy needs K * N < 2**31, got K = {K}, N = {N}")
-        if not hasattr(getattr(eng, "lib", None), "lookahead_policy"):
-            raise error.Error("lookahead_policy needs the device engine (mi_lookahead_policy): the engine behind this env has no such entry point")
-        self._bind_stream()
-        dev = self._tdev
-        p = params.to(device=dev).contiguous()
-        out = {"returns": t.empty((K, N), dtype=t.float64, device=dev), "steps": t.empty((K, N), dtype=t.int32, device=dev),
-               "terminated": t.empty((K, N), dtype=t.bool, device=dev), "truncated": t.empty((K, N), dtype=t.bool, device=dev)}
-        if final_obs:
-            out["final_obs"] = t.empty((K, N) + tuple(self._obs_shape[1:]), dtype=self._obs_tdtype, device=dev)
+        out = self._lookahead_outputs("lookahead_policy", K, final_obs)
+        p = params.to(device=self._tdev).contiguous()
         eng.lookahead_policy(p.data_ptr(), hidden, H, K, gamma, out["returns"].data_ptr(), out["steps"].data_ptr(), out["terminated"].data_ptr(),
                              out["truncated"].data_ptr(), out["final_obs"].data_ptr() if final_obs else None)
         return out  # (a converted copy `p`: lookahead()'s note)

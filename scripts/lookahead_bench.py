@@ -3,8 +3,8 @@
 
     python scripts/lookahead_bench.py [--rounds 5] [--parent PATH/TO/PARENT/libmi355env.so] [--out profiles/lookahead_ab.txt]
 
-Every measurement runs in its own process (scripts/step_wrappers_bench.py's scheme), `--rounds` times, this build's and -- with --parent -- the parent
-build's interleaved (MI355ENV_LIBRARY selects the build).  A process measures, for CartPole-v1 and Pendulum-v1 with output="torch" and fixed device
+Every measurement runs in its own process, `--rounds` times, this build's and -- with --parent -- the parent build's interleaved
+(scripts/bench_rounds.py).  A process measures, for CartPole-v1 and Pendulum-v1 with output="torch" and fixed device
 action tensors, the time per call -- device events around CALLS calls, median of WINDOWS windows -- of
 
   rollout          rollout(128, actions, return_actions=False) on 65 536 sub-environments: the path a planner had before (every build)
@@ -20,8 +20,9 @@ One process, this build: lookahead(actions[128, K, 65536]) for K = 1, 2, 4 and a
 import argparse
 import json
 import os
-import subprocess
 import sys
+
+from bench_rounds import finish, median_window, run_rounds, spread
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 H, CALLS, WINDOWS, WARMUP = 128, 200, 7, 20
@@ -35,19 +36,7 @@ def child():
     import gymnasium_amd
 
     def windows(call):
-        for _ in range(WARMUP):
-            call()
-        torch.cuda.synchronize()
-        took = []
-        for _ in range(WINDOWS):
-            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            t0.record()
-            for _ in range(CALLS):
-                call()
-            t1.record()
-            torch.cuda.synchronize()
-            took.append(t0.elapsed_time(t1) / CALLS * 1e3)
-        return sorted(took)[len(took) // 2]  # us per call, median window
+        return median_window(torch, call, WARMUP, CALLS, WINDOWS)
 
     def actions(env_id, shape):
         g = torch.Generator().manual_seed(3)
@@ -92,19 +81,7 @@ def scaling(out_path):
                 cand = torch.randint(0, n_act, (H, K, 65536), dtype=torch.int64, generator=g).cuda()
             else:
                 cand = (torch.rand((H, K, 65536, 1), generator=g) * 2.0 - 1.0).cuda()
-            for _ in range(5):
-                env.lookahead(cand, 0.99)
-            torch.cuda.synchronize()
-            took = []
-            for _ in range(5):
-                t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                t0.record()
-                for _ in range(50):
-                    env.lookahead(cand, 0.99)
-                t1.record()
-                torch.cuda.synchronize()
-                took.append(t0.elapsed_time(t1) / 50 * 1e3)
-            us = sorted(took)[2]
+            us = median_window(torch, lambda: env.lookahead(cand, 0.99), 5, 50, 5)
             lines.append(f"{env_id:26s} K = {K}  {us:9.1f} us  {H * K * 65536 / us * 1e6:.3e} lane-steps/s")
             print(lines[-1], flush=True)
         env.close()
@@ -125,34 +102,12 @@ def main():
         return child()
     if args.scaling:
         return scaling(args.out)
-    builds = [("this", None)] + ([("parent", args.parent)] if args.parent else [])
-    rows = {}
-    lines = []
-    for r in range(args.rounds):
-        for name, lib in (builds if r % 2 == 0 else builds[::-1]):
-            env = dict(os.environ)
-            if lib:
-                env["MI355ENV_LIBRARY"] = lib
-            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child"], env=env, capture_output=True, text=True, timeout=600)
-            hit = [ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")]
-            if p.returncode != 0 or not hit:
-                raise SystemExit(f"{name} child failed ({p.returncode}): {p.stdout[-400:]} {p.stderr[-1200:]}")
-            res = json.loads(hit[-1][7:])
-            for env_id, row in res.items():
-                for what, us in row.items():
-                    rows.setdefault((env_id, name, what), []).append(us)
-            lines.append(f"round {r} {name}: " + json.dumps(res))
-            print(lines[-1], flush=True)
+    rows, lines = run_rounds(__file__, args.rounds, args.parent, timeout=600)
     lines.append("")
     lines.append(f"us per call, {H} steps x 65 536 lanes = 8 388 608 lane-steps; median [min .. max] of {args.rounds} processes")
     for (env_id, name, what), v in sorted(rows.items()):
-        v = sorted(v)
-        lines.append(f"{env_id:12s} {name:6s} {what:16s} {v[len(v) // 2]:9.1f} [{v[0]:9.1f} .. {v[-1]:9.1f}]")
-    text = "\n".join(lines) + "\n"
-    print(text)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write(text)
+        lines.append(f"{env_id:12s} {name:6s} {what:16s} {spread(v, 9)}")
+    finish(lines, args.out)
 
 
 if __name__ == "__main__":

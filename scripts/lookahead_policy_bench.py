@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """lookahead_policy() against the only way to score K closed-loop policies before it, one MI355X, one session.
 
-    python scripts/lookahead_policy_bench.py [--rounds 3] [--out profiles/lookahead_policy_ab.txt]
+    python scripts/lookahead_policy_bench.py [--rounds 3] [--parent PATH/TO/PARENT/libmi355env.so] [--out profiles/lookahead_policy_ab.txt]
 
-Every round is a process of its own (scripts/lookahead_bench.py's scheme).  A process measures, for CartPole-v1 and Pendulum-v1, hidden = 0 and 64,
+Every round is a process of its own, this build's and -- with --parent -- the parent build's interleaved (scripts/bench_rounds.py).  A process measures, for CartPole-v1 and Pendulum-v1, hidden = 0 and 64,
 H = 128, gamma = 0.99 and K x N = 64 x 1024 (65 536 lanes) and 256 x 1024 (262 144 lanes), the time per scored batch -- device events around CALLS
 calls, the variants of a configuration taken in turn window by window, median window -- of
 
@@ -20,8 +20,9 @@ infrastructure only: no test reads its numbers.
 import argparse
 import json
 import os
-import subprocess
 import sys
+
+from bench_rounds import finish, median_window, run_rounds, spread
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 H, WINDOWS, WARMUP = 128, 5, 3
@@ -38,13 +39,7 @@ def child():
     import gymnasium_amd
 
     def timed(call, n):
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        for _ in range(n):
-            call()
-        t1.record()
-        torch.cuda.synchronize()
-        return t0.elapsed_time(t1) / n * 1e3  # us per call
+        return median_window(torch, call, 0, n, 1)  # us per call, one window
 
     def torch_policy(env_id, params, hidden, K, N):
         obs_dim, A = IDS[env_id]
@@ -112,34 +107,19 @@ def child():
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--parent", default=None)
     ap.add_argument("--out", default=None)
     ap.add_argument("--child", action="store_true")
     args = ap.parse_args()
     if args.child:
         return child()
-    rows, lines = {}, []
-    for r in range(args.rounds):
-        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child"], capture_output=True, text=True, timeout=900)
-        hit = [ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")]
-        if p.returncode != 0 or not hit:
-            raise SystemExit(f"child failed ({p.returncode}): {p.stdout[-400:]} {p.stderr[-1600:]}")
-        res = json.loads(hit[-1][7:])
-        for cfg, row in res.items():
-            for what, us in row.items():
-                rows.setdefault((cfg, what), []).append(us)
-        lines.append(f"round {r}: " + json.dumps(res))
-        print(lines[-1], flush=True)
+    rows, lines = run_rounds(__file__, args.rounds, args.parent, timeout=900)
     lines.append("")
     lines.append(f"us per scored batch (K candidates x N sub-environments x {H} steps); median [min .. max] of {args.rounds} processes; x = against `policy`")
-    for (cfg, what), v in sorted(rows.items()):
-        v = sorted(v)
-        base = sorted(rows[(cfg, "policy")])
-        lines.append(f"{cfg:34s} {what:14s} {v[len(v) // 2]:10.1f} [{v[0]:10.1f} .. {v[-1]:10.1f}]  x{v[len(v) // 2] / base[len(base) // 2]:.2f}")
-    text = "\n".join(lines) + "\n"
-    print(text)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write(text)
+    for (cfg, name, what), v in sorted(rows.items()):
+        base = sorted(rows[(cfg, name, "policy")])
+        lines.append(f"{cfg:34s} {name:6s} {what:14s} {spread(v, 10)}  x{sorted(v)[len(v) // 2] / base[len(base) // 2]:.2f}")
+    finish(lines, args.out)
 
 
 if __name__ == "__main__":

@@ -1,10 +1,10 @@
 """What HipVectorEnv.lookahead_policy() must return, by composition of calls that existed before it (shared by tests/test_lookahead_policy_host.py and
-tests/test_gpu_lookahead_policy.py; no tests here): tests/lookahead_cases.py's composition -- K * N sub-environments put into the tiled state and stepped H
+tests/test_gpu_lookahead_policy.py; no tests here): tests/lookahead_cases.py's composition() -- K * N sub-environments put into the tiled state and stepped H
 times -- with the action of every step computed from the observation the composed env last returned, by the network of include/mi355env.h
 (mi_lookahead_policy) restated in NumPy float32.  Over the oracle backend that is the reference's semantics."""
 import numpy as np
 
-from lookahead_cases import BOX_BOUND, CLASSIC_IDS, DISCRETE_ACTIONS, NEEDS_RESET
+from lookahead_cases import BOX_BOUND, CLASSIC_IDS, DISCRETE_ACTIONS, composition
 
 OBS_DIM = {"CartPole-v1": 4, "Pendulum-v1": 3, "Acrobot-v1": 6, "MountainCar-v0": 2, "MountainCarContinuous-v0": 2}
 KIND_ID = {"cartpole": "CartPole-v1", "pendulum": "Pendulum-v1", "acrobot": "Acrobot-v1", "mountain_car": "MountainCar-v0",
@@ -81,42 +81,13 @@ def expected_lookahead_policy(make_env, state, elapsed, flags, present_obs, para
     """lookahead_cases.expected_lookahead with closed-loop actions.  ``present_obs`` [N, obs_dim] float32 is the observation of ``state`` (always
     needed here: it decides the first action); ``params`` [K, P] float32.  Beyond the five outputs the dict holds ``actions`` [H, K, N(, 1)] and ``took``
     [H, K, N] (the candidate took step t), for the conditions a test sets on its inputs."""
-    params = np.asarray(params)
-    state, elapsed, flags = np.asarray(state, np.float64), np.asarray(elapsed, np.int32), np.asarray(flags, np.uint8)
-    present_obs = np.asarray(present_obs)
+    params, present_obs = np.asarray(params), np.asarray(present_obs)
     assert present_obs.dtype == np.float32
-    K, N = params.shape[0], state.shape[0]
-    KN = K * N
-    env = make_env(KN)
-    env_id = KIND_ID[env.KIND]
-    if not env._has_reset:
-        env.reset(seed=0)
-    env.set_state(np.tile(state, (K, 1)), np.tile(elapsed, K), np.tile(flags, K))
-    alive = (np.tile(flags, K) & NEEDS_RESET) == 0
-    G, disc = np.zeros(KN, np.float64), np.ones(KN, np.float64)
-    steps = np.zeros(KN, np.int32)
-    te_last, tr_last = np.zeros(KN, np.bool_), np.zeros(KN, np.bool_)
-    obs = np.tile(present_obs, (K, 1))
-    final = obs.copy()
-    actions, took = [], []
-    for t in range(H):
-        a = policy_actions(env_id, params, hidden, obs)
-        obs, rew, te, tr, _ = env.step(a)
-        obs, rew, te, tr = np.array(obs, np.float32), np.asarray(rew, np.float64), np.asarray(te, np.bool_), np.asarray(tr, np.bool_)
-        go = alive.copy()
-        term = disc * rew  # rounded, then added: the kernel's order
-        G = np.where(go, G + term, G)
-        disc = np.where(go, disc * np.float64(gamma), disc)
-        steps += go
-        te_last, tr_last = np.where(go, te, te_last), np.where(go, tr, tr_last)
-        final[go] = obs[go]
-        actions.append(a), took.append(go)
-        alive &= ~(te | tr)
-    env.close()
+    K, N = params.shape[0], np.asarray(state).shape[0]
+    out, actions, took = composition(make_env, state, elapsed, flags, K, H, gamma,
+                                     lambda t, obs, env: policy_actions(KIND_ID[env.KIND], params, hidden, obs), present_obs)
     actions = np.stack(actions)
-    return {"returns": G.reshape(K, N), "steps": steps.reshape(K, N), "terminated": te_last.reshape(K, N), "truncated": tr_last.reshape(K, N),
-            "final_obs": final.reshape((K, N) + final.shape[1:]), "actions": actions.reshape((H, K, N) + actions.shape[2:]),
-            "took": np.stack(took).reshape(H, K, N)}
+    return dict(out, actions=actions.reshape((H, K, N) + actions.shape[2:]), took=np.stack(took).reshape(H, K, N))
 
 
 def assert_case_is_not_trivial(env_id, want):

@@ -89,7 +89,7 @@ def stale_units(here):
 
 
 @pytest.mark.parametrize("header", ["mj_glue_kernels.h", "lane_common.h", "wrappers_internal.h", "pcg64_dev.h", "action_mask_internal.h",
-                                    "classic_kernels.h", "lane_step.h", "tabular_kernels.h",
+                                    "classic_kernels.h", "lane_step.h", "tabular_kernels.h", "candidate_lane.h",
                                     os.path.join("generated", "mjx_models.h"), os.path.join("..", "..", "include", "mi355env.h")])
 def test_touching_a_header_makes_its_includers_stale(copied_tree, header):
     os.utime(os.path.join(copied_tree, header), (1_000_200, 1_000_200))
@@ -108,6 +108,8 @@ def test_touching_a_header_makes_its_includers_stale(copied_tree, header):
         assert "classic.hip" in expected and "engine.hip" not in expected
     if header == "tabular_kernels.h":
         assert expected == {"tabular.hip"}
+    if header == "candidate_lane.h":
+        assert expected == {"lookahead.hip", "lookahead_policy.hip"}
 
 
 def test_touching_a_unit_or_the_build_script(copied_tree):

@@ -8,35 +8,12 @@ import numpy as np
 import pytest
 import torch
 
-import gymnasium_amd
-from lookahead_cases import (CLASSIC_IDS, NEEDS_RESET, acrobot_near_height, cartpole_near_thresholds, expected_lookahead,
-                             mountaincar_near_goal, random_actions)
+from lookahead_cases import (CLASSIC_IDS, KEYS, NEEDS_RESET, acrobot_near_height, assert_equal, cartpole_near_thresholds, composed_on_device, device_env,
+                             expected_lookahead, host, mountaincar_near_goal, oracle_env, random_actions)
 
 pytestmark = pytest.mark.gpu
 
 SHAPES = [(130, 3, 9, 1.0), (1, 1, 1, 1.0), (64, 1, 2, 1.0), (77, 5, 9, 0.97)]  # (N, K, H, gamma): 390 lanes are neither a wavefront nor a workgroup multiple
-KEYS = ("returns", "steps", "terminated", "truncated", "final_obs")
-
-
-def oracle_env(env_id, **kw):
-    from oracle import oracle
-
-    return lambda n: gymnasium_amd.make_vec(env_id, num_envs=n, _engine_factory=oracle.engine_factory, **kw)
-
-
-def device_env(env_id, n, **kw):
-    return gymnasium_amd.make_vec(env_id, num_envs=n, device=0, output="torch", **kw)
-
-
-def host(out):
-    return {k: v.cpu().numpy() for k, v in out.items()}
-
-
-def assert_equal(got, want, what):
-    for k in KEYS:
-        assert got[k].dtype == want[k].dtype and got[k].shape == want[k].shape, (what, k, got[k].dtype, got[k].shape)
-        bad = np.flatnonzero((got[k] != want[k]).reshape(got[k].shape[0] * got[k].shape[1], -1).any(axis=1))
-        assert np.array_equal(got[k], want[k]), (what, k, bad[:6], got[k].reshape(-1)[:4], want[k].reshape(-1)[:4])
 
 
 def reached_state(env_id, N, seed, warm, **kw):
@@ -197,21 +174,6 @@ def test_the_env_is_untouched(env_id):
     a.close(), b.close()
 
 
-def composed_on_device(env_id, attrs, words=None, **kw):
-    """make_env of expected_lookahead on the device engine: the K * N sub-environments carry the tiled attributes (and, with `words`, every copy of
-    row i carries row i's generator)."""
-    def make_env(n):
-        env = gymnasium_amd.make_vec(env_id, num_envs=n, device=0, **kw)
-        env.reset(seed=0)
-        reps = n // len(next(iter(attrs.values())))
-        for name, values in attrs.items():
-            env.set_attr(name, list(values) * reps)
-        if words is not None:
-            env._engine.seed(np.tile(words, (reps, 1)))
-        return env
-    return make_env
-
-
 @pytest.mark.parametrize("env_id,name,lo,hi", [("CartPole-v1", "length", 0.25, 1.0), ("Pendulum-v1", "g", 2.0, 12.0)])
 def test_attributes_of_the_candidates_own_sub_environment(env_id, name, lo, hi):
     N, K, H, gamma = 77, 5, 9, 0.97
@@ -269,3 +231,43 @@ def test_an_invalid_discrete_action_is_reported_at_synchronize():
         gpu.synchronize()
     assert all(np.array_equal(x, y) for x, y in zip(before, gpu.get_state()))
     gpu.close()
+
+
+def test_entry_points_refuse_with_their_exact_messages():
+    """mi_lookahead and mi_lookahead_policy called through the binding, past HipVectorEnv's own validation: the checks the two entry points share
+    (engine.hip) and those they keep, each with its status and its full text.  No call here launches a kernel."""
+    from gymnasium_amd import _native
+
+    INVALID, STATE = -1, -5  # MI_ERR_INVALID_ARGUMENT, MI_ERR_STATE (include/mi355env.h)
+
+    def refused(call, code, text):
+        with pytest.raises(_native.NativeError) as e:
+            call()
+        assert (e.value.code, e.value.message) == (code, text)
+
+    gpu = device_env("CartPole-v1", 2)
+    eng = gpu._engine
+    ptr = torch.zeros(64, dtype=torch.int64, device="cuda:0").data_ptr()  # (never read)
+    refused(lambda: eng.lookahead(ptr, 3, 2, 0.9), STATE, "lookahead before reset")
+    refused(lambda: eng.lookahead_policy(ptr, 0, 3, 2, 0.9), STATE, "lookahead_policy before reset")
+    gpu.reset(seed=0)
+    before = gpu.get_state()
+    for name, call in (("mi_lookahead", lambda H, K, gamma, p=ptr: eng.lookahead(p, H, K, gamma)),
+                       ("mi_lookahead_policy", lambda H, K, gamma, p=ptr, hidden=0: eng.lookahead_policy(p, hidden, H, K, gamma))):
+        refused(lambda: call(0, 2, 0.9), INVALID, f"{name}: horizon and candidates must be >= 1")
+        refused(lambda: call(3, 0, 0.9), INVALID, f"{name}: horizon and candidates must be >= 1")
+        refused(lambda: call(3, 2, 1.5), INVALID, f"{name}: gamma must be in [0, 1]")
+        refused(lambda: call(3, 2, float("nan")), INVALID, f"{name}: gamma must be in [0, 1]")
+        what = "actions" if name == "mi_lookahead" else "params"
+        refused(lambda: call(3, 2, 0.9, p=None), INVALID, f"{name}: {what} must not be NULL")
+        refused(lambda: call(3, 2 ** 30, 0.9), INVALID, f"{name}: candidates * num_envs must be < 2^31")
+    refused(lambda: eng.lookahead_policy(ptr, 257, 3, 2, 0.9), INVALID, "mi_lookahead_policy: hidden must be in [0, 256]")
+    refused(lambda: eng.lookahead_policy(ptr, 257, 0, 2, 0.9), INVALID, "mi_lookahead_policy: hidden must be in [0, 256]")  # (hidden is tested before the horizon)
+    refused(lambda: eng.lookahead(None, 0, 2, 0.9), INVALID, "mi_lookahead: actions must not be NULL")  # (... and the pointer before both)
+    assert all(np.array_equal(x, y) for x, y in zip(before, gpu.get_state()))
+    gpu.close()
+    box = device_env("Pendulum-v1", 2)
+    box.reset(seed=0)
+    refused(lambda: box._engine.lookahead(ptr, 3, 2, 0.9, actions_dtype=_native.MI_I64), INVALID, "actions_dtype must be MI_F32, MI_F64 or MI_F64_WEAK")
+    refused(lambda: box._engine.lookahead(ptr, 3, 2, 1.5, actions_dtype=_native.MI_I64), INVALID, "mi_lookahead: gamma must be in [0, 1]")  # (gamma first)
+    box.close()

@@ -11,14 +11,13 @@ import numpy as np
 import pytest
 import torch
 
-import gymnasium_amd
-from lookahead_cases import CLASSIC_IDS, DISCRETE_ACTIONS, NEEDS_RESET, acrobot_near_height, cartpole_near_thresholds, mountaincar_near_goal
+from lookahead_cases import (CLASSIC_IDS, DISCRETE_ACTIONS, KEYS, NEEDS_RESET, acrobot_near_height, assert_equal, cartpole_near_thresholds, composed_on_device,
+                             device_env, host, mountaincar_near_goal, oracle_env)
 from lookahead_policy_cases import (assert_case_is_not_trivial, expected_lookahead_policy, param_size, policy_actions, policy_logits,
                                     random_params)
 
 pytestmark = pytest.mark.gpu
 
-KEYS = ("returns", "steps", "terminated", "truncated", "final_obs")
 PATH_VAR = "MI355ENV_LOOKAHEAD_POLICY_PATH"
 NEAR = {"CartPole-v1": cartpole_near_thresholds, "MountainCar-v0": functools.partial(mountaincar_near_goal, goal=0.5),
         "MountainCarContinuous-v0": functools.partial(mountaincar_near_goal, goal=0.45), "Acrobot-v1": acrobot_near_height}
@@ -32,25 +31,7 @@ def scale(env_id, hidden):
     return 2.0 if env_id == "Pendulum-v1" else 1.0
 
 
-def oracle_env(env_id, **kw):
-    from oracle import oracle
-
-    return lambda n: gymnasium_amd.make_vec(env_id, num_envs=n, _engine_factory=oracle.engine_factory, **kw)
-
-
-def device_env(env_id, n, **kw):
-    return gymnasium_amd.make_vec(env_id, num_envs=n, device=0, output="torch", **kw)
-
-
-def host(out):
-    return {k: v.cpu().numpy() for k, v in out.items()}
-
-
-def assert_equal(got, want, what):
-    for k in KEYS:
-        assert got[k].dtype == want[k].dtype and got[k].shape == want[k].shape, (what, k, got[k].dtype, got[k].shape)
-        bad = np.flatnonzero((got[k] != want[k]).reshape(got[k].shape[0] * got[k].shape[1], -1).any(axis=1))
-        assert np.array_equal(got[k], want[k], equal_nan=True), (what, k, bad[:6], got[k].reshape(-1)[:4], want[k].reshape(-1)[:4])
+assert_equal = functools.partial(assert_equal, equal_nan=True)  # (test_ties_and_nan_logits makes NaN observations on both sides)
 
 
 @functools.lru_cache(maxsize=None)
@@ -266,21 +247,6 @@ def test_ties_and_nan_logits(env_id, hidden):
 
 
 # -- attributes, the generator ----------------------------------------------------------------------------------------------------------------------------
-def composed_on_device(env_id, attrs, words=None, **kw):
-    """make_env of expected_lookahead_policy on the device engine: the K * N sub-environments carry the tiled attributes (and, with `words`, every copy
-    of row i carries row i's generator)."""
-    def make_env(n):
-        env = gymnasium_amd.make_vec(env_id, num_envs=n, device=0, **kw)
-        env.reset(seed=0)
-        reps = n // len(next(iter(attrs.values())))
-        for name, values in attrs.items():
-            env.set_attr(name, list(values) * reps)
-        if words is not None:
-            env._engine.seed(np.tile(words, (reps, 1)))
-        return env
-    return make_env
-
-
 @pytest.mark.parametrize("env_id,name,lo,hi", [("CartPole-v1", "length", 0.25, 1.0), ("Pendulum-v1", "g", 2.0, 12.0), ("MountainCar-v0", "force", 0.0005, 0.002),
                                                ("MountainCarContinuous-v0", "power", 0.001, 0.002), ("Acrobot-v1", "LINK_MASS_2", 0.8, 1.2)])
 def test_attributes_of_the_candidates_own_sub_environment(env_id, name, lo, hi):

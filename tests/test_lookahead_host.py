@@ -3,8 +3,6 @@ ctypes mirror of mi_lookahead_io against the header, the wrappers' refusal, and 
 scalar loop.  What the kernel computes is a GPU matter (tests/test_gpu_lookahead.py)."""
 import ctypes
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,19 +12,8 @@ import gymnasium_amd
 from gymnasium_amd import _native, wrappers
 from gymnasium_amd.gym_api import error
 from conftest import ROOT
-from lookahead_cases import CLASSIC_IDS, cartpole_near_thresholds, expected_lookahead, random_actions
-
-
-def make(env_id, factory, n=4, **kw):
-    kw.setdefault("output", "torch")
-    return gymnasium_amd.make_vec(env_id, num_envs=n, _engine_factory=factory, **kw)
-
-
-def good_actions(env, H=3, K=2):
-    n = env.num_envs
-    if env._discrete:
-        return torch.zeros((H, K, n), dtype=torch.int64)
-    return torch.zeros((H, K, n, 1), dtype=torch.float32)
+from lookahead_cases import (CLASSIC_IDS, KINDS_AND_MODES_WITHOUT, METHODS, cartpole_near_thresholds, check_struct_layout, expected_lookahead, good_actions, make,
+                             random_actions)
 
 
 # -- the binding --------------------------------------------------------------------------------------------------------------------------------
@@ -42,20 +29,7 @@ def test_entry_point_is_a_host_symbol_of_abi_10():
 def test_struct_layout_matches_the_header(tmp_path):
     ct = _native.MiLookaheadIO
     assert ctypes.sizeof(ct) == 2 * 4 + 6 * 8 + 2 * 4 + 8
-    if shutil.which("gcc") is None:
-        pytest.skip("no C compiler to cross-check the offsets with")
-    lines = ["#include <stdio.h>", "#include <stddef.h>", f'#include "{os.path.join(ROOT, "include", "mi355env.h")}"', "int main(void) {",
-             'printf("size %zu\\n", sizeof(mi_lookahead_io));']
-    for fname, _ in ct._fields_:
-        lines.append(f'printf("{fname} %zu\\n", offsetof(mi_lookahead_io, {fname}));')
-    lines.append("return 0; }")
-    src = tmp_path / "layout.c"
-    src.write_text("\n".join(lines))
-    subprocess.run(["gcc", "-o", str(tmp_path / "layout"), str(src)], check=True)
-    out = dict(line.split() for line in subprocess.run([str(tmp_path / "layout")], check=True, capture_output=True, text=True).stdout.splitlines())
-    assert int(out["size"]) == ctypes.sizeof(ct)
-    for fname, _ in ct._fields_:
-        assert int(out[fname]) == getattr(ct, fname).offset, fname
+    check_struct_layout(ct, "mi_lookahead_io", os.path.join(ROOT, "include", "mi355env.h"), tmp_path)
 
 
 # -- refusals -------------------------------------------------------------------------------------------------------------------------------------
@@ -72,17 +46,17 @@ def test_checker_backend_needs_the_device_engine(oracle_factory, env_id):
     env.close()
 
 
-def test_numpy_output_is_refused(oracle_factory):
+@pytest.mark.parametrize("method", sorted(METHODS))
+def test_numpy_output_is_refused(oracle_factory, method):
+    good, call, _ = METHODS[method]
     env = make("CartPole-v1", oracle_factory, output="numpy")
     env.reset(seed=0)
     with pytest.raises(error.Error, match="output='torch'"):
-        env.lookahead(np.zeros((2, 2, 4), dtype=np.int64))
+        call(env, good(env).numpy())
     env.close()
 
 
-@pytest.mark.parametrize("env_id,kw,why", [("HalfCheetah-v5", {}, "MuJoCo and ToyText"), ("FrozenLake-v1", {}, "MuJoCo and ToyText"),
-                                           ("Blackjack-v1", {}, "MuJoCo and ToyText"), ("CartPole-v1", {"rng": "shared"}, "rng='shared'"),
-                                           ("Pendulum-v1", {"fast_math": True}, "fast_math")])
+@pytest.mark.parametrize("env_id,kw,why", KINDS_AND_MODES_WITHOUT)
 def test_kinds_and_modes_without_lookahead(oracle_factory, env_id, kw, why):
     env = make(env_id, oracle_factory, **kw)
     env.reset(seed=0)
@@ -91,50 +65,59 @@ def test_kinds_and_modes_without_lookahead(oracle_factory, env_id, kw, why):
     env.close()
 
 
-def test_envs_that_step_through_wrappers_are_refused(oracle_factory, monkeypatch):
+# (the refusals below are the same for both methods but for the name: one test over both, tests/test_lookahead_policy_host.py has none of them)
+@pytest.mark.parametrize("method", sorted(METHODS))
+def test_envs_that_step_through_wrappers_are_refused(oracle_factory, monkeypatch, method):
+    good, call, nothing_else = METHODS[method]
     env = make("CartPole-v1", oracle_factory)
     env.reset(seed=0)
-    a = good_actions(env)
+    x = good(env)
     monkeypatch.setattr(env, "_step_wrappers", (2, 0.0, 0), raising=False)
     with pytest.raises(error.Error, match="set_step_wrappers"):
-        env.lookahead(a)
+        call(env, x)
     monkeypatch.setattr(env, "_step_wrappers", (0, 0.25, 3), raising=False)
     with pytest.raises(error.Error, match="set_step_wrappers"):
-        env.lookahead(a)
+        call(env, x)
     monkeypatch.setattr(env, "_step_wrappers", (0, 0.0, 0), raising=False)
     monkeypatch.setattr(env, "_max_and_skip", 4, raising=False)
     with pytest.raises(error.Error, match="set_max_and_skip"):
-        env.lookahead(a)
+        call(env, x)
     monkeypatch.setattr(env, "_max_and_skip", 0, raising=False)
     env._fusion_state()["chain"].append(("obs", object()))  # what a fused NormalizeObservation registers (HipVectorEnv._fuse)
     with pytest.raises(error.Error, match="fused"):
-        env.lookahead(a)
+        call(env, x)
     env._fusion_state()["chain"].clear()
-    with pytest.raises(error.Error, match="mi_lookahead"):  # nothing else stands in the way
-        env.lookahead(a)
+    with pytest.raises(error.Error, match=nothing_else):  # nothing else stands in the way
+        call(env, x)
     env.close()
 
 
-def test_before_reset_and_after_close(oracle_factory):
+@pytest.mark.parametrize("method", sorted(METHODS))
+def test_before_reset_and_after_close(oracle_factory, method):
+    good, call, _ = METHODS[method]
     env = make("CartPole-v1", oracle_factory)
+    x = good(env)
     with pytest.raises(AssertionError, match="reset"):
-        env.lookahead(good_actions(env))
+        call(env, x)
     env.reset(seed=0)
     env.close()
     with pytest.raises(error.ClosedEnvironmentError):
-        env.lookahead(good_actions(env))
+        call(env, x)
 
 
-def test_wrappers_refuse_and_name_the_unwrapped_call(oracle_factory):
+@pytest.mark.parametrize("method", sorted(METHODS))
+def test_wrappers_refuse_and_name_the_unwrapped_call(oracle_factory, method):
+    good, call, _ = METHODS[method]
     env = make("CartPole-v1", oracle_factory)
     env.reset(seed=0)
-    a = good_actions(env)
+    x = good(env)
+    more = {"hidden": 0} if method == "lookahead_policy" else {}
     for w in (wrappers.RecordEpisodeStatistics(env), wrappers.ClipReward(env, -1.0, 1.0), wrappers.TransformReward(env, lambda r: r),
               wrappers.NumpyToTorch(wrappers.VectorWrapper(env))):
-        with pytest.raises(error.Error, match=r"env\.unwrapped\.lookahead"):
-            w.lookahead(a)
-        with pytest.raises(error.Error, match=r"env\.unwrapped\.lookahead"):
-            w.lookahead(a, 0.9, final_obs=True)
+        with pytest.raises(error.Error, match=rf"env\.unwrapped\.{method}\b"):
+            call(w, x)
+        with pytest.raises(error.Error, match=rf"env\.unwrapped\.{method}\b"):
+            call(w, x, 0.9, final_obs=True, **more)
     env.close()
 
 
@@ -156,12 +139,14 @@ def test_discrete_actions_are_validated(oracle_factory):
     env.close()
 
 
-def test_candidates_times_envs_must_fit_31_bits(oracle_factory):
+@pytest.mark.parametrize("method", sorted(METHODS))
+def test_candidates_times_envs_must_fit_31_bits(oracle_factory, method):
+    good, call, _ = METHODS[method]
     env = make("CartPole-v1", oracle_factory, n=4)
     env.reset(seed=0)
-    a = torch.zeros((1, 1, 4), dtype=torch.int64).expand(1, 2 ** 29, 4)  # (a view: no memory behind the 2^31 lanes)
+    x = good(env, K=1)  # expanded along K: a view, no memory behind the 2^31 lanes
     with pytest.raises(ValueError, match=r"K \* N < 2\*\*31"):
-        env.lookahead(a)
+        call(env, x.expand(-1, 2 ** 29, -1) if method == "lookahead" else x.expand(2 ** 29, -1))
     env.close()
 
 
@@ -181,19 +166,21 @@ def test_box_actions_are_validated(oracle_factory, env_id):
     env.close()
 
 
-def test_gamma_is_validated(oracle_factory):
+@pytest.mark.parametrize("method", sorted(METHODS))
+def test_gamma_is_validated(oracle_factory, method):
+    good, call, needs_engine = METHODS[method]
     env = make("CartPole-v1", oracle_factory)
     env.reset(seed=0)
-    a = good_actions(env)
+    x = good(env)
     for bad in (-0.01, 1.0000001, float("nan"), float("inf"), 2):
         with pytest.raises(ValueError, match="gamma"):
-            env.lookahead(a, bad)
+            call(env, x, bad)
     for bad in ("0.9", None, True, [0.9]):
         with pytest.raises(TypeError, match="gamma"):
-            env.lookahead(a, bad)
+            call(env, x, bad)
     for ok in (0, 1, 0.0, 1.0, np.float64(0.5), np.float32(0.25)):
-        with pytest.raises(error.Error, match="mi_lookahead"):
-            env.lookahead(a, ok)
+        with pytest.raises(error.Error, match=needs_engine):
+            call(env, x, ok)
     env.close()
 
 

@@ -1,34 +1,23 @@
 """CPU side of HipVectorEnv.lookahead_policy(): every refusal and validation error, the checker backend being told apart by the missing entry point, the
-ctypes mirror of mi_lookahead_policy_io against the header, the wrappers' refusal, policy_param_layout, and the shared helper
+ctypes mirror of mi_lookahead_policy_io against the header, policy_param_layout, and the shared helper
 (tests/lookahead_policy_cases.py) against a hand-written scalar loop and a float64 evaluation.  What the kernel computes is a GPU matter
 (tests/test_gpu_lookahead_policy.py)."""
 import ctypes
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 import gymnasium_amd
-from gymnasium_amd import _native, wrappers
+from gymnasium_amd import _native
 from gymnasium_amd.gym_api import error
 from conftest import ROOT
-from lookahead_cases import CLASSIC_IDS, DISCRETE_ACTIONS, cartpole_near_thresholds
+from lookahead_cases import CLASSIC_IDS, DISCRETE_ACTIONS, KINDS_AND_MODES_WITHOUT, cartpole_near_thresholds, check_struct_layout, good_params, make
 from lookahead_policy_cases import (OBS_DIM, expected_lookahead_policy, n_outputs, param_size, policy_actions, policy_logits, random_params,
                                     split_params)
 
 NEEDS_ENGINE = r"needs the device engine \(mi_lookahead_policy\)"
-
-
-def make(env_id, factory, n=4, **kw):
-    kw.setdefault("output", "torch")
-    return gymnasium_amd.make_vec(env_id, num_envs=n, _engine_factory=factory, **kw)
-
-
-def good_params(env, K=2, hidden=0):
-    return torch.zeros((K, env.policy_param_layout(hidden)["size"]), dtype=torch.float32)
 
 
 # -- the binding --------------------------------------------------------------------------------------------------------------------------------
@@ -47,20 +36,7 @@ def test_struct_layout_matches_the_header(tmp_path):
     assert [f for f, _ in ct._fields_] == ["struct_size", "params", "returns", "steps", "terminated", "truncated", "final_obs", "horizon", "candidates",
                                            "hidden", "gamma"]
     assert ctypes.sizeof(ct) == 8 + 6 * 8 + 3 * 4 + 4 + 8
-    if shutil.which("gcc") is None:
-        pytest.skip("no C compiler to cross-check the offsets with")
-    lines = ["#include <stdio.h>", "#include <stddef.h>", f'#include "{os.path.join(ROOT, "include", "mi355env.h")}"', "int main(void) {",
-             'printf("size %zu\\n", sizeof(mi_lookahead_policy_io));']
-    for fname, _ in ct._fields_:
-        lines.append(f'printf("{fname} %zu\\n", offsetof(mi_lookahead_policy_io, {fname}));')
-    lines.append("return 0; }")
-    src = tmp_path / "layout.c"
-    src.write_text("\n".join(lines))
-    subprocess.run(["gcc", "-o", str(tmp_path / "layout"), str(src)], check=True)
-    out = dict(line.split() for line in subprocess.run([str(tmp_path / "layout")], check=True, capture_output=True, text=True).stdout.splitlines())
-    assert int(out["size"]) == ctypes.sizeof(ct)
-    for fname, _ in ct._fields_:
-        assert int(out[fname]) == getattr(ct, fname).offset, fname
+    check_struct_layout(ct, "mi_lookahead_policy_io", os.path.join(ROOT, "include", "mi355env.h"), tmp_path)
 
 
 # -- policy_param_layout ------------------------------------------------------------------------------------------------------------------------
@@ -118,70 +94,12 @@ def test_checker_backend_needs_the_device_engine(oracle_factory, env_id):
     env.close()
 
 
-def test_numpy_output_is_refused(oracle_factory):
-    env = make("CartPole-v1", oracle_factory, output="numpy")
-    env.reset(seed=0)
-    with pytest.raises(error.Error, match="output='torch'"):
-        env.lookahead_policy(np.zeros((2, 10), dtype=np.float32), 3)
-    env.close()
-
-
-@pytest.mark.parametrize("env_id,kw,why", [("HalfCheetah-v5", {}, "MuJoCo and ToyText"), ("FrozenLake-v1", {}, "MuJoCo and ToyText"),
-                                           ("Blackjack-v1", {}, "MuJoCo and ToyText"), ("CartPole-v1", {"rng": "shared"}, "rng='shared'"),
-                                           ("Pendulum-v1", {"fast_math": True}, "fast_math")])
+@pytest.mark.parametrize("env_id,kw,why", KINDS_AND_MODES_WITHOUT)
 def test_kinds_and_modes_without_lookahead(oracle_factory, env_id, kw, why):
     env = make(env_id, oracle_factory, **kw)
     env.reset(seed=0)
     with pytest.raises(error.Error, match=why):
         env.lookahead_policy(torch.zeros((2, 10), dtype=torch.float32), 3)
-    env.close()
-
-
-def test_envs_that_step_through_wrappers_are_refused(oracle_factory, monkeypatch):
-    env = make("CartPole-v1", oracle_factory)
-    env.reset(seed=0)
-    p = good_params(env)
-    monkeypatch.setattr(env, "_step_wrappers", (2, 0.0, 0), raising=False)
-    with pytest.raises(error.Error, match="set_step_wrappers"):
-        env.lookahead_policy(p, 3)
-    monkeypatch.setattr(env, "_step_wrappers", (0, 0.25, 3), raising=False)
-    with pytest.raises(error.Error, match="set_step_wrappers"):
-        env.lookahead_policy(p, 3)
-    monkeypatch.setattr(env, "_step_wrappers", (0, 0.0, 0), raising=False)
-    monkeypatch.setattr(env, "_max_and_skip", 4, raising=False)
-    with pytest.raises(error.Error, match="set_max_and_skip"):
-        env.lookahead_policy(p, 3)
-    monkeypatch.setattr(env, "_max_and_skip", 0, raising=False)
-    env._fusion_state()["chain"].append(("obs", object()))  # what a fused NormalizeObservation registers (HipVectorEnv._fuse)
-    with pytest.raises(error.Error, match="fused"):
-        env.lookahead_policy(p, 3)
-    env._fusion_state()["chain"].clear()
-    with pytest.raises(error.Error, match=NEEDS_ENGINE):  # nothing else stands in the way
-        env.lookahead_policy(p, 3)
-    env.close()
-
-
-def test_before_reset_and_after_close(oracle_factory):
-    env = make("CartPole-v1", oracle_factory)
-    with pytest.raises(AssertionError, match="reset"):
-        env.lookahead_policy(good_params(env), 3)
-    env.reset(seed=0)
-    p = good_params(env)
-    env.close()
-    with pytest.raises(error.ClosedEnvironmentError):
-        env.lookahead_policy(p, 3)
-
-
-def test_wrappers_refuse_and_name_the_unwrapped_call(oracle_factory):
-    env = make("CartPole-v1", oracle_factory)
-    env.reset(seed=0)
-    p = good_params(env)
-    for w in (wrappers.RecordEpisodeStatistics(env), wrappers.ClipReward(env, -1.0, 1.0), wrappers.TransformReward(env, lambda r: r),
-              wrappers.NumpyToTorch(wrappers.VectorWrapper(env))):
-        with pytest.raises(error.Error, match=r"env\.unwrapped\.lookahead_policy"):
-            w.lookahead_policy(p, 3)
-        with pytest.raises(error.Error, match=r"env\.unwrapped\.lookahead_policy"):
-            w.lookahead_policy(p, 3, 0.9, hidden=0, final_obs=True)
     env.close()
 
 
@@ -232,31 +150,6 @@ def test_hidden_and_horizon_are_validated(oracle_factory):
     for hidden in (1, 256):
         with pytest.raises(error.Error, match=NEEDS_ENGINE):
             env.lookahead_policy(good_params(env, 2, hidden), np.int64(1), hidden=hidden)
-    env.close()
-
-
-def test_candidates_times_envs_must_fit_31_bits(oracle_factory):
-    env = make("CartPole-v1", oracle_factory, n=4)
-    env.reset(seed=0)
-    p = torch.zeros((1, 10), dtype=torch.float32).expand(2 ** 29, 10)  # (a view: no memory behind the 2^31 lanes)
-    with pytest.raises(ValueError, match=r"K \* N < 2\*\*31"):
-        env.lookahead_policy(p, 1)
-    env.close()
-
-
-def test_gamma_is_validated(oracle_factory):
-    env = make("CartPole-v1", oracle_factory)
-    env.reset(seed=0)
-    p = good_params(env)
-    for bad in (-0.01, 1.0000001, float("nan"), float("inf"), 2):
-        with pytest.raises(ValueError, match="gamma"):
-            env.lookahead_policy(p, 3, bad)
-    for bad in ("0.9", None, True, [0.9]):
-        with pytest.raises(TypeError, match="gamma"):
-            env.lookahead_policy(p, 3, bad)
-    for ok in (0, 1, 0.0, 1.0, np.float64(0.5), np.float32(0.25)):
-        with pytest.raises(error.Error, match=NEEDS_ENGINE):
-            env.lookahead_policy(p, 3, ok)
     env.close()
 
 
